@@ -13,14 +13,19 @@ bytes are the same).  With N > 1 every rank encodes its own batches (image
 parallel, weak scaling, no data-path collective) and one RCCL gather at the end of the
 timed region concatenates the bitstream on rank 0.
 
-Prints ONE JSON line on rank 0 (contract in the task description), including
+The timed region is exactly --steps steps after --warmup steps.  Prints ONE JSON line on rank 0 (contract in the
+task description); a plain run measures only what that line's headline (`value`, `ms_per_step`) needs.  `--full`
+adds, after the timed region, what takes runs of its own:
   roofline      -- the dominant kernel class (the tower GEMMs -- gemm_w8_kernel for QKV / c_fc, gemm_q4_kernel for the residual layers; MFMA bound): algorithmic
-                   FLOPs / HIP-event time measured live over the timed steps on the launch
+                   FLOPs / HIP-event time measured over extra passes of the timed size on the launch
                    stream, against the dense fp16 MFMA peak
   cpu_baseline  -- the CPU oracle (PIL resize + fp32 torch-CPU tower + C rANS, BASELINE configs[0]
-                   shape) timed on this box's host cores on a bounded sample (rank 0, N = 1 only)
+                   shape) timed on the host's cores on a bounded sample (rank 0, N = 1 only)
   verified      -- after the timed region, the records of the timed batch are compared with the CPU
-                   oracle's coding of the same embeddings, and 8 embeddings with the fp32 CPU tower
+                   oracle's coding of the same embeddings, and 32 embeddings with the fp32 CPU tower
+  shipped_affine and the *_stage legs -- the checkpoint's own affine, the entropy stage, preprocessing, the
+                   hyperprior coder, STL10-shaped inputs, the reference's call and the RN50 tower, each timed alone
+`--dump-outputs DIR` writes the records of the last timed step as .npy files (dump_outputs).
 
 `python bench.py --gpus N` starts its own N ranks (torch.distributed.run on 127.0.0.1); under a
 launcher (RANK / WORLD_SIZE set) it is one of the ranks.
@@ -44,14 +49,32 @@ CLIP_MEAN = (0.48145466, 0.4578275, 0.40821073)
 CLIP_STD = (0.26862954, 0.26130258, 0.27577711)
 
 
-def synth_batch(B, seed, device):
-    """u8 ~ U{0..255} i.i.d. (seeded) -> CLIP-normalised fp16, NHWC (SURVEY.md 8d config 2)."""
+def _synth_u8(B, seed):
     import torch
     g = torch.Generator().manual_seed(seed)
-    u8 = torch.randint(0, 256, (B, 224, 224, 3), generator=g, dtype=torch.uint8).to(device)
+    return torch.randint(0, 256, (B, 224, 224, 3), generator=g, dtype=torch.uint8)
+
+
+def _normalise(u8, device):
+    import torch
+    u8 = u8.to(device)
     mean = torch.tensor(CLIP_MEAN, device=device)
     std = torch.tensor(CLIP_STD, device=device)
     return ((u8.float() / 255 - mean) / std).half().contiguous()
+
+
+def synth_batch(B, seed, device):
+    """u8 ~ U{0..255} i.i.d. (seeded) -> CLIP-normalised fp16, NHWC (SURVEY.md 8d config 2)."""
+    return _normalise(_synth_u8(B, seed), device)
+
+
+def synth_batches(specs, device):
+    """[synth_batch(B, seed, device) for (B, seed) in specs], the same images: the host's random draws (~1 s per
+    1024 images, one generator each) run on threads of their own, so that set-up does not grow with the batches."""
+    from concurrent.futures import ThreadPoolExecutor
+    with ThreadPoolExecutor(max(1, min(len(specs), 16))) as ex:
+        u8 = list(ex.map(lambda s: _synth_u8(*s), specs))
+    return [_normalise(u, device) for u in u8]
 
 
 def cpu_baseline(batch=32, min_seconds=10.0, max_seconds=30.0):
@@ -189,6 +212,34 @@ def verify_first_batch(comp, x):
     return out
 
 
+DUMP_LIMIT_BYTES = 64 << 20
+
+
+def dump_outputs(dirname, body, n_images, world, batch):
+    """--dump-outputs: what the timed loop handed its caller for the images of its last step on every rank -- their
+    container records (4-byte big-endian length + rANS payload per image, in image order; ranks in rank order),
+    the bytes of a compress_dataset file -- as float32: DIR/records.npy (the bytes) and DIR/record_bytes.npy (each
+    record's length).  Beyond DUMP_LIMIT_BYTES the first records that fit are kept."""
+    import struct
+    import numpy as np
+    body = np.ascontiguousarray(body, dtype=np.uint8)
+    ends = np.empty(n_images, np.int64)
+    pos = 0
+    for i in range(n_images):
+        pos += 4 + struct.unpack_from(">I", body, pos)[0]
+        ends[i] = pos
+    assert pos == body.size, f"{body.size} record bytes, {pos} parsed"
+    per_rank = n_images // world
+    last = np.concatenate([np.arange(r * per_rank + per_rank - batch, (r + 1) * per_rank) for r in range(world)])
+    lengths = ends[last] - np.where(last > 0, ends[last - 1], 0)
+    keep = int(np.searchsorted(np.cumsum(lengths) * 4 + 4 * np.arange(1, last.size + 1), DUMP_LIMIT_BYTES, "right"))
+    last, lengths = last[:keep], lengths[:keep]
+    records = np.concatenate([body[e - n:e] for e, n in zip(ends[last], lengths)])
+    os.makedirs(dirname, exist_ok=True)
+    np.save(os.path.join(dirname, "records.npy"), records.astype(np.float32))
+    np.save(os.path.join(dirname, "record_bytes.npy"), lengths.astype(np.float32))
+
+
 def kernel_source_sha():
     """Tag of the kernel sources a committed counter profile belongs to: sha256 over csrc/*.{hip,h,cpp} + the
     C-ABI header (the GPU box has no .git, so a commit id cannot be checked there)."""
@@ -218,9 +269,8 @@ def calibrate_affine_(comp, device, images=4096, batch=1024, seed0=1000, spread=
         k = np.arange(n - 2) + off[c]
         pm[c] = (w * k).sum()
         ps[c] = np.sqrt((w * (k - pm[c]) ** 2).sum())
-    zs = []
-    for i in range(0, images, batch):
-        zs.append(comp.clip(synth_batch(min(batch, images - i), seed0 + i // batch, device)).float())
+    zs = [comp.clip(xb).float() for xb in synth_batches(
+        [(min(batch, images - i), seed0 + i // batch) for i in range(0, images, batch)], device)]
     z = torch.cat(zs).double().cpu().numpy()
     m, sd = z.mean(0), z.std(0)
     es = spread * ps / sd
@@ -265,6 +315,12 @@ def main():
     ap.add_argument("--batch", type=int, default=1024, help="images per step per GPU")
     ap.add_argument("--chunk", type=int, default=0, help="images per tower slice (0 = default)")
     ap.add_argument("--layout", choices=["nhwc", "nchw"], default="nhwc")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed region, also measure and check what the headline does not need: roofline "
+                         "passes, CPU baseline, shipped affine, oracle check, the other stages (each --no-* below "
+                         "drops one of them)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default="",
+                    help="write the records of the last timed step to DIR/*.npy (float32)")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--backend", choices=["nccl", "gloo"], default="nccl")
     ap.add_argument("--dataset-images", type=int, default=0,
@@ -284,9 +340,9 @@ def main():
     ap.add_argument("--shipped-affine", action="store_true",
                     help="keep the shipped b005 scaling / biasing (fitted to real CLIP features): with the synthetic "
                          "tower nearly every symbol escapes -- the stress case, 4107 bits/img")
-    ap.add_argument("--min-seconds", type=float, default=1.0,
+    ap.add_argument("--min-seconds", type=float, default=0.0,
                     help="the timed region repeats the block of --steps steps until it has run this long AND ends on "
-                         "a whole tower pass (0: one block exactly)")
+                         "a whole tower pass (0, the default: exactly --steps steps)")
     ap.add_argument("--rotate", type=int, default=9,
                     help="distinct synthetic batches that take turns in the timed loop")
     ap.add_argument("--cu-split", choices=["cu", "xcd", "none"], default=None,
@@ -296,6 +352,8 @@ def main():
     ap.add_argument("--no-profile", action="store_true",
                     help="do not bracket kernels with HIP events (roofline becomes null)")
     args = ap.parse_args()
+    if args.dump_outputs and (args.dataset_images or args.host_images):
+        ap.error("--dump-outputs writes the outputs of the timed steps: not with --dataset-images / --host-images")
     cu_mask = None
     if int(os.environ.get("WORLD_SIZE", "1")) > 1:
         r, w = int(os.environ.get("LOCAL_RANK", "0")), int(os.environ.get("LOCAL_WORLD_SIZE", os.environ["WORLD_SIZE"]))
@@ -363,7 +421,7 @@ def main():
             dist.init_process_group("gloo")
 
     base = None
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:
+    if args.full and rank == 0 and world == 1 and not args.no_cpu_baseline:
         base = cpu_baseline()
 
     import hubconf
@@ -436,11 +494,11 @@ def main():
         calibrated = True
     # --rotate distinct batches take turns in the timed loop (one tensor pushed every step can be served from the
     # 256-MB memory-side cache and always codes the same symbols); xs[0] is the batch the checker re-codes
-    xs = [synth_batch(args.batch, seed=rank + 131 * i, device=device) for i in range(max(args.rotate, 1))]
+    xs = synth_batches([(args.batch, rank + 131 * i) for i in range(max(args.rotate, 1))], device)
     if args.layout == "nchw":
         xs = [v.permute(0, 3, 1, 2).contiguous() for v in xs]
     x = xs[0]
-    prof = None if args.no_profile else KernelProfiler(max_launches=8192)
+    prof = KernelProfiler(max_launches=8192) if args.full and not args.no_profile else None
 
     def step(profiler=None):
         z = comp.clip(x, profiler=profiler)
@@ -500,6 +558,8 @@ def main():
     local_elapsed = time.perf_counter() - t0     # this rank's own clock (before the closing barrier): stragglers show
     fence()
     elapsed = time.perf_counter() - t0
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, body, n_all, world, args.batch)
 
     # Per-kernel HIP-event timing: the same steps again with every launch bracketed by events
     # on the launch stream.  Kept out of the region `value` is computed from because the event
@@ -509,10 +569,10 @@ def main():
     # (the same batch, repeated).
     from lossyless_amd.compressor import _TOWER_BATCH
     tower_batch = max(_TOWER_BATCH, args.batch) if args.entropy_group else args.batch
-    reps = -(-tower_batch // args.batch)
-    xp = torch.cat([xs[k % len(xs)] for k in range(reps)])[:tower_batch] if reps > 1 else x
     n_prof = max(1, min(args.steps * args.batch // tower_batch, 12))   # (the event pool holds 8192 launches; a pass has ~90)
     if prof:
+        reps = -(-tower_batch // args.batch)
+        xp = torch.cat([xs[k % len(xs)] for k in range(reps)])[:tower_batch] if reps > 1 else x
         comp.clip(xp, profiler=prof)
         prof.collect()
         for _ in range(n_prof):
@@ -565,7 +625,7 @@ def main():
     # batches: one more timed block of whole tower passes lasting >= 1 s.  With synthetic tower weights nearly every
     # symbol escapes the coding window (the coder's worst case); the tower's work is the same.
     shipped_line = None
-    if calibrated and world == 1 and args.entropy_group:
+    if args.full and calibrated and world == 1 and args.entropy_group:
         import math
         fitted = (comp.scaling.detach().clone(), comp.biasing.detach().clone())
         with torch.no_grad():
@@ -590,11 +650,11 @@ def main():
             comp.scaling.copy_(fitted[0]); comp.biasing.copy_(fitted[1])
 
     verified = None
-    if rank == 0 and not args.no_verify:
+    if args.full and rank == 0 and not args.no_verify:
         verified = verify_first_batch(comp, x)
 
     ent = pre = hyp = stl = rn = refcall = None
-    if rank == 0 and world == 1 and not args.no_extra:
+    if args.full and rank == 0 and world == 1 and not args.no_extra:
         ent = entropy_stage_leg(comp, device)
         pre = preprocess_leg(comp, device)
         hyp = hyperprior_leg(device)

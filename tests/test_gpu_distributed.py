@@ -187,7 +187,7 @@ def test_bench_spawns_its_own_ranks(tmp_path):
         assert len(lines) == 1, r.stdout
         return json.loads(lines[0])
 
-    common = ["--batch", "64", "--no-cpu-baseline", "--no-extra", "--backend", backend]
+    common = ["--batch", "64", "--full", "--no-cpu-baseline", "--no-extra", "--backend", backend]
     two = run("--gpus", "2", "--steps", "3", "--warmup", "1", *common)
     assert two["n_gpus"] == 2 and two["metric"] == "encode_img_per_sec" and two["verified"] is True
     assert two["scaling"] == "weak" and two["value"] > 0
@@ -213,7 +213,7 @@ def test_world_8_dry_run_of_the_timed_bench_path(tmp_path):
     for k in ("RANK", "WORLD_SIZE", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT", "HSA_CU_MASK"):
         env.pop(k, None)
     r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "8", "--backend", "gloo", "--steps", "2",
-                        "--warmup", "1", "--min-seconds", "0", "--batch", "256", "--no-cpu-baseline", "--no-extra"],
+                        "--warmup", "1", "--min-seconds", "0", "--batch", "256", "--full", "--no-cpu-baseline", "--no-extra"],
                        env=env, capture_output=True, text=True, timeout=560)
     assert r.returncode == 0, r.stdout[-1500:] + r.stderr[-3000:]
     lines = [l for l in r.stdout.splitlines() if l.startswith("{")]

@@ -5,7 +5,7 @@
 #
 #   tools/ab.sh soak  OUT [arm ...]   1-rank file vs RUNS (4) two-rank files of IMAGES (1000000) images per arm
 #                                     (tools/two_rank_soak.py; CU_SPLIT=none|cu|xcd, default none = ranks share every XCD)
-#   tools/ab.sh bench OUT [arm ...]   ROUNDS (3) interleaved bench.py lines per arm (--no-cpu-baseline --no-extra)
+#   tools/ab.sh bench OUT [arm ...]   ROUNDS (3) interleaved bench.py lines per arm (--full --min-seconds 1 --no-cpu-baseline --no-extra)
 #   tools/ab.sh tower OUT [arm ...]   ROUNDS (3) interleaved tower-only passes per arm (tools/lnx_wait_sweep.py)
 #   tools/ab.sh suite OUT             the GPU suite + one bench line + the round's profile (tools/profile_round.sh $ROUND)
 #
@@ -48,7 +48,7 @@ for f in sorted(glob.glob(sys.argv[1] + "/soak_*.jsonl")):
 PY
     ;;
   bench)
-    B="python bench.py --no-cpu-baseline --no-extra ${BENCH_ARGS:-}"
+    B="python bench.py --full --min-seconds 1 --no-cpu-baseline --no-extra ${BENCH_ARGS:-}"
     for i in $(seq 1 ${ROUNDS:-3}); do
       for arm in "${arms[@]}"; do
         tag=${arm//[@=,\/]/_}
@@ -69,7 +69,7 @@ PY
   suite)
     timeout ${SUITE_TIMEOUT:-1500} python -m pytest tests -q -m gpu --durations=15 > $O/pytest_gpu.log 2>&1
     tail -n 25 $O/pytest_gpu.log
-    python bench.py > $O/bench_1gpu.json 2> $O/bench.err; cat $O/bench_1gpu.json
+    python bench.py --full --min-seconds 1 > $O/bench_1gpu.json 2> $O/bench.err; cat $O/bench_1gpu.json
     [ -n "$ROUND" ] && { bash tools/profile_round.sh $ROUND > $O/profile.log 2>&1; tail -n 30 $O/profile.log; }
     ;;
   *) echo "usage: tools/ab.sh soak|bench|tower|suite OUT [arm ...]"; exit 2 ;;

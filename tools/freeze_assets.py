@@ -10,7 +10,11 @@ product -- and the script then REQUIRES the product's EntropyBottleneck.update()
 them exactly before it freezes them into the shipped state-dict
 (`_quantized_cdf/_offset/_cdf_length` populated).  A state-dict that already carries tables
 makes update() a no-op -- the reference's own mechanism -- so the integer tables stop depending
-on the host's libm.
+on the host's libm.  The checkpoints themselves are recorded by digest in
+tests/golden/reference_checkpoints.json (shape, dtype, SHA-256 of every tensor), which
+tests/test_host_coder.py holds the shipped assets to, and the fp32 pmf / tail masses the oracle
+quantised into the tables in tests/golden/reference_pmf.npz: their fp32 evaluation depends on
+the host's vector kernels (MKL's tanh), the integer step from them to the tables does not.
 """
 import hashlib
 import json
@@ -29,18 +33,26 @@ REF = "/root/reference/hub"
 BETAS = {"1e-01": 0.1, "5e-02": 0.05, "1e-02": 0.01}
 
 
+def tensor_digest(v):
+    """shape, dtype and SHA-256 of a tensor's bytes (tests/golden/reference_checkpoints.json)."""
+    return dict(shape=list(v.shape), dtype=str(v.dtype).replace("torch.", ""),
+                sha256=hashlib.sha256(v.contiguous().numpy().tobytes()).hexdigest())
+
+
 def main():
     os.makedirs(os.path.join(ROOT, "lossyless_amd", "assets"), exist_ok=True)
     os.makedirs(os.path.join(ROOT, "tests", "golden"), exist_ok=True)
-    manifest = {}
+    manifest, checkpoints, masses = {}, {}, {}
     for tag in BETAS:
         sd = torch.load(f"{REF}/beta{tag}/factorized_rate.pt", map_location="cpu", weights_only=True)
+        checkpoints[tag] = {k: tensor_digest(v) for k, v in sd.items()}
         eb = EntropyBottleneck(512, init_scale=10, filters=[3, 3, 3, 3])
         update_registered_buffers(eb, "entropy_bottleneck",
                                   ["_quantized_cdf", "_offset", "_cdf_length"], sd)
         eb.load_state_dict({k.split(".", 1)[1]: v for k, v in sd.items()
                             if k.startswith("entropy_bottleneck.")})
         ot = oracle_eb.derive_tables(sd, "fp32")
+        masses[f"pmf_{tag}"], masses[f"tail_{tag}"] = ot["pmf"].astype(np.float32), ot["tail"].astype(np.float32)
         tab = {k: np.ascontiguousarray(ot[k]) for k in ("cdf", "cdf_len", "offset", "median",
                                                          "exp_scale", "bias")}
         assert eb.update() is True
@@ -64,6 +76,9 @@ def main():
         print(tag, manifest[tag])
     with open(os.path.join(ROOT, "tests", "golden", "tables_manifest.json"), "w") as f:
         json.dump(manifest, f, indent=1, sort_keys=True)
+    with open(os.path.join(ROOT, "tests", "golden", "reference_checkpoints.json"), "w") as f:
+        json.dump(checkpoints, f, indent=1, sort_keys=True)
+    np.savez_compressed(os.path.join(ROOT, "tests", "golden", "reference_pmf.npz"), **masses)
 
 
 if __name__ == "__main__":
