@@ -402,6 +402,14 @@ int lla_gemm_f16(const void *A, const void *W, const float *bias, void *C, int M
 int lla_gemm_f16_ex(const void *A, int lda, const void *W, const float *bias, void *C, int ldc,
                     const void *resid, int ldr, int M, int N, int K, int epilogue, void *stream);
 
+/* Introspection for tests and tools (no device call): which kernel lla_gemm_f16_ex / the towers would launch for this shape on
+ * a device with `cus` compute units.  epi: LLA_EPI_* (3: the patch embedding, amode 1 NHWC / 2 NCHW; 9: residual + LayerNorm),
+ * amode 0: plain operands, 3: implicit 3x3 convolution; a_chunk_images: the image batch in pieces (0: contiguous).
+ * *kernel: 0 nothing to launch, 1 gemm_f16_kernel, 2 gemm256_f16_kernel, 3 / 4 gemm_persistent_kernel 128 / 256 columns wide,
+ * 5 gemm_pp_kernel, 6 gemm_q4_kernel, 7 gemm_w8_kernel; *tile_rows: rows per tile; *grid: workgroups.  LLA_EINVAL: refused. */
+int lla_gemm_plan(int epi, int amode, int M, int N, int K, int lda, int ldc, int a_chunk_images, int cus,
+                  int *kernel, int *tile_rows, int *grid);
+
 /* fp32 Linear layer on the fp32 matrix cores: C[M][N] = A[M][K] * W[N][K]^T (+ bias) (ReLU if `relu`), all
  * fp32 row-major with row strides lda / ldw / ldc (elements, multiples of 4; K % 8 == 0, N % 4 == 0 -- pad with
  * zeros).  Stands in for the `nn.Linear` layers of the reference's hyperprior networks, which run in fp32 under

@@ -72,6 +72,7 @@ _SIGNATURES = {
     "lla_vit_b32_forward_gather": (_i, [_vp, _vp, _i, _i, _i, _i, _vp, _vp, _sz, _vp, _vp]),
     "lla_gemm_f16": (_i, [_vp, _vp, _vp, _vp, _i, _i, _i, _i, _vp]),
     "lla_patch_embed_f16": (_i, [_vp, _i, _i, _vp, _vp, _vp, _vp]),
+    "lla_gemm_plan": (_i, [_i, _i, _i, _i, _i, _i, _i, _i, _i, _vp, _vp, _vp]),
     "lla_gemm_f16_ex": (_i, [_vp, _i, _vp, _vp, _vp, _i, _vp, _i, _i, _i, _i, _i, _vp]),
     "lla_gemm_f32": (_i, [_vp, _i, _vp, _i, _vp, _vp, _i, _i, _i, _i, _i, _vp]),
     "lla_conv3x3_relu_f16": (_i, [_vp, _i, _i, _i, _i, _i, _vp, _vp, _vp, _i, _i, _vp]),
@@ -130,8 +131,9 @@ def stale(path=None):
 
 
 def ensure_built(path=None):
-    """(Re)build the library at `path` (the product library, the -DLLA_ABLATION build or a `make variant` build is told
-    from its file name) if it is missing or stale.  Call BEFORE the first lib(): a loaded library cannot be replaced."""
+    """(Re)build the library at `path` (the product library, the -DLLA_ABLATION build or the probe build is told from its
+    file name; a `make variant` build -- the product's sources with compile-time DEFS, no environment switch -- cannot be:
+    its DEFS are not recorded) if it is missing or stale.  Call BEFORE the first lib(): a loaded library cannot be replaced."""
     import subprocess
     path = path or LIB_PATH
     why = stale(path)

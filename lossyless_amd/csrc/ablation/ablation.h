@@ -1,4 +1,4 @@
-// tools/ builds only (make ablation / make probes / make variant): the environment reader of the A/B switches.  The product
+// tools/ builds only (make ablation / make probes / make w8variant / make tuvariant): the environment reader of the A/B switches.  The product
 // library has no such function -- its translation units contain no switch site (switches.h, gemm_pp.hip).
 #pragma once
 #include <cstdlib>

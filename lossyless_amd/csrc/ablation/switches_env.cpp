@@ -1,5 +1,5 @@
 // The tools/ builds' switch values (../switches.h): read once per process from the LLA_* environment variables, defaults =
-// the product's constants (../switches_product.cpp).  Linked by `make ablation` / `make probes` / `make variant` INSTEAD of
+// the product's constants (../switches_product.cpp).  Linked by `make ablation` / `make probes` (and the w8variant / tuvariant builds on their objects) INSTEAD of
 // switches_product.cpp; never part of liblossyless_amd.so.
 #include <cstdlib>
 

@@ -3,6 +3,7 @@
 // verbatim in round 4 so that the new kernel compiles as its own translation unit.
 #pragma once
 #include "common.h"
+#include "gemm_plan.h"
 
 #include <cstdlib>
 #include <type_traits>
@@ -37,27 +38,17 @@ typedef f16 f16x8 __attribute__((ext_vector_type(8)));
 typedef f16 f16x4 __attribute__((ext_vector_type(4)));
 typedef float f32x16 __attribute__((ext_vector_type(16)));
 
-constexpr int kWidth = 768, kLayers = 12, kHeadDim = 64, kTokens = 50;  // 12 heads
-constexpr int kPatches = 49, kPatchK = 3072, kMlp = 3072, kOut = 512;
 constexpr int kImgElems = 224 * 224 * 3;
 
 
 // ---------------------------------------------------------------------------
 // GEMM
 // ---------------------------------------------------------------------------
-constexpr int BM = 128, BN = 128, BK = 64;
-constexpr int BM2 = 256, BN2 = 128;   // gemm256_f16_kernel's tile (gemm_kernels.h; lla_conv3x3_relu_f16 checks its shapes against it)
 #ifndef LLA_W8_DEFAULT
 #define LLA_W8_DEFAULT 1   // 1: the large fp16-output GEMMs (QKV, c_fc; M >= 9000, N % 256 == 0) run on gemm_w8.hip
 #endif
 constexpr int kGemmThreads = 256;
 
-enum { EPI_F16 = 0, EPI_QGELU = 1, EPI_RESID = 2, EPI_PATCH = 3, EPI_RELU = 4, EPI_ADDRELU = 5,
-       // (6 .. 8: the algebraic LayerNorm fusion of round 3, retired in round 6: docs/history/DESIGN_rounds_1-5.md 5.4)
-       // round 5: EPI_RESID whose epilogue ALSO applies the LayerNorm that follows the residual add (ln_2 after out-proj,
-       // ln_1 of the next block after c_proj) to its own 256 x 256 chunk of x and writes it as fp16: the three column
-       // tiles of a row tile exchange exact per-row partial sums through memory (GemmParams::lnx_*, gemm_q4.hip)
-       EPI_RESID_LNX = 9 };
 // `sc0` (miss in this CU's vector L1, L2 hits allowed) on the loads that read buffers another kernel of the same
 // stream rewrites in place (docs/history/DESIGN_rounds_1-5.md 5.3: with two tower lanes a LayerNorm wave was served stale L1 lines of the
 // residual stream): LLA_DMA_SC0 = the GEMMs' LDS-DMA operand loads (activations; no reuse in L1 anyway), LLA_RMW_SC0 =
@@ -93,10 +84,6 @@ enum { EPI_F16 = 0, EPI_QGELU = 1, EPI_RESID = 2, EPI_PATCH = 3, EPI_RELU = 4, E
 #else
 #define LLA_RMW_SC ""
 #endif
-constexpr int epi_base(int e) { return e == EPI_RESID_LNX ? EPI_RESID : e; }   // the epilogue family of a kernel instantiation
-
-enum { A_PLAIN = 0, A_PATCH_NHWC = 1, A_PATCH_NCHW = 2, A_CONV3 = 3 };
-
 // 128 bytes of zeros: the out-of-image taps of the implicit 3x3 convolution GEMM read their A chunk here
 __device__ __attribute__((aligned(128))) f16 g_zero_line[64];
 
@@ -134,6 +121,10 @@ struct GemmParams {
   int lnx_wait;                 // shader cycles a workgroup waits for its two siblings before it leaves the row tile to
                                 // lnx_cleanup_kernel (0: looks once; < 0: does not even look -- every row tile takes the clean-up path)
 };
+// what the selection (gemm_plan.h) looks at
+inline GemmShape gemm_shape(int epi, int amode, const GemmParams &p) {
+  return {epi, amode, p.M, p.N, p.K, p.lda, p.ldc, p.n_store, p.a_chunk_images};
+}
 namespace {
 constexpr int kLnSlots = 24;  // the slice buffers reserve kLnSlots x 8 bytes per row for the LayerNorm epilogues' exchange area (tower.hip: `part`)
 

@@ -1031,8 +1031,5 @@ __global__ __launch_bounds__(512, 2) void gemm_pp_kernel(GemmParams p) {
   kernel_release();
 }
 
-// Rounds a persistent grid needs for `tiles` work items (the slowest workgroup's tile count).
-inline int rounds_for(int tiles, int cus) { return (tiles + cus - 1) / cus; }
-
 }  // namespace
 }  // namespace lla

@@ -1,37 +1,17 @@
 // Eight-wave GEMM on v_mfma_f32_16x16x32_f16 (gemm_w8_kernel.h): the product's launcher.  Takes the tower's large fp16-output
-// layers (QKV, c_fc + QuickGELU) at every M; one instantiation per epilogue, serial epilogue, no switch.  (The tools/ builds
-// compile ablation/gemm_w8_select.hip instead.)
+// layers (QKV, c_fc + QuickGELU) at every M; one instantiation per epilogue, serial epilogue, no switch; which shapes it takes
+// and its grid: gemm_plan.h.  (The tools/ builds compile ablation/gemm_w8_select.hip instead.)
 #include "gemm_w8_kernel.h"
 
 namespace lla {
-namespace {
-
-template <int EPI>
-int launch_w8_epi(const GemmParams &p, hipStream_t st) {
-  const int cus = num_cus();
-  const int total = ((p.M + 255) / 256) * (p.N / 256);
-  int grid = total < cus ? total : cus;
-  if (total > cus) {   // balanced persistent grid: only as many workgroups as the round count needs, a multiple of the 8 XCDs
-    const int rounds = (total + cus - 1) / cus;
-    const int need = ((total + rounds - 1) / rounds + 7) & ~7;
-    if (need < grid) grid = need;
-  }
-  gemm_w8_kernel<EPI><<<grid, 512, 0, st>>>(p);
-  return check_launch();
-}
-
-}  // namespace
 
 int launch_w8(int epi, const GemmParams &p, hipStream_t st) {
-  if (p.M <= 0 || (p.N & 255) || p.N > 3072 || (p.K & 63) || p.K < 128 || p.lda < p.K || (p.lda & 7) || p.ldc < p.N || (p.ldc & 7)) return LLA_EINVAL;
-  // 32-bit byte offsets: inside a tile's operand panel, and of the panels from the operands' bases (the descriptor's scalar offset)
-  if ((size_t)256 * (size_t)p.lda * 2 >= (1ull << 31) || (size_t)256 * (size_t)p.K * 2 >= (1ull << 31)) return LLA_EINVAL;
-  if ((size_t)p.M * (size_t)p.lda * 2 >= (1ull << 32) || (size_t)p.N * (size_t)p.K * 2 >= (1ull << 32)) return LLA_EINVAL;
-  switch (epi) {
-    case EPI_F16: return launch_w8_epi<EPI_F16>(p, st);
-    case EPI_QGELU: return launch_w8_epi<EPI_QGELU>(p, st);
-    default: return LLA_EINVAL;
-  }
+  const GemmShape s = gemm_shape(epi, A_PLAIN, p);
+  if (!w8_takes(s)) return LLA_EINVAL;
+  const int grid = w8_grid(s, num_cus());
+  if (epi == EPI_F16) gemm_w8_kernel<EPI_F16><<<grid, 512, 0, st>>>(p);
+  else gemm_w8_kernel<EPI_QGELU><<<grid, 512, 0, st>>>(p);
+  return check_launch();
 }
 
 }  // namespace lla

@@ -11,18 +11,26 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 EXTS = ("hip", "h", "cpp", "inc")
 
 
-def source_sha(csrc=HERE):
-    h = hashlib.sha256()
+def hashed_files(csrc=HERE):
+    """The files the sha covers, in hashing order (`--list`: the Makefile's prerequisites of the objects that carry the sha)."""
     header = os.path.join(csrc, "..", "..", "include", "lossyless_amd.h")
     abl = os.path.join(csrc, "ablation")       # (the tools/ builds' launchers and switch readers: one sha for every build)
     files = [os.path.join(csrc, fn) for fn in os.listdir(csrc)]
     files += [os.path.join(abl, fn) for fn in os.listdir(abl)] if os.path.isdir(abl) else []
-    for path in sorted(files, key=lambda q: os.path.relpath(q, csrc)) + [header]:
-        if os.path.isfile(path) and path.rsplit(".", 1)[-1] in EXTS:
-            with open(path, "rb") as f:
-                h.update(os.path.relpath(path, csrc).encode() + b"\0" + f.read())
+    return [path for path in sorted(files, key=lambda q: os.path.relpath(q, csrc)) + [header]
+            if os.path.isfile(path) and path.rsplit(".", 1)[-1] in EXTS]
+
+
+def source_sha(csrc=HERE):
+    h = hashlib.sha256()
+    for path in hashed_files(csrc):
+        with open(path, "rb") as f:
+            h.update(os.path.relpath(path, csrc).encode() + b"\0" + f.read())
     return h.hexdigest()[:16]
 
 
 if __name__ == "__main__":
-    sys.stdout.write(source_sha())
+    if sys.argv[1:] == ["--list"]:
+        sys.stdout.write(" ".join(os.path.relpath(path, HERE) for path in hashed_files()))
+    else:
+        sys.stdout.write(source_sha())

@@ -483,10 +483,11 @@ static int vit_forward_impl(const void *images, int layout, int B, const void *w
     // four-wave kernel takes: ln_2 of every block in out-proj's epilogue, ln_1 of the next block in c_proj's; behind each
     // such GEMM lnx_cleanup_kernel redoes the row tiles whose column tiles missed each other.  Output in ws.xh (the
     // consumers' A operand then).  The exchange words of the slice's launches are zeroed here, once.
-    // (... and inside the four-wave kernel's 32-bit panel offsets for BOTH residual GEMMs -- c_proj's A operand has the
-    // longest rows, lda = 3072: slices of 14 080+ images, ADVICE r5 -- so that launch_q4(EPI_RESID_LNX) cannot answer
-    // LLA_EINVAL here; such slices take the LayerNorm kernels, with the residual GEMMs on the ping-pong kernel)
-    const bool lnx = (M & 255) == 0 && M >= 9000 && (size_t)M * kMlp * 2 < (1ull << 32) && (!tower || tower->lnx);
+    // (... for BOTH residual GEMMs: c_proj's A operand has the longest rows, lda = 3072, and leaves the four-wave kernel's
+    // 32-bit panel offsets first -- slices of 14 080+ images, ADVICE r5 -- so its gate (gemm_plan.h) is the one asked, and
+    // launch_q4(EPI_RESID_LNX) cannot answer LLA_EINVAL here; such slices take the LayerNorm kernels, with the residual
+    // GEMMs on the ping-pong kernel)
+    const bool lnx = M >= kBigM && q4_takes({EPI_RESID_LNX, A_PLAIN, M, kWidth, kMlp, kMlp, kWidth, 0, 0}) && (!tower || tower->lnx);
     const int tiles_m = M / 256;
     float *const lnx_part = ws.part;                                                       // [tiles_m][3][256] granules of 16 bytes
     unsigned *const lnx_words = reinterpret_cast<unsigned *>(ws.part + (size_t)tiles_m * 3 * 256 * 4);   // [launch]{flag [tiles_m][3], done [tiles_m][3]}

@@ -602,3 +602,235 @@ def test_cu_mask_geometry_comes_from_the_kfd_topology(tmp_path, monkeypatch):
     m = gp.partition_shared_gpu(0, 2, sysfs=str(tmp_path / "nowhere"), if_unknown=1)
     assert m == "0:" + ",".join(str(i) for i in range(128))                        # unreadable: the MI355X's 8 x 32
     monkeypatch.delenv("HSA_CU_MASK")
+
+
+# ---- GEMM selection (csrc/gemm_plan.h through lla_gemm_plan): which kernel, which tile height, how many workgroups ----
+_GK = dict(none=0, tile128=1, tile256=2, persist1=3, persist2=4, pp=5, q4=6, w8=7)   # enum GemmKernel
+_F16, _QGELU, _RESID, _PATCH, _RELU, _ADDRELU, _LNX = 0, 1, 2, 3, 4, 5, 9               # epilogues
+_PLAIN, _NHWC, _NCHW, _CONV3 = 0, 1, 2, 3                                             # operand modes
+
+
+def _expected_plan(epi, amode, M, N, K, lda, ldc, chunk, cus):
+    """The product's selection, restated from the table at the top of csrc/gemm_plan.h independently of its code:
+    -> (status, kernel, tile rows, workgroups)."""
+    cdiv = lambda a, b: -(-a // b)
+    refuse = (-1, 0, 0, 0)
+
+    def persistent(kernel, tiles_n, tall_allowed, balanced):
+        cost = {rows: cdiv(cdiv(M, rows) * tiles_n, cus) * rows for rows in (256, 320)}     # rounds x rows
+        rows = 320 if tall_allowed and cost[320] <= cost[256] else 256
+        tiles = cdiv(M, rows) * tiles_n
+        grid = min(tiles, cus)
+        if balanced and tiles > cus:            # as few workgroups as the same number of rounds needs, whole XCDs
+            grid = min(cus, cdiv(cdiv(tiles, cdiv(tiles, cus)), 8) * 8)
+        return (0, kernel, rows, grid)
+
+    if M <= 0:
+        return (0, 0, 0, 0)
+    if N % 128 or K % 64:
+        return refuse
+    if (epi, amode) not in [(e, _PLAIN) for e in (_F16, _QGELU, _RESID, _RELU, _ADDRELU, _LNX)] + [
+            (_PATCH, _NHWC), (_PATCH, _NCHW), (_RELU, _CONV3)]:
+        return refuse
+    panel = 256 * lda * 2 < 2 ** 31 and 256 * K * 2 < 2 ** 31 and M * lda * 2 < 2 ** 32 and N * K * 2 < 2 ** 32
+    wide3 = N % 256 == 0 and N >= 768
+    four_wave = M % 256 == 0 and N % 256 == 0 and N <= 3072 and K >= 256 and lda >= K and lda % 8 == 0 and panel
+    tiles4 = (M // 256) * (N // 256)
+    if epi == _LNX:
+        if not (four_wave and N == 768 and ldc == 768):
+            return refuse
+        return (0, _GK["q4"], 256, 256) if cus == 256 and tiles4 > cus else persistent(_GK["q4"], N // 256, False, True)
+    if chunk and (epi != _PATCH or chunk % 256 or M < 9000 or not wide3 or K < 256):
+        return refuse
+    if epi in (_RESID, _PATCH) and (M + M // 49 + 2) * ldc >= 2 ** 32:
+        return refuse
+    stored = ldc if ldc < N else N
+    if epi in (_RELU, _ADDRELU):
+        if amode == _PLAIN and M >= 9000 and N % 256 == 0 and stored == N:
+            return persistent(_GK["persist2"], N // 256, True, False)
+        if M > 128 or amode == _CONV3:
+            return (0, _GK["tile256"], 256, cdiv(M, 256) * (N // 128))
+        return (0, _GK["tile128"], 128, cdiv(M, 128) * (N // 128))
+    if M <= 128:
+        return (0, _GK["tile128"], 128, N // 128)
+    if M < 9000:
+        return (0, _GK["tile256"], 256, cdiv(M, 256) * (N // 128))
+    if epi in (_F16, _QGELU) and N % 256 == 0 and N <= 3072 and K >= 128 and lda >= K and lda % 8 == 0 and ldc >= N and \
+            ldc % 8 == 0 and panel:
+        return persistent(_GK["w8"], N // 256, False, True)
+    if epi == _RESID and ldc == N and four_wave:
+        return persistent(_GK["q4"], N // 256, False, True)
+    if wide3 and K >= 256:
+        return persistent(_GK["pp"], N // 256, not chunk, True)
+    if wide3:
+        return persistent(_GK["persist2"], N // 256, True, False)
+    return persistent(_GK["persist1"], N // 128, False, False)
+
+
+def _tower_gemm_shapes(B):
+    """(epilogue, operand mode, M, N, K, lda, ldc) of every GEMM of the ViT-B/32 tower on a slice of B images (csrc/tower.hip)."""
+    M, row = 50 * B, 50 * 768
+    return [(_PATCH, _NHWC, 49 * B, 768, 3072, 0, 768), (_PATCH, _NCHW, 49 * B, 768, 3072, 0, 768),
+            (_F16, _PLAIN, M, 2304, 768, 768, 2304), (_RESID, _PLAIN, M, 768, 768, 768, 768),             # QKV, out-proj
+            (_QGELU, _PLAIN, M, 3072, 768, 768, 3072), (_RESID, _PLAIN, M, 768, 3072, 3072, 768),          # c_fc, c_proj
+            (_LNX, _PLAIN, M, 768, 768, 768, 768), (_LNX, _PLAIN, M, 768, 3072, 3072, 768),                # ... with LayerNorm
+            # the last block: K and V for every token, everything else for the class rows alone (strided in place)
+            (_F16, _PLAIN, M, 1536, 768, 768, 2304), (_F16, _PLAIN, B, 768, 768, row, 3 * row),
+            (_RESID, _PLAIN, B, 768, 768, row, row), (_QGELU, _PLAIN, B, 3072, 768, 768, 3072),
+            (_RESID, _PLAIN, B, 768, 3072, 3072, row), (_F16, _PLAIN, B, 512, 768, 768, 512)]               # final projection
+
+
+def _rn50_gemm_shapes(n):
+    """... and of every 1x1 / 3x3 convolution of the RN50-CLIP tower behind its direct stem convolution, n images a chunk."""
+    from lossyless_amd import clip_rn50
+    L, d, out = _lib.lib(), (ctypes.c_int64 * 8)(), []
+    res = {"conv2": 112, "conv3": 112}
+    r = 56
+    for s, nb in enumerate(clip_rn50.BLOCKS):
+        for b in range(nb):
+            o = r // (2 if s > 0 and b == 0 else 1)
+            p = f"layer{s + 1}.{b}."
+            res.update({p + "conv1": r, p + "conv2": r, p + "conv3": o, p + "downsample.1": o})
+            r = o
+    for i, (name, _) in enumerate(clip_rn50.conv_names()):
+        if name == "conv1":
+            continue
+        assert L.lla_rn50_conv_desc(i, d) == 0
+        cin, cout, k, stride, kpad, npad = [int(v) for v in d][:6]
+        M, ldc = n * res[name] ** 2, (npad if cout == npad else cout)
+        if k == 3:
+            out.append((_RELU, _CONV3, M, npad, kpad, cin, ldc))
+        else:
+            out += [(e, _PLAIN, M, npad, kpad, kpad, ldc) for e in (_RELU, _ADDRELU, _F16)]
+    return out
+
+
+def _plan_cases():
+    cases = [s + (0,) for B in (4, 128, 129, 180, 257, 640, 1024, 8704) for s in _tower_gemm_shapes(B)]
+    cases += [s + (0,) for n in (32, 256) for s in _rn50_gemm_shapes(n)]
+    ms = sorted({m + d for m in (128, 256, 9000, 9216, 12800, 51200, 435200) for d in (-1, 0, 1)} | {0, 1, 100, 5000})
+    for M in ms:
+        for N in (128, 256, 512, 768, 2304, 3072):
+            for K in (64, 128, 192, 256, 768, 3072):
+                cases += [(e, _PLAIN, M, N, K, K, N, 0) for e in (_F16, _QGELU, _RESID, _RELU, _ADDRELU)]
+                cases += [(_PATCH, _NCHW, M, N, K, 0, N, 0), (_RELU, _CONV3, M, N, K, 64, N, 0), (_RELU, _PLAIN, M, N, K, K, 64, 0)]
+    cases += [(_PATCH, _NHWC, 49 * B, 768, 3072, 0, 768, 256) for B in (256, 1024, 8704)]      # the image batch in pieces
+    return cases
+
+
+def _plan_answers(L, cases, cus_list=(256, 304, 64)):
+    k, rows, grid = ctypes.c_int(-7), ctypes.c_int(-7), ctypes.c_int(-7)
+    out = []
+    for cus in cus_list:
+        for c in cases:
+            rc = L.lla_gemm_plan(*c, cus, ctypes.byref(k), ctypes.byref(rows), ctypes.byref(grid))
+            out.append((rc, k.value, rows.value, grid.value))
+    return out
+
+
+def test_gemm_selection_table():
+    """Which kernel the tower's GEMM shapes reach, on which tiles and grid -- on 256 CUs (MI355X), and on 304 and 64 so that the
+    grid arithmetic is not only checked where it happens to be a no-op."""
+    L, cases = _lib.lib(), _plan_cases()
+    for cus in (256, 304, 64):
+        got = _plan_answers(L, cases, (cus,))
+        for c, g in zip(cases, got):
+            assert g == _expected_plan(*c, cus), (c, cus, g, _expected_plan(*c, cus))
+    # ... and spelled out for the flagship batch: 8704 images on 256 CUs
+    at = lambda i: _plan_answers(L, [_tower_gemm_shapes(8704)[i] + (0,)], (256,))[0]
+    assert at(0) == (0, _GK["pp"], 320, 256)                                    # patch embedding: 1333 x 3 tall tiles, 16 rounds
+    assert at(2) == (0, _GK["w8"], 256, 256) and at(4) == (0, _GK["w8"], 256, 256)      # QKV, c_fc
+    assert at(3) == (0, _GK["q4"], 256, 256) and at(5) == (0, _GK["q4"], 256, 256)      # out-proj, c_proj: 5100 tiles, 20 rounds
+    assert at(9)[1] == _GK["tile256"] and at(13) == (0, _GK["tile256"], 256, 34 * 4)     # class rows only, final projection
+    b1024 = _plan_answers(L, [s + (0,) for s in _tower_gemm_shapes(1024)], (256,))
+    assert b1024[0] == (0, _GK["pp"], 320, 240)       # 157 x 3 = 471 tall tiles in 2 rounds: 236 -> 240 workgroups
+    assert b1024[2] == (0, _GK["w8"], 256, 232) and b1024[3] == (0, _GK["q4"], 256, 200)    # 1800 tiles in 8 rounds of 225; 600 in 3
+    assert b1024[6] == (0, _GK["q4"], 256, 256)       # LayerNorm in the epilogue: the triple walk's 8 x 32 workgroups
+
+
+def test_gemm_selection_refusals():
+    """What the launchers answer LLA_EINVAL to, through the plan."""
+    L = _lib.lib()
+    plan = lambda *c, cus=256: _plan_answers(L, [c], (cus,))[0]
+    ok = (_F16, _PLAIN, 12800, 768, 768, 768, 768, 0)
+    assert plan(*ok)[0] == 0 and plan(_F16, _PLAIN, 0, 768, 768, 768, 768, 0) == (0, 0, 0, 0)       # nothing to do
+    assert plan(_F16, _PLAIN, 12800, 192, 768, 768, 192, 0)[0] == -1            # N % 128
+    assert plan(_F16, _PLAIN, 12800, 768, 96, 96, 768, 0)[0] == -1              # K % 64
+    assert plan(_PATCH, _PLAIN, 12800, 768, 3072, 3072, 768, 0)[0] == -1 and plan(7, _PLAIN, *ok[2:])[0] == -1   # no such pair
+    assert plan(_ADDRELU, _CONV3, 12800, 128, 576, 64, 128, 0)[0] == -1
+    # fp32 epilogues: 32-bit element offsets into C (rows + rows / 49 + 2) * ldc
+    assert plan(_RESID, _PLAIN, 5_400_000, 768, 768, 768, 768, 0)[0] == 0 and plan(_RESID, _PLAIN, 5_500_000, 768, 768, 768, 768, 0)[0] == -1
+    # the image batch in pieces: patch embedding of >= 9000 rows in pieces of whole 256 images on the ping-pong kernel's 256-row tiles
+    pieces = lambda M, chunk, epi=_PATCH, amode=_NHWC, N=768, K=3072: plan(epi, amode, M, N, K, 0 if amode else K, N, chunk)
+    assert pieces(49 * 1024, 256) == (0, _GK["pp"], 256, 200)                   # (196 x 3 = 588 tiles in 3 rounds of 196 -> 200)
+    assert pieces(49 * 1024, 100)[0] == -1 and pieces(49 * 128, 256)[0] == -1 and pieces(49 * 1024, 256, N=512)[0] == -1
+    assert pieces(49 * 1024, 256, K=128)[0] == -1 and pieces(50 * 1024, 256, epi=_F16, amode=_PLAIN)[0] == -1
+    # the four-wave kernel with LayerNorm (the tower asks before it plans a slice): whole tiles, N = ldc = 768, and c_proj's
+    # operand panels within 32-bit byte offsets of A's base -- 14 080 images are the first slice of whole tiles beyond them
+    lnx = lambda B, ldc=768: plan(_LNX, _PLAIN, 50 * B, 768, 3072, 3072, ldc, 0)[0]
+    assert lnx(8704) == 0 and lnx(13824) == 0 and lnx(14080) == -1 and lnx(1000) == -1 and lnx(8704, ldc=1536) == -1
+    # ... and what the eight- / four-wave kernels leave to the ping-pong kernel instead of refusing
+    assert plan(_F16, _PLAIN, 12800, 3328, 768, 768, 3328, 0)[1] == _GK["pp"]                   # N > 3072
+    assert plan(_RESID, _PLAIN, 12837, 768, 768, 768, 768, 0)[1] == _GK["pp"]                   # ragged M
+    assert plan(_F16, _PLAIN, 1_000_000, 768, 3072, 3072, 768, 0)[1] == _GK["pp"]               # M lda 2 >= 2^32
+    assert L.lla_gemm_plan(*ok, 0, None, None, None) == -1
+
+
+_PLAN_CHILD = r"""
+import json, os, sys
+sys.path.insert(0, sys.argv[1]); sys.path.insert(0, os.path.join(sys.argv[1], "tests"))
+import test_host
+from lossyless_amd import _lib
+assert _lib.LIB_PATH.endswith("_ablation.so")
+print("PLAN=" + json.dumps(test_host._plan_answers(_lib.lib(), test_host._plan_cases())))
+"""
+
+
+def _tools_build_answers(tmp_path, **switches):
+    from conftest import ABLATION_LIB
+    script = tmp_path / "plan.py"
+    script.write_text(_PLAN_CHILD)
+    env = {k: v for k, v in os.environ.items() if not k.startswith("LLA_")}
+    r = subprocess.run([sys.executable, str(script), ROOT], env=dict(env, LLA_LIB=ABLATION_LIB, **switches),
+                       capture_output=True, text=True, timeout=600)
+    assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-2000:]
+    import json
+    return [tuple(a) for a in json.loads(r.stdout.split("PLAN=")[1])]
+
+
+def test_tools_build_selects_what_the_product_selects(tmp_path):
+    """Every A/B number takes its baseline arm from the tools/ build: with no switch set it must choose the product's kernel,
+    tile height and grid for every shape (the bits cannot tell: every kernel gives the same).  Then a few switches."""
+    from conftest import ABLATION_LIB
+    if not os.path.exists(ABLATION_LIB) or _lib.stale(ABLATION_LIB):
+        pytest.skip("the tools/ build is not built: make -C lossyless_amd/csrc ablation")
+    cases = _plan_cases()
+    product = _plan_answers(_lib.lib(), cases)
+    assert _tools_build_answers(tmp_path) == product
+    n = len(cases)
+    qkv = cases.index(_tower_gemm_shapes(8704)[2] + (0,))              # at 256 CUs: the first third of the answers
+    patch1024 = cases.index(_tower_gemm_shapes(1024)[0] + (0,))
+    assert product[qkv] == (0, _GK["w8"], 256, 256) and product[patch1024] == (0, _GK["pp"], 320, 240)
+    off = _tools_build_answers(tmp_path, LLA_GEMM_W8="0")
+    assert off[qkv] == (0, _GK["q4"], 256, 256)                        # the round-5 selection: the four-wave kernel
+    assert [a for a, p in zip(off, product) if p[1] != _GK["w8"]] == [p for p in product if p[1] != _GK["w8"]]
+    pp_only = _tools_build_answers(tmp_path, LLA_GEMM_W8="0", LLA_GEMM_Q4="0")
+    assert pp_only[qkv] == (0, _GK["pp"], 320, 256) and not any(a[1] in (_GK["w8"], _GK["q4"]) for a, c in zip(pp_only, cases * 3) if c[0] != _LNX)
+    t128 = _tools_build_answers(tmp_path, LLA_GEMM_W8="0", LLA_GEMM_Q4="0", LLA_GEMM_TILE="128")
+    assert t128[qkv] == (0, _GK["tile128"], 128, 3400 * 18)
+    full = _tools_build_answers(tmp_path, LLA_GEMM_BALANCED="0")
+    assert full[patch1024] == (0, _GK["pp"], 320, 256) and full[qkv] == product[qkv] and len(full) == 3 * n
+
+
+def test_objects_that_carry_the_source_sha_follow_every_hashed_file():
+    """`make` must not report a library up to date whose sha the tree no longer has -- host.o is recompiled when
+    any file source_sha.py hashes changes, in the product and in the tools/ build.  Dry runs: nothing is touched or compiled."""
+    csrc = os.path.join(ROOT, "lossyless_amd", "csrc")
+    listed = subprocess.run([sys.executable, "source_sha.py", "--list"], cwd=csrc, capture_output=True, text=True).stdout.split()
+    assert "ablation/gemm_select.hip" in listed and "gemm_plan.h" in listed and "../../include/lossyless_amd.h" in listed
+    for fn in ("tower.hip", "gemm_plan.h", "ablation/gemm_select.hip", "ablation/ablation.h", "../../include/lossyless_amd.h"):
+        for target in ([], ["ablation"]):
+            r = subprocess.run(["make", "-C", csrc, "-n", "-W", fn, *target], capture_output=True, text=True)
+            assert r.returncode == 0, r.stderr
+            compiles = [l for l in r.stdout.splitlines() if "LLA_SOURCE_SHA" in l and l.rstrip().endswith("host.cpp")]
+            assert len(compiles) == 1 and "-o build/host.o" in compiles[0], (fn, target, r.stdout)
