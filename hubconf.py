@@ -14,6 +14,7 @@ import pathlib
 import torch
 
 from lossyless_amd import ClipCompressor as _Compressor
+from lossyless_amd import HyperpriorClipCompressor as _HyperpriorCompressor
 
 _ASSET_DIR = pathlib.Path(__file__).resolve().parent / "lossyless_amd" / "assets"
 _ASSET_NAME = "beta{beta:0.0e}_factorized_rate.pt"
@@ -59,3 +60,19 @@ def _entry(tag, beta):
 clip_compressor_b005 = _entry("b005", 5e-2)
 clip_compressor_b001 = _entry("b001", 1e-2)
 clip_compressor_b01 = _entry("b01", 1e-1)
+
+
+def clip_hyperprior_compressor(state_dict, device=_ON, **kwargs):
+    """CLIP ViT-B/32 + scale-hyperprior compressor (the model behind the reference's headline table), MI355X kernels.
+
+    state_dict   : what the reference's ``HRateHyperprior`` saves (``main.py`` training), as a dict or a path to it.  No
+                   hyperprior checkpoint ships with the reference, so there is nothing to fetch.
+    device, clip_weights, gpu_preprocess, other kwargs : as for ``clip_compressor_b005``; forwarded to
+                   ``lossyless_amd.HyperpriorClipCompressor``
+
+    Returns ``(compressor, transform)`` with the factorized entry points' surface; ``compress`` returns
+    ``[z_strings, side_z_strings]``, the ``.bin`` file holds two records per image, and ``decompress_dataset`` decodes on
+    the GPU (``is_cpu=True`` raises: the coding-table rows come from an MLP evaluated on the fp32 matrix cores).
+    """
+    model = _HyperpriorCompressor(pretrained_state_dict=state_dict, device=device, **kwargs)
+    return model, model.preprocess

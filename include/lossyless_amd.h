@@ -150,6 +150,21 @@ int lla_rans_compact(const uint8_t *scratch, size_t stride, const uint32_t *leng
                      int record_prefix, uint8_t *out, size_t cap, uint64_t *out_off,
                      void *workspace, size_t workspace_bytes, void *stream);
 
+/* Two sets of end-aligned streams (a = z, b = side information of the scale hyperprior) packed into ONE body of
+ * interleaved length-prefixed records:
+ *   out = be32(len a_0) a_0 be32(len b_0) b_0 be32(len a_1) a_1 ...
+ * i.e. the reference's container body (hub/compressor.py:192-196) with two records per image, which is what a
+ * dataset coded by HRateHyperprior.compress (lossyless/rates.py:701-713: [z_strings, side_z_strings]) holds.
+ * out_off [dev] 2B+1 entries (record r starts at out_off[r]; out_off[2B] = total bytes).  cap and overrun as in
+ * lla_rans_compact: records that would end beyond cap are not written, out_off still reports the needed size.
+ * workspace [dev] 8-byte aligned, lla_rans_compact_pairs_workspace_bytes(B) bytes.  LLA_EINVAL for B >= 2^30 (the
+ * 2B records are counted in an int). */
+size_t lla_rans_compact_pairs_workspace_bytes(int B);
+int lla_rans_compact_pairs(const uint8_t *scratch_a, size_t stride_a, const uint32_t *lengths_a,
+                           const uint8_t *scratch_b, size_t stride_b, const uint32_t *lengths_b, int B,
+                           uint8_t *out, size_t cap, uint64_t *out_off, void *workspace,
+                           size_t workspace_bytes, void *stream);
+
 /* Replaces ans.RansDecoder().decode_with_indexes(encoded, indexes, cdfs,
  * cdfs_sizes, offsets) -> list[int], called per image by EntropyModel.decompress
  * <- hub/compressor.py:124,238; lossyless/rates.py:563.
@@ -160,6 +175,15 @@ int lla_rans_decode_batch(const uint8_t *payload, const uint64_t *off, int recor
                           int C, const int32_t *cdf, int W, const int32_t *cdf_len,
                           const int32_t *offset, int32_t *symbols_out, int32_t *status,
                           void *stream);
+
+/* lla_rans_decode_batch over every off_step-th record: image b's stream is
+ * payload[off[off_first + b*off_step] + skip .. off[off_first + b*off_step + 1]).  off_first = 1, off_step = 2 reads the
+ * side-information records of a body written by lla_rans_compact_pairs.  lla_rans_decode_batch is off_first = 0,
+ * off_step = 1. */
+int lla_rans_decode_batch_strided(const uint8_t *payload, const uint64_t *off, int record_prefix,
+                                  int off_first, int off_step, int B, int C, const int32_t *cdf, int W,
+                                  const int32_t *cdf_len, const int32_t *offset, int32_t *symbols_out,
+                                  int32_t *status, void *stream);
 
 /* The same two coder calls with an arbitrary table row per symbol, i.e. the full
  * ans.RansEncoder().encode_with_indexes(symbols, indexes, cdfs, cdfs_sizes, offsets) /
@@ -178,6 +202,38 @@ int lla_rans_decode_indexed(const uint8_t *payload, const uint64_t *off, int rec
                             int n, const int32_t *indexes, const int32_t *cdf, int T, int W,
                             const int32_t *cdf_len, const int32_t *offset, int32_t *symbols_out,
                             int32_t *status, void *stream);
+
+/* Conditional part of the scale hyperprior in one kernel.  Replaces, per batch, lossyless/rates.py:694-729:
+ * process_z_in (:434-435), get_indexes_means_hat's build_indexes(scales_hat) and means_hat = scales_hat (:694-698),
+ * and GaussianConditional.compress(z_in, indexes, means=means_hat) (:712: quantize "symbols" + one
+ * RansEncoder.encode_with_indexes per image).  Per element, every operation rounded to fp32 on its own:
+ *   z_in = (float(z) + bias) * exp_scale
+ *   row  = T-1 - #{t < T-1 : max(scale, scale_bound) <= scale_table[t]}     (GaussianConditional.build_indexes)
+ *   mean = scale            (the UNBOUNDED prediction: the reference passes the scales as means, rates.py:694-696)
+ *   sym  = int(rint(z_in - mean))
+ * and sym is coded with table row `row` into the end-aligned scratch exactly as lla_rans_encode_indexed would.
+ * z [dev] B*C of z_dtype; bias/exp_scale [dev] C; scales [dev] fp32, element (b, c) at scales[b*ld_scales + c]
+ * (ld_scales >= C: the first half of the z_encoder output is read where it lies); scale_table [dev] T floats;
+ * cdf [dev] T*W int32, cdf_len/offset [dev] T (rows are read from global memory: a 64-level table is 800 KB).
+ * symbols_out / indexes_out [dev] B*C int32, either may be NULL.  scratch/stride/lengths as in lla_rans_encode_batch. */
+int lla_gaussian_quantise_encode(const void *z, int z_dtype, int B, int C, const float *bias,
+                                 const float *exp_scale, const float *scales, size_t ld_scales,
+                                 const float *scale_table, float scale_bound, const int32_t *cdf, int T, int W,
+                                 const int32_t *cdf_len, const int32_t *offset, uint8_t *scratch, size_t stride,
+                                 uint32_t *lengths, int32_t *symbols_out, int32_t *indexes_out, void *stream);
+
+/* The inverse (lossyless/rates.py:715-724: build_indexes + GaussianConditional.decompress(z_strings, indexes,
+ * means=means_hat) -- one RansDecoder.decode_with_indexes per image -- + process_z_out, :437-438): row and mean are
+ * derived from `scales` as above, the records decoded, and
+ *   z_hat = (float(sym) + mean) / exp_scale - bias          fp32 [dev] B*C.
+ * Image b's stream is record off_first + b*off_step of `off` (see lla_rans_decode_batch_strided; off_first = 0,
+ * off_step = 2 reads the z records of a body written by lla_rans_compact_pairs).  status [dev] B ints as in
+ * lla_rans_decode_batch; every read is bounded by the record and by the table row, whatever the bytes hold. */
+int lla_gaussian_decode_dequantise(const uint8_t *payload, const uint64_t *off, int record_prefix, int off_first,
+                                   int off_step, int B, int C, const float *bias, const float *exp_scale,
+                                   const float *scales, size_t ld_scales, const float *scale_table,
+                                   float scale_bound, const int32_t *cdf, int T, int W, const int32_t *cdf_len,
+                                   const int32_t *offset, float *z_hat, int32_t *status, void *stream);
 
 /* EntropyModel.dequantize + process_z_out (hub/compressor.py:111-115):
  * z_hat = (float(sym) + median) / exp_scale - bias, fp32 per operation. */

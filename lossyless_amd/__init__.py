@@ -26,7 +26,8 @@ if not _keep:
     _os.environ.setdefault("GPU_PINNED_MIN_XFER_SIZE", "65536")
 
 from .compressor import ClipCompressor  # noqa: F401
+from .hyperprior_compressor import HyperpriorClipCompressor  # noqa: F401
 from .entropy import EntropyBottleneck  # noqa: F401
 from .clip_vit import VisionTransformer, synthetic_vit_state_dict  # noqa: F401
 
-__all__ = ["ClipCompressor", "EntropyBottleneck", "VisionTransformer", "synthetic_vit_state_dict"]
+__all__ = ["ClipCompressor", "HyperpriorClipCompressor", "EntropyBottleneck", "VisionTransformer", "synthetic_vit_state_dict"]

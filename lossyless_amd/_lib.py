@@ -13,6 +13,7 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("LLA_LIB") or os.path.join(_HERE, "liblossyless_amd.so")
 
 LLA_OK = 0
+LLA_EINVAL, LLA_ECAP, LLA_EHIP, LLA_EDATA = -1, -2, -3, -4      # (include/lossyless_amd.h)
 ABI_VERSION = 4
 LLA_Z_F16, LLA_Z_F32 = 1, 2
 LLA_LAYOUT_NHWC, LLA_LAYOUT_NCHW = 0, 1
@@ -42,6 +43,13 @@ _SIGNATURES = {
                                  _vp, _vp, _vp]),
     "lla_rans_compact_workspace_bytes": (_sz, [_i]),
     "lla_rans_compact": (_i, [_vp, _sz, _vp, _i, _i, _vp, _sz, _vp, _vp, _sz, _vp]),
+    "lla_rans_compact_pairs_workspace_bytes": (_sz, [_i]),
+    "lla_rans_compact_pairs": (_i, [_vp, _sz, _vp, _vp, _sz, _vp, _i, _vp, _sz, _vp, _vp, _sz, _vp]),
+    "lla_rans_decode_batch_strided": (_i, [_vp, _vp, _i, _i, _i, _i, _i, _vp, _i, _vp, _vp, _vp, _vp, _vp]),
+    "lla_gaussian_quantise_encode": (_i, [_vp, _i, _i, _i, _vp, _vp, _vp, _sz, _vp, ctypes.c_float, _vp, _i, _i, _vp, _vp,
+                                          _vp, _sz, _vp, _vp, _vp, _vp]),
+    "lla_gaussian_decode_dequantise": (_i, [_vp, _vp, _i, _i, _i, _i, _i, _vp, _vp, _vp, _sz, _vp, ctypes.c_float, _vp, _i,
+                                            _i, _vp, _vp, _vp, _vp, _vp]),
     "lla_rans_decode_batch": (_i, [_vp, _vp, _i, _i, _i, _vp, _i, _vp, _vp, _vp, _vp, _vp]),
     "lla_rans_encode_indexed": (_i, [_vp, _vp, _i, _i, _vp, _i, _i, _vp, _vp, _vp, _sz, _vp, _vp]),
     "lla_rans_decode_indexed": (_i, [_vp, _vp, _i, _i, _i, _vp, _vp, _i, _i, _vp, _vp, _vp, _vp, _vp]),

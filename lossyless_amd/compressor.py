@@ -137,14 +137,7 @@ class ClipCompressor(nn.Module):
                  device="cuda" if torch.cuda.is_available() else "cpu", *,
                  clip_weights=None, vit_chunk=0, gpu_preprocess=False):
         super().__init__()
-        vit_sd, self.clip_weights_desc = resolve_clip_weights(clip_weights)
-        self.clip = VisionTransformer(vit_sd, chunk=vit_chunk)
-        self.gpu_preprocess = bool(gpu_preprocess)
-        self._staging = _PinnedStaging()
-        self.preprocess = RawRGB() if self.gpu_preprocess else ClipPreprocess()
-        self.preprocess_gpu = ClipPreprocessGPU()   # batched twin: uint8 images -> fp16 NHWC
-
-        self.z_dim = 512
+        self._init_tower(clip_weights, vit_chunk, gpu_preprocess)
         self.side_z_dim = 512 // 5
 
         self.scaling = torch.nn.Parameter(torch.ones(self.z_dim))
@@ -166,6 +159,17 @@ class ClipCompressor(nn.Module):
         self.device = device
         self.to(self.device)
         self.eval()
+
+    def _init_tower(self, clip_weights, vit_chunk, gpu_preprocess):
+        """The tower, its preprocessing and the staging buffers: everything before the rate model, shared with the
+        subclasses that put another coder behind the same tower."""
+        vit_sd, self.clip_weights_desc = resolve_clip_weights(clip_weights)
+        self.clip = VisionTransformer(vit_sd, chunk=vit_chunk)
+        self.gpu_preprocess = bool(gpu_preprocess)
+        self._staging = _PinnedStaging()
+        self.preprocess = RawRGB() if self.gpu_preprocess else ClipPreprocess()
+        self.preprocess_gpu = ClipPreprocessGPU()   # batched twin: uint8 images -> fp16 NHWC
+        self.z_dim = 512
 
     def to(self, device):
         self.device = device
@@ -377,8 +381,8 @@ class ClipCompressor(nn.Module):
 
         if rank == 0:
             with Path(file).open("wb") as f:
-                f.write(struct.pack(">I", n_all))   # write_uints(f, (len(Z_bytes),))
-                f.write(body.tobytes())             # N x { >I len, bytes }
+                f.write(struct.pack(">I", n_all * self.records_per_image))   # write_uints(f, (len(Z_bytes),))
+                f.write(body.tobytes())             # records x { >I len, bytes }
             enc_time = (time.time() - start) / max(n_all, 1)
             rate = 8 * Path(file).stat().st_size / max(n_all, 1)
             if label_file is not None:
@@ -393,11 +397,17 @@ class ClipCompressor(nn.Module):
         """One pass of the hot path over one batch: images -> CLIP tower -> quantise -> rANS ->
         compaction into container records (be32 length + stream per image), returned as a
         host uint8 array.  One device->host sync per batch (the reference syncs per image)."""
-        z = self._embed(x)
-        payload, offsets, _ = self.entropy_bottleneck.encode_device(z, self._tables(),
-                                                                    record_prefix=True)
+        payload, offsets = self._encode_records(self._embed(x))
         total = int(offsets[-1])
         return payload[:total].cpu().numpy()
+
+    records_per_image = 1      # container records one image takes (the count the file opens with is over records)
+
+    def _encode_records(self, z):
+        """Embeddings [B,512] on the GPU -> (container records as a device uint8 tensor, record offsets [.. + 1]; the last
+        one is the number of bytes used), nothing synchronised: what :class:`RecordStream` codes a group with."""
+        payload, offsets, _ = self.entropy_bottleneck.encode_device(z, self._tables(), record_prefix=True)
+        return payload, offsets
 
     def _prefetch(self, batches):
         """Host batches -> device batches, one batch ahead: batch i+1 is staged in pinned memory and
@@ -839,8 +849,7 @@ class RecordStream:
             with torch.cuda.stream(self._coder):
                 if self.deferred:
                     c.clip.join(zb.device)          # the coder stream (current here) waits for both lanes
-                payload, offsets, _ = c.entropy_bottleneck.encode_device(
-                    zb[:self.rows], c._tables(), record_prefix=True)
+                payload, offsets = c._encode_records(zb[:self.rows])
                 total_host = torch.empty(1, dtype=offsets.dtype, pin_memory=True)
                 total_host.copy_(offsets[-1:], non_blocking=True)
                 done = torch.cuda.Event()

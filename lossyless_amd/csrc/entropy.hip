@@ -420,7 +420,7 @@ __device__ __forceinline__ bool open_stream(DecState &s, const uint8_t *payload,
 }
 
 __global__ __launch_bounds__(kEncThreads) void rans_decode_kernel(
-    const uint8_t *__restrict__ payload, const uint64_t *__restrict__ off, int skip, int B, int C,
+    const uint8_t *__restrict__ payload, const uint64_t *__restrict__ off, int skip, int off_step, int B, int C,
     const int32_t *__restrict__ cdf, int W, const int32_t *__restrict__ cdf_len,
     const int32_t *__restrict__ offset, int32_t *__restrict__ out, int32_t *__restrict__ status) {
   extern __shared__ __attribute__((aligned(16))) uint8_t smem[];
@@ -435,7 +435,7 @@ __global__ __launch_bounds__(kEncThreads) void rans_decode_kernel(
 
   DecState s;
   int32_t *dst = out + (size_t)img * C;
-  if (!open_stream(s, payload, off, skip & 0xff, img)) {
+  if (!open_stream(s, payload, off, skip & 0xff, img * off_step)) {
     for (int c = 0; c < C; ++c) dst[c] = 0;
     if (status) status[img] = 1;
     return;
@@ -491,38 +491,60 @@ __global__ __launch_bounds__(kEncThreads) void rans_encode_indexed_kernel(
 // entries: the 64-level scale table of lossyless/rates.py:567-569 is 64 x 3133 int32 = 800 KB padded
 // but ~27 000 valid entries = 54 KB) and searched there; when they do not fit the LDS the kernel was
 // given, the rows are searched in global memory (same code, int32 rows).
+struct PackedRows {
+  uint32_t *rowoff;   // [T+1] row starts (u32)
+  int2 *par;          // [T] (len, offset)
+  uint16_t *tab;      // packed rows (u16)
+  bool in_lds;        // uniform: the rows fit the LDS the kernel was given
+};
+__host__ __device__ inline size_t packed_rows_head(int T) {
+  return (((size_t)(T + 1) * 4 + 7) & ~(size_t)7) + (size_t)T * sizeof(int2);
+}
+// Called by every thread of the workgroup (barriers inside).  smem must be 8-byte aligned.
+__device__ __forceinline__ PackedRows stage_packed_rows(uint8_t *smem, unsigned lds_bytes,
+                                                        const int32_t *__restrict__ cdf, int T, int W,
+                                                        const int32_t *__restrict__ cdf_len,
+                                                        const int32_t *__restrict__ offset) {
+  PackedRows r;
+  r.rowoff = reinterpret_cast<uint32_t *>(smem);
+  r.par = reinterpret_cast<int2 *>(smem + (((size_t)(T + 1) * 4 + 7) & ~(size_t)7));
+  r.tab = reinterpret_cast<uint16_t *>(reinterpret_cast<uint8_t *>(r.par) + (size_t)T * sizeof(int2));
+  const size_t head = packed_rows_head(T);
+  r.in_lds = head < lds_bytes;
+  if (r.in_lds) {
+    for (int t = threadIdx.x; t < T; t += blockDim.x) r.par[t] = make_int2(min(max(cdf_len[t], 3), W), offset[t]);
+    __syncthreads();
+    if (threadIdx.x == 0) {
+      uint32_t acc = 0;
+      for (int t = 0; t < T; ++t) { r.rowoff[t] = acc; acc += (uint32_t)r.par[t].x; }
+      r.rowoff[T] = acc;
+    }
+    __syncthreads();
+    r.in_lds = head + (size_t)r.rowoff[T] * 2 <= lds_bytes;   // uniform
+    if (r.in_lds) {
+      for (int t = 0; t < T; ++t) {
+        const int len = r.par[t].x;
+        const int32_t *src = cdf + (size_t)t * W;
+        uint16_t *dst = r.tab + r.rowoff[t];
+        for (int i = threadIdx.x; i < len; i += blockDim.x) dst[i] = (uint16_t)src[i];
+      }
+      __syncthreads();
+    }
+  }
+  return r;
+}
+
 __global__ __launch_bounds__(kEncThreads) void rans_decode_indexed_kernel(
     const uint8_t *__restrict__ payload, const uint64_t *__restrict__ off, int skip, int B, int n,
     const int32_t *__restrict__ indexes, const int32_t *__restrict__ cdf, int T, int W,
     const int32_t *__restrict__ cdf_len, const int32_t *__restrict__ offset,
     int32_t *__restrict__ out, int32_t *__restrict__ status, unsigned lds_bytes) {
   extern __shared__ __attribute__((aligned(16))) uint8_t smem[];
-  // [T+1] row starts (u32) | [T] (len, offset) | packed rows (u16)
-  uint32_t *rowoff = reinterpret_cast<uint32_t *>(smem);
-  int2 *par = reinterpret_cast<int2 *>(smem + (((size_t)(T + 1) * 4 + 7) & ~(size_t)7));
-  uint16_t *tab = reinterpret_cast<uint16_t *>(reinterpret_cast<uint8_t *>(par) + (size_t)T * sizeof(int2));
-  const size_t head = (size_t)(reinterpret_cast<uint8_t *>(tab) - smem);
-  bool in_lds = head < lds_bytes;
-  if (in_lds) {
-    for (int t = threadIdx.x; t < T; t += blockDim.x) par[t] = make_int2(min(max(cdf_len[t], 3), W), offset[t]);
-    __syncthreads();
-    if (threadIdx.x == 0) {
-      uint32_t acc = 0;
-      for (int t = 0; t < T; ++t) { rowoff[t] = acc; acc += (uint32_t)par[t].x; }
-      rowoff[T] = acc;
-    }
-    __syncthreads();
-    in_lds = head + (size_t)rowoff[T] * 2 <= lds_bytes;   // uniform
-    if (in_lds) {
-      for (int t = 0; t < T; ++t) {
-        const int len = par[t].x;
-        const int32_t *src = cdf + (size_t)t * W;
-        uint16_t *dst = tab + rowoff[t];
-        for (int i = threadIdx.x; i < len; i += blockDim.x) dst[i] = (uint16_t)src[i];
-      }
-      __syncthreads();
-    }
-  }
+  const PackedRows rows = stage_packed_rows(smem, lds_bytes, cdf, T, W, cdf_len, offset);
+  const bool in_lds = rows.in_lds;
+  const uint32_t *rowoff = rows.rowoff;
+  const int2 *par = rows.par;
+  const uint16_t *tab = rows.tab;
   const int i = blockIdx.x * kEncThreads + threadIdx.x;
   if (i >= B) return;
   DecState s;
@@ -600,6 +622,195 @@ __global__ void represent_kernel(const void *__restrict__ z, size_t n, int C,
 }
 
 // ---------------------------------------------------------------------------
+// Scale hyperprior, conditional part (lossyless/rates.py:694-729): the table row AND the mean of every element
+// come from the predicted scale, so subtract / round / build_indexes / code (and decode / add / process_z_out)
+// are one kernel each.  One image per lane as above; rows are read from global memory by the encoder (one
+// look-up per symbol, off the state's dependency chain) and searched in LDS by the decoder.
+// ---------------------------------------------------------------------------
+struct __attribute__((aligned(8))) AffineParams {
+  float bias, es;
+};
+
+// LDS both kernels start with: [C] (bias, exp_scale) | [T] scale table (padded to 8 bytes)
+__host__ __device__ inline size_t gauss_head_bytes(int C, int T) {
+  return (size_t)C * sizeof(AffineParams) + (((size_t)T * sizeof(float) + 7) & ~(size_t)7);
+}
+
+__device__ __forceinline__ void stage_gauss_head(uint8_t *smem, int C, int T, const float *__restrict__ bias,
+                                                 const float *__restrict__ exp_scale,
+                                                 const float *__restrict__ scale_table) {
+  AffineParams *aff = reinterpret_cast<AffineParams *>(smem);
+  float *stab = reinterpret_cast<float *>(smem + (size_t)C * sizeof(AffineParams));
+  for (int c = threadIdx.x; c < C; c += blockDim.x) aff[c] = AffineParams{bias[c], exp_scale[c]};
+  for (int t = threadIdx.x; t < T; t += blockDim.x) stab[t] = scale_table[t];
+}
+
+// GaussianConditional.build_indexes for G elements at once (every table entry is read once per group):
+// T-1 minus the number of t < T-1 with max(scale, bound) <= table[t].  Counted as the reference counts it, not
+// searched: nothing is assumed about the table's order, and a NaN scale compares false everywhere (row T-1) as
+// torch.max / <= make it.  The result is in [0, T-1] whatever the scale.
+template <int G>
+__device__ __forceinline__ void scale_rows(const float *stab, int T, float bound, const float (&scale)[G],
+                                           int (&row)[G]) {
+  float sb[G];
+#pragma unroll
+  for (int k = 0; k < G; ++k) {
+    sb[k] = scale[k] < bound ? bound : scale[k];
+    row[k] = T - 1;
+  }
+  for (int t = 0; t < T - 1; ++t) {
+    const float v = stab[t];
+#pragma unroll
+    for (int k = 0; k < G; ++k) row[k] -= sb[k] <= v ? 1 : 0;
+  }
+}
+
+template <int ZMODE>
+__global__ __launch_bounds__(kEncThreads) void gaussian_encode_kernel(
+    const void *__restrict__ in, int B, int C, const float *__restrict__ bias,
+    const float *__restrict__ exp_scale, const float *__restrict__ scales, size_t ld_scales,
+    const float *__restrict__ scale_table, float scale_bound, const int32_t *__restrict__ cdf, int T, int W,
+    const int32_t *__restrict__ cdf_len, const int32_t *__restrict__ offset, uint8_t *__restrict__ scratch,
+    size_t stride, uint32_t *__restrict__ lengths, int32_t *__restrict__ symbols_out,
+    int32_t *__restrict__ indexes_out) {
+  extern __shared__ __attribute__((aligned(16))) uint8_t smem[];
+  const AffineParams *aff = reinterpret_cast<const AffineParams *>(smem);
+  const float *stab = reinterpret_cast<const float *>(smem + (size_t)C * sizeof(AffineParams));
+  int2 *par = reinterpret_cast<int2 *>(smem + gauss_head_bytes(C, T));   // [T] (row length, offset)
+  stage_gauss_head(smem, C, T, bias, exp_scale, scale_table);
+  for (int t = threadIdx.x; t < T; t += blockDim.x) par[t] = make_int2(min(max(cdf_len[t], 3), W), offset[t]);
+  __syncthreads();
+
+  const int img = blockIdx.x * kEncThreads + threadIdx.x;
+  if (img >= B) return;
+
+  using F = Fetch<ZMODE>;
+  constexpr int G = F::G;
+  using elem = typename F::elem;
+  const elem *src = reinterpret_cast<const elem *>(in) + (size_t)img * C;
+  const float *sc = scales + (size_t)img * ld_scales;
+
+  uint8_t *end = scratch + (size_t)img * stride + stride;
+  EncState s;
+  s.x = kStateLow;
+  s.wp = reinterpret_cast<uint32_t *>(end);
+
+  auto prep = [&](int c, elem raw_in, float scale, int t) {
+    const AffineParams a = aff[c];
+    float zf;
+    if constexpr (ZMODE == 1) zf = __half2float(raw_in);
+    else zf = raw_in;
+    // (z + bias) * exp_scale - mean, three separately rounded operations; the mean IS the predicted scale, unbounded
+    const int32_t sym = quantise_one(zf, a.bias, a.es, scale);
+    if (symbols_out) symbols_out[(size_t)img * C + c] = sym;
+    if (indexes_out) indexes_out[(size_t)img * C + c] = t;
+    const int2 q = par[t];
+    return prepare_channel(cdf + (size_t)t * W, q.x, q.y, sym);
+  };
+
+  const int tail = C % G;
+  for (int c = C - 1; c >= C - tail; --c) {
+    const float sv[1] = {sc[c]};
+    int t[1];
+    scale_rows<1>(stab, T, scale_bound, sv, t);
+    emit_channel(s, prep(c, src[c], sv[0], t[0]));
+  }
+  const bool vec_z = (reinterpret_cast<uintptr_t>(src) & 15u) == 0;
+  const bool vec_s = (reinterpret_cast<uintptr_t>(sc) & 15u) == 0;
+  for (int g = (C - tail) / G - 1; g >= 0; --g) {
+    elem v[G];
+    float sv[G];
+    if (vec_z) {
+      *reinterpret_cast<uint4 *>(v) = *reinterpret_cast<const uint4 *>(src + g * G);
+    } else {
+#pragma unroll
+      for (int k = 0; k < G; ++k) v[k] = src[g * G + k];
+    }
+    if (vec_s) {
+#pragma unroll
+      for (int k = 0; k < G; k += 4)
+        *reinterpret_cast<float4 *>(sv + k) = *reinterpret_cast<const float4 *>(sc + g * G + k);
+    } else {
+#pragma unroll
+      for (int k = 0; k < G; ++k) sv[k] = sc[g * G + k];
+    }
+    int t[G];
+    scale_rows<G>(stab, T, scale_bound, sv, t);
+    Prepared pr[G];
+#pragma unroll
+    for (int k = 0; k < G; ++k) pr[k] = prep(g * G + k, v[k], sv[k], t[k]);
+#pragma unroll
+    for (int k = G - 1; k >= 0; --k) emit_channel(s, pr[k]);
+  }
+
+  s.wp -= 2;
+  s.wp[0] = (uint32_t)s.x;
+  s.wp[1] = (uint32_t)(s.x >> 32);
+  lengths[img] = (uint32_t)(end - reinterpret_cast<uint8_t *>(s.wp));
+}
+
+// Inverse: image i's stream is record i * off_step of `off` (off_step = 2 walks the z records of an interleaved
+// (z, side) body).  Every read is bounded by the record (refill) and by the row length (search_row); the row comes
+// from scale_rows, i.e. is in range whatever the scales hold.
+__global__ __launch_bounds__(kEncThreads) void gaussian_decode_kernel(
+    const uint8_t *__restrict__ payload, const uint64_t *__restrict__ off, int skip, int off_step, int B, int C,
+    const float *__restrict__ bias, const float *__restrict__ exp_scale, const float *__restrict__ scales,
+    size_t ld_scales, const float *__restrict__ scale_table, float scale_bound,
+    const int32_t *__restrict__ cdf, int T, int W, const int32_t *__restrict__ cdf_len,
+    const int32_t *__restrict__ offset, float *__restrict__ z_hat, int32_t *__restrict__ status,
+    unsigned lds_bytes) {
+  extern __shared__ __attribute__((aligned(16))) uint8_t smem[];
+  const AffineParams *aff = reinterpret_cast<const AffineParams *>(smem);
+  const float *stab = reinterpret_cast<const float *>(smem + (size_t)C * sizeof(AffineParams));
+  const size_t head = gauss_head_bytes(C, T);     // (<= lds_bytes: checked by the launcher)
+  stage_gauss_head(smem, C, T, bias, exp_scale, scale_table);
+  __syncthreads();
+  const PackedRows rows = stage_packed_rows(smem + head, lds_bytes - (unsigned)head, cdf, T, W, cdf_len, offset);
+
+  const int i = blockIdx.x * kEncThreads + threadIdx.x;
+  if (i >= B) return;
+  DecState s;
+  float *dst = z_hat + (size_t)i * C;
+  if (!open_stream(s, payload, off, skip, i * off_step)) {
+    for (int c = 0; c < C; ++c) dst[c] = 0.f;
+    if (status) status[i] = 1;
+    return;
+  }
+  const float *sc = scales + (size_t)i * ld_scales;
+  // The rows do not depend on the coder state: they are derived a group ahead of the serial decode, so that every
+  // scale-table entry is read once per group (as the encoder does), and the next group's scales are in flight.
+  constexpr int G = 4;
+  float sv_next[G];
+#pragma unroll
+  for (int k = 0; k < G; ++k) sv_next[k] = k < C ? sc[k] : 0.f;
+  for (int c0 = 0; c0 < C; c0 += G) {
+    float sv[G];
+    int t[G];
+#pragma unroll
+    for (int k = 0; k < G; ++k) {
+      sv[k] = sv_next[k];
+      sv_next[k] = c0 + G + k < C ? sc[c0 + G + k] : 0.f;
+    }
+    scale_rows<G>(stab, T, scale_bound, sv, t);
+#pragma unroll
+    for (int k = 0; k < G; ++k) {
+      const int c = c0 + k;
+      if (c >= C) break;
+      int32_t sym;
+      if (rows.in_lds) {
+        const int2 q = rows.par[t[k]];
+        sym = decode_symbol<true>(s, rows.tab + rows.rowoff[t[k]], q.x) + q.y;
+      } else {
+        sym = decode_symbol<true>(s, cdf + (size_t)t[k] * W, min(max(cdf_len[t[k]], 3), W)) + offset[t[k]];
+      }
+      const AffineParams a = aff[c];
+      dst[c] = dequantise_one((float)sym, a.bias, a.es, sv[k]);   // (sym + mean) / exp_scale - bias
+    }
+  }
+  if (status) status[i] = s.pos > s.nwords ? 1 : 0;
+}
+
+// ---------------------------------------------------------------------------
 // compaction: lengths -> exclusive offsets (wave scans) -> wave-per-image copy
 // ---------------------------------------------------------------------------
 constexpr int kScanThreads = 1024;
@@ -663,19 +874,12 @@ __global__ __launch_bounds__(kScanThreads) void final_offsets_kernel(
   if (i < B) out_off[i] = sums_ex[blockIdx.x] + inc - v;
 }
 
-__global__ __launch_bounds__(256) void copy_streams_kernel(
-    const uint8_t *__restrict__ scratch, size_t stride, const uint32_t *__restrict__ lengths,
-    int B, int record_prefix, uint8_t *__restrict__ out, size_t cap,
-    const uint64_t *__restrict__ out_off) {
-  const int img = blockIdx.x * 4 + (threadIdx.x / kWave);
-  const int lane = threadIdx.x & (kWave - 1);
-  if (img >= B) return;
-  const uint32_t len = lengths[img];
-  const uint64_t o = out_off[img];
+// one wave copies one stream (4-byte words) to out + o, behind its big-endian length if record_prefix
+__device__ __forceinline__ void copy_record(const uint8_t *__restrict__ stream_end, uint32_t len, int record_prefix,
+                                            uint8_t *__restrict__ out, size_t cap, uint64_t o, int lane) {
   const uint64_t need = o + len + (record_prefix ? 4u : 0u);
-  if (need > cap) return;  // caller learns the required size from out_off[B]
-  const uint32_t *src =
-      reinterpret_cast<const uint32_t *>(scratch + (size_t)img * stride + stride - len);
+  if (need > cap) return;  // caller learns the required size from the last offset
+  const uint32_t *src = reinterpret_cast<const uint32_t *>(stream_end - len);
   uint32_t *dst = reinterpret_cast<uint32_t *>(out + o);
   if (record_prefix) {
     if (lane == 0) dst[0] = __builtin_bswap32(len);  // big-endian u32, hub/compressor.py:258
@@ -685,11 +889,56 @@ __global__ __launch_bounds__(256) void copy_streams_kernel(
   for (uint32_t w = lane; w < nw; w += kWave) dst[w] = src[w];
 }
 
+__global__ __launch_bounds__(256) void copy_streams_kernel(
+    const uint8_t *__restrict__ scratch, size_t stride, const uint32_t *__restrict__ lengths,
+    int B, int record_prefix, uint8_t *__restrict__ out, size_t cap,
+    const uint64_t *__restrict__ out_off) {
+  const int img = blockIdx.x * 4 + (threadIdx.x / kWave);
+  const int lane = threadIdx.x & (kWave - 1);
+  if (img >= B) return;
+  copy_record(scratch + (size_t)img * stride + stride, lengths[img], record_prefix, out, cap, out_off[img], lane);
+}
+
+// (z, side) pairs: record 2i is image i's stream of scratch_a, record 2i+1 its stream of scratch_b
+__global__ __launch_bounds__(256) void interleave_lengths_kernel(const uint32_t *__restrict__ a,
+                                                                 const uint32_t *__restrict__ b, int B,
+                                                                 uint32_t *__restrict__ out) {
+  const int i = blockIdx.x * 256 + threadIdx.x;
+  if (i >= B) return;
+  out[2 * i] = a[i];
+  out[2 * i + 1] = b[i];
+}
+
+__global__ __launch_bounds__(256) void copy_pairs_kernel(
+    const uint8_t *__restrict__ scratch_a, size_t stride_a, const uint8_t *__restrict__ scratch_b,
+    size_t stride_b, const uint32_t *__restrict__ lengths2, int B, uint8_t *__restrict__ out, size_t cap,
+    const uint64_t *__restrict__ out_off) {
+  const int rec = blockIdx.x * 4 + (threadIdx.x / kWave);
+  const int lane = threadIdx.x & (kWave - 1);
+  if (rec >= 2 * B) return;
+  const int img = rec >> 1;
+  const uint8_t *end = (rec & 1) ? scratch_b + (size_t)img * stride_b + stride_b
+                                 : scratch_a + (size_t)img * stride_a + stride_a;
+  copy_record(end, lengths2[rec], 1, out, cap, out_off[rec], lane);
+}
+
 inline int grid_for(size_t n, int threads, int cap = 2048) {
   size_t g = (n + threads - 1) / threads;
   if (g > (size_t)cap) g = cap;
   if (g < 1) g = 1;
   return (int)g;
+}
+
+// LDS for a decoder that packs the T rows (stage_packed_rows) behind `front` bytes of its own: the rows' valid entries number
+// at most T*W (known exactly only on the device), so the launch asks for min(device limit, front + header + 2*T*W) -- small
+// tables leave room for several workgroups per CU.  The limit and the kernel's opt-in to > 48 KiB are per DEVICE (a process
+// may drive several GPUs).  Returns `front` alone when not even the header fits (absurdly many rows: global-memory search).
+unsigned packed_rows_lds(const void *kernel, size_t front, int T, int W) {
+  const unsigned lds_max = dynamic_lds_limit(kernel);
+  const size_t head = front + packed_rows_head(T);
+  const size_t want = head + 2 * (size_t)T * (size_t)W + 64;
+  return head + 64 > lds_max ? (unsigned)front
+                             : (unsigned)(want < lds_max ? ((want + 255) & ~(size_t)255) : lds_max);
 }
 
 bool table_args_ok(int B, int C, int W, const void *cdf, const void *cdf_len, const void *off) {
@@ -796,20 +1045,67 @@ int lla_rans_compact(const uint8_t *scratch, size_t stride, const uint32_t *leng
   return check_launch();
 }
 
-int lla_rans_decode_batch(const uint8_t *payload, const uint64_t *off, int record_prefix, int B,
-                          int C, const int32_t *cdf, int W, const int32_t *cdf_len,
-                          const int32_t *offset, int32_t *symbols_out, int32_t *status,
-                          void *stream) {
+size_t lla_rans_compact_pairs_workspace_bytes(int B) {
+  const size_t b2 = 2 * (size_t)(B > 0 ? B : 1);     // (2B records; B is below 2^30 where this is used, so b2 fits an int)
+  const size_t nblk = (b2 + kScanThreads - 1) / kScanThreads;
+  return ((b2 * sizeof(uint32_t) + 7) & ~(size_t)7) + (nblk + 1) * sizeof(uint64_t);
+}
+
+int lla_rans_compact_pairs(const uint8_t *scratch_a, size_t stride_a, const uint32_t *lengths_a,
+                           const uint8_t *scratch_b, size_t stride_b, const uint32_t *lengths_b, int B,
+                           uint8_t *out, size_t cap, uint64_t *out_off, void *workspace,
+                           size_t workspace_bytes, void *stream) {
+  hipStream_t st = as_stream(stream);
+  if (B == 0) {
+    if (!out_off) return LLA_EINVAL;
+    hipError_t e = hipMemsetAsync(out_off, 0, sizeof(uint64_t), st);
+    return e == hipSuccess ? LLA_OK : hip_fail(e);
+  }
+  if (!scratch_a || !lengths_a || !scratch_b || !lengths_b || !out || !out_off || !workspace || B < 0 ||
+      B >= (1 << 30))     // (2B records are counted in an int)
+    return LLA_EINVAL;
+  if (workspace_bytes < lla_rans_compact_pairs_workspace_bytes(B)) return LLA_ECAP;
+  if ((reinterpret_cast<uintptr_t>(out) & 3u) || (stride_a & 3u) || (stride_b & 3u) ||
+      (reinterpret_cast<uintptr_t>(workspace) & 7u))
+    return LLA_EINVAL;
+  // the two length arrays interleaved are the lengths of 2B records: the scans of lla_rans_compact do the rest
+  const int B2 = 2 * B;
+  uint32_t *lengths2 = reinterpret_cast<uint32_t *>(workspace);
+  uint64_t *sums = reinterpret_cast<uint64_t *>(reinterpret_cast<uint8_t *>(workspace) +
+                                                (((size_t)B2 * sizeof(uint32_t) + 7) & ~(size_t)7));
+  const int nblk = (B2 + kScanThreads - 1) / kScanThreads;
+  interleave_lengths_kernel<<<(B + 255) / 256, 256, 0, st>>>(lengths_a, lengths_b, B, lengths2);
+  block_sums_kernel<<<nblk, kScanThreads, 0, st>>>(lengths2, B2, 4u, sums);
+  scan_sums_kernel<<<1, kScanThreads, 0, st>>>(sums, nblk, out_off + B2);
+  final_offsets_kernel<<<nblk, kScanThreads, 0, st>>>(lengths2, B2, 4u, sums, out_off);
+  copy_pairs_kernel<<<(B2 + 3) / 4, 256, 0, st>>>(scratch_a, stride_a, scratch_b, stride_b, lengths2, B, out, cap,
+                                                  out_off);
+  return check_launch();
+}
+
+int lla_rans_decode_batch_strided(const uint8_t *payload, const uint64_t *off, int record_prefix,
+                                  int off_first, int off_step, int B, int C, const int32_t *cdf, int W,
+                                  const int32_t *cdf_len, const int32_t *offset, int32_t *symbols_out,
+                                  int32_t *status, void *stream) {
   if (B == 0) return LLA_OK;
-  if (!payload || !off || !symbols_out || !table_args_ok(B, C, W, cdf, cdf_len, offset))
+  if (!payload || !off || !symbols_out || off_first < 0 || off_step < 1 ||
+      !table_args_ok(B, C, W, cdf, cdf_len, offset))
     return LLA_EINVAL;
   const int grid = (B + kEncThreads - 1) / kEncThreads;
   const size_t lds = enc_table_bytes(C, W) + (size_t)C * sizeof(int2);
   if (lds > 64 * 1024) return LLA_EINVAL;
   int skip = record_prefix ? 4 : 0;
   rans_decode_kernel<<<grid, kEncThreads, lds, as_stream(stream)>>>(
-      payload, off, skip, B, C, cdf, W, cdf_len, offset, symbols_out, status);
+      payload, off + off_first, skip, off_step, B, C, cdf, W, cdf_len, offset, symbols_out, status);
   return check_launch();
+}
+
+int lla_rans_decode_batch(const uint8_t *payload, const uint64_t *off, int record_prefix, int B,
+                          int C, const int32_t *cdf, int W, const int32_t *cdf_len,
+                          const int32_t *offset, int32_t *symbols_out, int32_t *status,
+                          void *stream) {
+  return lla_rans_decode_batch_strided(payload, off, record_prefix, 0, 1, B, C, cdf, W, cdf_len, offset,
+                                       symbols_out, status, stream);
 }
 
 int lla_rans_encode_indexed(const int32_t *symbols, const int32_t *indexes, int B, int n,
@@ -836,17 +1132,54 @@ int lla_rans_decode_indexed(const uint8_t *payload, const uint64_t *off, int rec
       !offset || !symbols_out)
     return LLA_EINVAL;
   const int grid = (B + kEncThreads - 1) / kEncThreads;
-  // LDS for the packed rows: their valid entries number at most T*W (known exactly only on the device), so the
-  // launch asks for min(device limit, header + 2*T*W) -- small tables leave room for several workgroups per CU.
-  // The limit and the kernel's opt-in to > 48 KiB are per DEVICE (a process may drive several GPUs).
-  const unsigned lds_max = dynamic_lds_limit(reinterpret_cast<const void *>(rans_decode_indexed_kernel));
-  const size_t head = (((size_t)(T + 1) * 4 + 7) & ~(size_t)7) + (size_t)T * sizeof(int2);
-  const size_t want = head + 2 * (size_t)T * (size_t)W + 64;
-  const unsigned lds = head + 64 > lds_max ? 0u   // (absurdly many rows: global-memory search)
-                                           : (unsigned)(want < lds_max ? ((want + 255) & ~(size_t)255) : lds_max);
+  const unsigned lds = packed_rows_lds(reinterpret_cast<const void *>(rans_decode_indexed_kernel), 0, T, W);
   rans_decode_indexed_kernel<<<grid, kEncThreads, lds, as_stream(stream)>>>(
       payload, off, record_prefix ? 4 : 0, B, n, indexes, cdf, T, W, cdf_len, offset, symbols_out,
       status, lds);
+  return check_launch();
+}
+
+int lla_gaussian_quantise_encode(const void *z, int z_dtype, int B, int C, const float *bias,
+                                 const float *exp_scale, const float *scales, size_t ld_scales,
+                                 const float *scale_table, float scale_bound, const int32_t *cdf, int T, int W,
+                                 const int32_t *cdf_len, const int32_t *offset, uint8_t *scratch, size_t stride,
+                                 uint32_t *lengths, int32_t *symbols_out, int32_t *indexes_out, void *stream) {
+  if (B == 0) return LLA_OK;
+  if (B < 0 || C <= 0 || T <= 0 || W < 3 || !z || !bias || !exp_scale || !scales || ld_scales < (size_t)C ||
+      !scale_table || !cdf || !cdf_len || !offset || !scratch || !lengths)
+    return LLA_EINVAL;
+  if (z_dtype != LLA_Z_F16 && z_dtype != LLA_Z_F32) return LLA_EINVAL;
+  if (stride < lla_rans_max_encoded_bytes(C) || (stride & 3u)) return LLA_ECAP;
+  const size_t lds = gauss_head_bytes(C, T) + (size_t)T * sizeof(int2);
+  if (lds > 64 * 1024) return LLA_EINVAL;
+  const int grid = (B + kEncThreads - 1) / kEncThreads;
+  if (z_dtype == LLA_Z_F16)
+    gaussian_encode_kernel<1><<<grid, kEncThreads, lds, as_stream(stream)>>>(
+        z, B, C, bias, exp_scale, scales, ld_scales, scale_table, scale_bound, cdf, T, W, cdf_len, offset, scratch,
+        stride, lengths, symbols_out, indexes_out);
+  else
+    gaussian_encode_kernel<2><<<grid, kEncThreads, lds, as_stream(stream)>>>(
+        z, B, C, bias, exp_scale, scales, ld_scales, scale_table, scale_bound, cdf, T, W, cdf_len, offset, scratch,
+        stride, lengths, symbols_out, indexes_out);
+  return check_launch();
+}
+
+int lla_gaussian_decode_dequantise(const uint8_t *payload, const uint64_t *off, int record_prefix, int off_first,
+                                   int off_step, int B, int C, const float *bias, const float *exp_scale,
+                                   const float *scales, size_t ld_scales, const float *scale_table,
+                                   float scale_bound, const int32_t *cdf, int T, int W, const int32_t *cdf_len,
+                                   const int32_t *offset, float *z_hat, int32_t *status, void *stream) {
+  if (B == 0) return LLA_OK;
+  if (B < 0 || C <= 0 || T <= 0 || W < 3 || !payload || !off || off_first < 0 || off_step < 1 || !bias ||
+      !exp_scale || !scales || ld_scales < (size_t)C || !scale_table || !cdf || !cdf_len || !offset || !z_hat)
+    return LLA_EINVAL;
+  const size_t front = gauss_head_bytes(C, T);
+  if (front > 32 * 1024) return LLA_EINVAL;
+  const unsigned lds = packed_rows_lds(reinterpret_cast<const void *>(gaussian_decode_kernel), front, T, W);
+  const int grid = (B + kEncThreads - 1) / kEncThreads;
+  gaussian_decode_kernel<<<grid, kEncThreads, lds, as_stream(stream)>>>(
+      payload, off + off_first, record_prefix ? 4 : 0, off_step, B, C, bias, exp_scale, scales, ld_scales,
+      scale_table, scale_bound, cdf, T, W, cdf_len, offset, z_hat, status, lds);
   return check_launch();
 }
 

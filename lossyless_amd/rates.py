@@ -484,3 +484,162 @@ class HRateHyperprior(HRateEstimator):
         indexes, means_hat = self.get_indexes_means_hat(side_z_strings)
         z_hat = self.gaussian_conditional.decompress(z_strings, indexes, means=means_hat)
         return self.process_z_out(z_hat.reshape(z_hat.shape[0], -1))
+
+    # ---- device path: the same strings with nothing crossing the bus.  ``compress`` copies the side strings to the
+    # host, re-joins and DECODES them to get s_hat back, builds the indexes in a 63-step torch loop and copies the z
+    # strings out separately; here s_hat comes from the symbols the side encoder already produced (the coder is
+    # lossless), and subtract / round / build_indexes / code are one kernel (``lla_gaussian_quantise_encode``).
+    def _device_params(self):
+        """What the fused kernels read besides the two models' coding tables, cached per parameter version: the affine
+        as ``process_z_in`` evaluates it, the zero bias / unit scale the side path quantises with, the fp32 scale table."""
+        gc = self.gaussian_conditional
+        dev = self.scaling.device
+        key = (dev, self.scaling._version, self.biasing._version, gc.scale_table.data_ptr(), gc.scale_bound.data_ptr())
+        cached = getattr(self, "_dev_params", None)
+        if cached is None or cached[0] != key:
+            p = dict(bias=self.biasing.detach().float().contiguous(), exp_scale=self._exp_scaling().contiguous(),
+                     side_bias=torch.zeros(self.side_z_dim, dtype=torch.float32, device=dev),
+                     side_scale=torch.ones(self.side_z_dim, dtype=torch.float32, device=dev),
+                     scale_table=gc.scale_table.detach().float().contiguous(),
+                     scale_bound=float(gc.lower_bound_scale.bound.float().item()))
+            self._dev_params = cached = (key, p)
+        return cached[1]
+
+    def _scales_of(self, side_sym):
+        """Side symbols int32 [B, side_z_dim] -> (fp32 matrix the scales are the leading z_dim columns of, its row
+        stride): ``z_encoder(sym + median)``, read in place by the kernels (``chunk_params`` would be a view too)."""
+        s_hat = side_sym.to(torch.float32) + self.entropy_bottleneck.device_tables()["median"][None, :]
+        params = self.z_encoder(s_hat)
+        if params.dtype != torch.float32 or params.stride(1) != 1:
+            params = params.float().contiguous()
+        return params, params.stride(0)
+
+    def _check_device_path(self, what):
+        if not self.is_coder_updated:
+            raise RuntimeError("call update() / prepare_compressor_() first")
+        _require_coder(self.entropy_bottleneck)
+        _require_coder(self.gaussian_conditional)
+        if self.scaling.device.type != "cuda":
+            raise RuntimeError(f"{what} runs on the GPU only (no CPU fallback)")
+
+    @torch.no_grad()
+    def encode_device(self, z, want_symbols=False):
+        """z [B, z_dim] fp16 / fp32 on the GPU -> ``(payload, offsets)``: uint8 device tensor holding the interleaved
+        length-prefixed records ``be32(len z_0) z_0 be32(len side_0) side_0 be32(len z_1) ...`` and int64 device tensor
+        [2B+1] of record offsets (``offsets[-1]`` = bytes used).  Record 2i / 2i+1 are the bytes ``compress(z)`` returns
+        as ``z_strings[i]`` / ``side_z_strings[i]``.  Nothing is copied to the host or synchronised.
+        ``want_symbols``: also return ``dict(side_symbols, z_symbols, z_indexes)`` (int32 device tensors; tests)."""
+        self._check_device_path("encode_device")
+        if z.dim() != 2 or z.shape[1] != self.z_dim:
+            raise ValueError(f"z must be [B, {self.z_dim}], got {tuple(z.shape)}")
+        if z.dtype not in (torch.float16, torch.float32):
+            z = z.float()
+        z = z.contiguous()     # (the kernel reads dense rows: a strided view is copied)
+        _lib.require_cuda(z, "z")
+        L, dev, st = _lib.lib(), z.device, _lib.stream_ptr(z.device)
+        B, C, S = z.shape[0], self.z_dim, self.side_z_dim
+        p, ebt, gct = self._device_params(), self.entropy_bottleneck.device_tables(), self.gaussian_conditional.device_tables()
+
+        def scratch_for(n):
+            stride = int(L.lla_rans_max_encoded_bytes(n))
+            return (stride, torch.empty(max(B, 1) * stride, dtype=torch.uint8, device=dev),
+                    torch.empty(max(B, 1), dtype=torch.int32, device=dev))
+
+        side_z = self.side_encoder(self.process_z_in(z)).contiguous()
+        side_sym = torch.empty((B, S), dtype=torch.int32, device=dev)
+        stride_s, scratch_s, len_s = scratch_for(S)
+        rc = L.lla_quantise_encode(_lib.ptr(side_z), _lib.LLA_Z_F32, B, S, _lib.ptr(p["side_bias"]),
+                                   _lib.ptr(p["side_scale"]), _lib.ptr(ebt["median"]), _lib.ptr(ebt["cdf"]), ebt["W"],
+                                   _lib.ptr(ebt["cdf_len"]), _lib.ptr(ebt["offset"]), _lib.ptr(scratch_s), stride_s,
+                                   _lib.ptr(len_s), _lib.ptr(side_sym), st)
+        _lib.check(rc, "lla_quantise_encode")
+        params, ld = self._scales_of(side_sym)
+        z_sym = torch.empty((B, C), dtype=torch.int32, device=dev) if want_symbols else None
+        z_idx = torch.empty((B, C), dtype=torch.int32, device=dev) if want_symbols else None
+        stride_z, scratch_z, len_z = scratch_for(C)
+        rc = L.lla_gaussian_quantise_encode(
+            _lib.ptr(z), _lib.LLA_Z_F16 if z.dtype == torch.float16 else _lib.LLA_Z_F32, B, C, _lib.ptr(p["bias"]),
+            _lib.ptr(p["exp_scale"]), _lib.ptr(params), ld, _lib.ptr(p["scale_table"]), p["scale_bound"],
+            _lib.ptr(gct["cdf"]), gct["T"], gct["W"], _lib.ptr(gct["cdf_len"]), _lib.ptr(gct["offset"]),
+            _lib.ptr(scratch_z), stride_z, _lib.ptr(len_z), _lib.ptr(z_sym), _lib.ptr(z_idx), st)
+        _lib.check(rc, "lla_gaussian_quantise_encode")
+        cap = max(B, 1) * (stride_z + stride_s + 8)
+        payload = torch.empty(cap, dtype=torch.uint8, device=dev)
+        offsets = torch.empty(2 * B + 1, dtype=torch.int64, device=dev)
+        wsb = int(L.lla_rans_compact_pairs_workspace_bytes(B))
+        ws = torch.empty(wsb, dtype=torch.uint8, device=dev)
+        rc = L.lla_rans_compact_pairs(_lib.ptr(scratch_z), stride_z, _lib.ptr(len_z), _lib.ptr(scratch_s), stride_s,
+                                      _lib.ptr(len_s), B, _lib.ptr(payload), cap, _lib.ptr(offsets), _lib.ptr(ws), wsb, st)
+        _lib.check(rc, "lla_rans_compact_pairs")
+        if want_symbols:
+            return payload, offsets, dict(side_symbols=side_sym, z_symbols=z_sym, z_indexes=z_idx)
+        return payload, offsets
+
+    @torch.no_grad()
+    def decode_device(self, payload, offsets, B):
+        """Inverse of ``encode_device``: payload uint8 (at least 4 bytes longer than ``offsets[-1]``: the decoders read
+        whole words) / offsets int64 [2B+1] on the GPU -> z_hat [B, z_dim] fp32 on the GPU, the values ``decompress``
+        gives for the same strings.  The side records are decoded (``lla_rans_decode_batch_strided``), ``z_encoder``
+        runs, then ``lla_gaussian_decode_dequantise``.  ValueError if a record is malformed: the
+        kernels bound every read and a damaged record sets its image's status, which costs ONE host sync per call, at the
+        end, to read the statuses back."""
+        self._check_device_path("decode_device")
+        if offsets.dtype != torch.int64 or offsets.numel() != 2 * B + 1:
+            raise ValueError("offsets must be int64 [2B+1]")
+        if payload.dtype != torch.uint8 or payload.dim() != 1:
+            raise ValueError("payload must be a 1-D uint8 tensor")
+        payload, offsets = payload.contiguous(), offsets.contiguous()
+        _lib.require_cuda(payload, "payload")
+        _lib.require_cuda(offsets, "offsets")
+        L, dev, st = _lib.lib(), payload.device, _lib.stream_ptr(payload.device)
+        C, S = self.z_dim, self.side_z_dim
+        p, ebt, gct = self._device_params(), self.entropy_bottleneck.device_tables(), self.gaussian_conditional.device_tables()
+        side_sym = torch.empty((B, S), dtype=torch.int32, device=dev)
+        status = torch.zeros((2, max(B, 1)), dtype=torch.int32, device=dev)
+        rc = L.lla_rans_decode_batch_strided(_lib.ptr(payload), _lib.ptr(offsets), 1, 1, 2, B, S, _lib.ptr(ebt["cdf"]),
+                                             ebt["W"], _lib.ptr(ebt["cdf_len"]), _lib.ptr(ebt["offset"]),
+                                             _lib.ptr(side_sym), _lib.ptr(status[0]), st)
+        _lib.check(rc, "lla_rans_decode_batch_strided")
+        params, ld = self._scales_of(side_sym)
+        z_hat = torch.empty((B, C), dtype=torch.float32, device=dev)
+        rc = L.lla_gaussian_decode_dequantise(
+            _lib.ptr(payload), _lib.ptr(offsets), 1, 0, 2, B, C, _lib.ptr(p["bias"]), _lib.ptr(p["exp_scale"]),
+            _lib.ptr(params), ld, _lib.ptr(p["scale_table"]), p["scale_bound"], _lib.ptr(gct["cdf"]), gct["T"], gct["W"],
+            _lib.ptr(gct["cdf_len"]), _lib.ptr(gct["offset"]), _lib.ptr(z_hat), _lib.ptr(status[1]), st)
+        _lib.check(rc, "lla_gaussian_decode_dequantise")
+        if B and int(status.max()) != 0:
+            raise ValueError("malformed rANS stream")
+        return z_hat
+
+    @torch.no_grad()
+    def represent_device(self, z):
+        """z -> the z_hat that ``decode_device(*encode_device(z))`` gives, without coding (the same fp32 operations in the
+        same order: round(side - median) + median, z_encoder, round(z_in - scales) + scales, process_z_out)."""
+        self._check_device_path("represent_device")
+        z_in = self.process_z_in(z)
+        med = self.entropy_bottleneck.device_tables()["median"][None, :]
+        s_hat = torch.round(self.side_encoder(z_in) - med) + med
+        scales = self.z_encoder(s_hat)[:, :self.z_dim]
+        return self.process_z_out(torch.round(z_in - scales) + scales)
+
+
+def synthetic_hyperprior_state_dict(seed=0, z_dim=512):
+    """Seeded random ``HRateHyperprior`` state dict with built coding tables, for tests and benchmarks (no hyperprior
+    checkpoint ships with the reference; rates on these weights mean nothing).  A freshly initialised z_encoder predicts
+    scales near zero, i.e. the first table row everywhere, so the scale half of its last layer gets a per-channel bias
+    spread log-uniformly over (and past both ends of) the 64-level scale table -- 0.03 .. 400 against 0.11 .. 256 -- and
+    larger weights, so that the row also varies from image to image; the side encoder's last layer is scaled up so that the
+    side symbols are not all zero."""
+    with torch.random.fork_rng(devices=[]):
+        torch.manual_seed(seed)
+        m = HRateHyperprior(z_dim).eval()
+        with torch.no_grad():
+            m.scaling.normal_(0.3, 0.1)
+            m.biasing.normal_(0, 0.1)
+            m.side_encoder.module[-1].weight.mul_(8)
+            last = m.z_encoder.module[-1]
+            last.weight[:z_dim].mul_(8)
+            spread = torch.exp(torch.linspace(math.log(0.03), math.log(400.0), z_dim))
+            last.bias[:z_dim] = spread[torch.randperm(z_dim)]
+        m.update(force=True)
+        return {k: v.detach().clone() for k, v in m.state_dict().items()}
