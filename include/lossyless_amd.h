@@ -185,6 +185,29 @@ int lla_rans_decode_batch_strided(const uint8_t *payload, const uint64_t *off, i
                                   const int32_t *cdf_len, const int32_t *offset, int32_t *symbols_out,
                                   int32_t *status, void *stream);
 
+/* Random access into a container body: decode + dequantise the records a caller NAMES, in the order it names them.
+ * Extends the reference's decompress_dataset (hub/compressor.py:209-254: read every record of the file in order, one
+ * decode per image, stack on the host) to what a downstream trainer draws from a compressed dataset -- a shuffled
+ * minibatch, on the device, from a body that stays compressed in device memory.
+ * payload / off (N+1 entries) / record_prefix and the tables exactly as in lla_rans_decode_batch; index [dev] B int64.
+ * Output row b, at z_hat + b*ld_out ELEMENTS (ld_out >= C), is record index[b] dequantised:
+ *   (float(sym) + median) / exp_scale - bias, fp32 per operation  (lla_dequantise; hub/compressor.py:111-115)
+ * z_dtype LLA_Z_F32: bit-equal to lla_rans_decode_batch + lla_dequantise; LLA_Z_F16: that value rounded to nearest
+ * even.  Columns C .. ld_out-1 of a row are never written.  Symbols never reach global memory.
+ * status [dev] B ints: 0 decoded; 1 stream overrun or unopenable (row zeroed); 2 index[b] outside [0, N) (nothing
+ * read for it, row zeroed).  Repeated indices are legal.  B == 0: LLA_OK, no launch. */
+int lla_rans_decode_gather(const uint8_t *payload, const uint64_t *off, int record_prefix, int N,
+                           const int64_t *index, int B, int C, const int32_t *cdf, int W,
+                           const int32_t *cdf_len, const int32_t *offset, const float *bias,
+                           const float *exp_scale, const float *median, void *z_hat, int z_dtype,
+                           size_t ld_out, int32_t *status, void *stream);
+/* Host twin (host pointers, threaded over images): same values, same statuses. */
+int lla_rans_decode_gather_host(const uint8_t *payload, const uint64_t *off, int record_prefix, int N,
+                                const int64_t *index, int B, int C, const int32_t *cdf, int W,
+                                const int32_t *cdf_len, const int32_t *offset, const float *bias,
+                                const float *exp_scale, const float *median, void *z_hat, int z_dtype,
+                                size_t ld_out, int32_t *status);
+
 /* The same two coder calls with an arbitrary table row per symbol, i.e. the full
  * ans.RansEncoder().encode_with_indexes(symbols, indexes, cdfs, cdfs_sizes, offsets) /
  * ans.RansDecoder().decode_with_indexes(...) signatures as GaussianConditional.compress /

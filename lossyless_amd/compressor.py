@@ -643,6 +643,13 @@ class ClipCompressor(nn.Module):
             return Z_hat, Y
         return Z_hat
 
+    def open_dataset(self, file, label_file=None, device=None):
+        """The container ``file`` as a :class:`~lossyless_amd.latents.CompressedLatents`: it stays compressed on
+        ``device`` (default: this compressor's) and serves the rows of any index vector -- shuffled minibatches for a
+        downstream predictor -- where ``decompress_dataset`` inflates the whole file to a host array."""
+        from .latents import CompressedLatents
+        return CompressedLatents(file, self, label_file=label_file, device=device)
+
 
 _HOST_THREADS = 4      # torch intra-op threads during the host side of compress_dataset (see there)
 

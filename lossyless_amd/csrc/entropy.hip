@@ -448,6 +448,130 @@ __global__ __launch_bounds__(kEncThreads) void rans_decode_kernel(
 }
 
 // ---------------------------------------------------------------------------
+// Gather + decode + dequantise: lane b of the launch decodes record index[b] (random access into a container
+// body that stays compressed in device memory) and the workgroup writes the dequantised rows.  One stream per
+// lane as above; the symbols never leave the registers.  A lane that stored its own row would put 64 separate
+// cache lines behind every store of a wave (rows are 2 KB apart), so the values take the indexed decoder's
+// LDS staging in the opposite direction: every lane parks kGatherG channels of its row in LDS, then the
+// workgroup writes them out with four consecutive lanes covering the 64 contiguous bytes (fp32) one row has in
+// the group.
+//   staging: [256 lanes][kGatherG floats] in 16-byte chunks; lane L's chunk j sits at slot (j + (L >> 1)) & 3 of
+//   its 64-byte line.  A ds_write_b128 is served in groups of 8 consecutive lanes over 32 banks; their lines are 64
+//   bytes apart, so without the rotation lanes L, L+2, L+4, L+6 meet in the same four banks (4-way conflict); with it
+//   the eight chunks cover the 32 banks once.  The write-out reads whole lines (4 threads per line, every chunk once).
+// LDS at C = 512, W = 33: table 33 792 + parameters 512 x 20 = 10 240 + staging 16 384 = 60 416 bytes.
+// ---------------------------------------------------------------------------
+constexpr int kGatherG = 16;
+__device__ __forceinline__ float dequantise_one(float q, float bias, float es, float med);   // (with the elementwise kernels, below)
+struct __attribute__((aligned(16))) GatherParams {
+  float bias, es, med;
+  int32_t off;
+};
+__host__ __device__ inline size_t gather_lds_bytes(int C, int W) {
+  return enc_table_bytes(C, W) + (size_t)C * sizeof(GatherParams) + (((size_t)C * sizeof(int32_t) + 15u) & ~(size_t)15u) +
+         (size_t)kEncThreads * kGatherG * sizeof(float);
+}
+
+__device__ __forceinline__ void store_out(float *p, float v) { *p = v; }
+__device__ __forceinline__ void store_out(__half *p, float v) { *p = __float2half_rn(v); }
+__device__ __forceinline__ void store_out4(float *p, const float4 &v) { *reinterpret_cast<float4 *>(p) = v; }
+__device__ __forceinline__ void store_out4(__half *p, const float4 &v) {
+  const __half2 a = __floats2half2_rn(v.x, v.y), b = __floats2half2_rn(v.z, v.w);
+  *reinterpret_cast<uint2 *>(p) = uint2{__builtin_bit_cast(uint32_t, a), __builtin_bit_cast(uint32_t, b)};
+}
+
+template <typename OutT>
+__global__ __launch_bounds__(kEncThreads) void rans_decode_gather_kernel(
+    const uint8_t *__restrict__ payload, const uint64_t *__restrict__ off, int skip, int N,
+    const int64_t *__restrict__ index, int B, int C, const int32_t *__restrict__ cdf, int W,
+    const int32_t *__restrict__ cdf_len, const int32_t *__restrict__ offset, const float *__restrict__ bias,
+    const float *__restrict__ exp_scale, const float *__restrict__ median, OutT *__restrict__ out, size_t ld_out,
+    int32_t *__restrict__ status) {
+  extern __shared__ __attribute__((aligned(16))) uint8_t smem[];
+  uint16_t *tab = reinterpret_cast<uint16_t *>(smem);
+  GatherParams *par = reinterpret_cast<GatherParams *>(smem + enc_table_bytes(C, W));
+  int32_t *len = reinterpret_cast<int32_t *>(par + C);
+  float4 *stage = reinterpret_cast<float4 *>(smem + gather_lds_bytes(C, W) -
+                                             (size_t)kEncThreads * kGatherG * sizeof(float));
+  for (int c = threadIdx.x; c < C; c += blockDim.x) {
+    par[c] = GatherParams{bias[c], exp_scale[c], median[c], offset[c]};
+    len[c] = cdf_len[c];
+  }
+  stage_table(tab, cdf, C * W);
+
+  // No lane leaves before the last barrier: one without a record (past B, index out of range, stream unopenable)
+  // parks zeros, which is also what its row must hold.
+  const int lane = threadIdx.x;
+  const int row0 = blockIdx.x * kEncThreads;
+  const int img = row0 + lane;
+  int st = 0;
+  bool live = false;
+  DecState s;
+  if (img < B) {
+    const int64_t rec = index[img];
+    if (rec < 0 || rec >= (int64_t)N) st = 2;
+    else if (!open_stream(s, payload, off, skip, (int)rec)) st = 1;
+    live = st == 0;
+  }
+
+  constexpr int kChunks = kGatherG / 4;                 // 16-byte chunks per staged line
+  const int rot = lane >> 1;
+  // write-out: 4 threads per row (one chunk each), 64 rows per pass
+  const int wr = lane >> 2, wj = lane & 3;
+  const bool vec_ok = (reinterpret_cast<uintptr_t>(out) % (4 * sizeof(OutT)) == 0) && (ld_out % 4 == 0);
+  const int rows_here = min(kEncThreads, B - row0);
+
+  for (int c0 = 0; c0 < C; c0 += kGatherG) {
+    float v[kGatherG];
+#pragma unroll
+    for (int k = 0; k < kGatherG; ++k) {
+      const int c = c0 + k;
+      v[k] = 0.f;
+      if (live && c < C) {
+        const GatherParams q = par[c];
+        const int32_t sym = decode_symbol<false>(s, tab + c * W, len[c]) + q.off;
+        v[k] = dequantise_one((float)sym, q.bias, q.es, q.med);
+      }
+    }
+#pragma unroll
+    for (int j = 0; j < kChunks; ++j)
+      stage[lane * kChunks + ((j + rot) & 3)] = float4{v[4 * j], v[4 * j + 1], v[4 * j + 2], v[4 * j + 3]};
+    __syncthreads();
+    const int c = c0 + 4 * wj;
+#pragma unroll
+    for (int p = 0; p < kEncThreads / 64; ++p) {
+      const int r = p * 64 + wr;
+      if (r < rows_here && c < C) {
+        const float4 q = stage[r * kChunks + ((wj + (r >> 1)) & 3)];
+        OutT *dst = out + (size_t)(row0 + r) * ld_out + c;
+        if (vec_ok && c + 3 < C) {
+          store_out4(dst, q);
+        } else {
+          store_out(dst, q.x);
+          if (c + 1 < C) store_out(dst + 1, q.y);
+          if (c + 2 < C) store_out(dst + 2, q.z);
+          if (c + 3 < C) store_out(dst + 3, q.w);
+        }
+      }
+    }
+    __syncthreads();
+  }
+
+  if (live && s.pos > s.nwords) st = 1;
+  if (img < B && status) status[img] = st;
+  // A stream that overran is known only now, after other lanes have written its row: once those stores have
+  // completed (agent-scope fence in every thread, then the barrier), its own lane zeroes the row.  Rare path.
+  if (__syncthreads_or(live && st == 1)) {
+    __threadfence();
+    __syncthreads();
+    if (live && st == 1) {
+      OutT *dst = out + (size_t)img * ld_out;
+      for (int c = 0; c < C; ++c) store_out(dst + c, 0.f);
+    }
+  }
+}
+
+// ---------------------------------------------------------------------------
 // Arbitrary table row per symbol (compressai encode_with_indexes / decode_with_indexes as
 // GaussianConditional uses them: lossyless/rates.py:694-729).  One string per lane; rows are
 // read from global memory (a 64-level scale table is T x W = 64 x ~3100 int32, too large for
@@ -1106,6 +1230,31 @@ int lla_rans_decode_batch(const uint8_t *payload, const uint64_t *off, int recor
                           void *stream) {
   return lla_rans_decode_batch_strided(payload, off, record_prefix, 0, 1, B, C, cdf, W, cdf_len, offset,
                                        symbols_out, status, stream);
+}
+
+int lla_rans_decode_gather(const uint8_t *payload, const uint64_t *off, int record_prefix, int N,
+                           const int64_t *index, int B, int C, const int32_t *cdf, int W,
+                           const int32_t *cdf_len, const int32_t *offset, const float *bias,
+                           const float *exp_scale, const float *median, void *z_hat, int z_dtype,
+                           size_t ld_out, int32_t *status, void *stream) {
+  if (z_dtype != LLA_Z_F16 && z_dtype != LLA_Z_F32) return LLA_EINVAL;
+  if (B == 0) return LLA_OK;
+  if (!payload || !off || !index || !bias || !exp_scale || !median || !z_hat || !status || N < 0 ||
+      !table_args_ok(B, C, W, cdf, cdf_len, offset) || ld_out < (size_t)C)
+    return LLA_EINVAL;
+  const int grid = (B + kEncThreads - 1) / kEncThreads;
+  const size_t lds = gather_lds_bytes(C, W);
+  if (lds > 64 * 1024) return LLA_EINVAL;
+  const int skip = record_prefix ? 4 : 0;
+  if (z_dtype == LLA_Z_F16)
+    rans_decode_gather_kernel<__half><<<grid, kEncThreads, lds, as_stream(stream)>>>(
+        payload, off, skip, N, index, B, C, cdf, W, cdf_len, offset, bias, exp_scale, median,
+        reinterpret_cast<__half *>(z_hat), ld_out, status);
+  else
+    rans_decode_gather_kernel<float><<<grid, kEncThreads, lds, as_stream(stream)>>>(
+        payload, off, skip, N, index, B, C, cdf, W, cdf_len, offset, bias, exp_scale, median,
+        reinterpret_cast<float *>(z_hat), ld_out, status);
+  return check_launch();
 }
 
 int lla_rans_encode_indexed(const int32_t *symbols, const int32_t *indexes, int B, int n,

@@ -1,6 +1,7 @@
 // Host-side entry points of liblossyless_amd.so that have no device work.
 #include <algorithm>
 #include <cmath>
+#include <cstring>
 #include <numeric>
 #include <vector>
 
@@ -304,6 +305,64 @@ extern "C" int lla_dequantise_host(const int32_t *symbols, int B, int C, const f
         const float q = v / exp_scale[c];
         z_hat[size_t(b) * C + c] = q - bias[c];
       }
+  });
+  return LLA_OK;
+}
+
+namespace {
+
+// fp32 -> IEEE binary16 bits, round to nearest even (what the device's v_cvt_f16_f32 gives)
+inline uint16_t half_bits_rn(float f) {
+  const _Float16 h = static_cast<_Float16>(f);
+  uint16_t bits;
+  static_assert(sizeof bits == sizeof h, "");
+  std::memcpy(&bits, &h, sizeof bits);
+  return bits;
+}
+
+}  // namespace
+
+extern "C" int lla_rans_decode_gather_host(const uint8_t *payload, const uint64_t *off, int record_prefix,
+                                           int N, const int64_t *index, int B, int C, const int32_t *cdf,
+                                           int W, const int32_t *cdf_len, const int32_t *offset,
+                                           const float *bias, const float *exp_scale, const float *median,
+                                           void *z_hat, int z_dtype, size_t ld_out, int32_t *status) {
+  // Host twin of lla_rans_decode_gather: record index[b] -> row b, decoded and dequantised in one pass over the
+  // image (same fp32 operations as lla_dequantise_host), same statuses, rows of status != 0 zeroed.
+  if (z_dtype != LLA_Z_F16 && z_dtype != LLA_Z_F32) return LLA_EINVAL;
+  if (B == 0) return LLA_OK;
+  if (B < 0 || N < 0 || C <= 0 || !payload || !off || !index || !bias || !exp_scale || !median || !z_hat ||
+      !status || ld_out < size_t(C) || !tables_ok(C, cdf, W, cdf_len, offset))
+    return LLA_EINVAL;
+  const size_t pre = record_prefix ? 4 : 0;
+  for_images(B, [&](int lo, int hi) {
+    std::vector<int32_t> sym((size_t)C);
+    for (int b = lo; b < hi; ++b) {
+      const int64_t rec = index[b];
+      int st = 0;
+      if (rec < 0 || rec >= int64_t(N)) {
+        st = 2;
+      } else {
+        const uint64_t a = off[rec] + pre, e = off[rec + 1];
+        // (the device kernel opens a stream of whole 32-bit words only)
+        st = (e < a || e - a < 8 || ((e - a) & 3u))
+                 ? 1
+                 : decode_image(payload + a, size_t(e - a), C, cdf, W, cdf_len, offset, sym.data());
+      }
+      float *row32 = static_cast<float *>(z_hat) + size_t(b) * ld_out;
+      uint16_t *row16 = static_cast<uint16_t *>(z_hat) + size_t(b) * ld_out;
+      for (int c = 0; c < C; ++c) {
+        float z = 0.f;
+        if (st == 0) {
+          const float v = float(sym[size_t(c)]) + median[c];
+          const float q = v / exp_scale[c];
+          z = q - bias[c];
+        }
+        if (z_dtype == LLA_Z_F32) row32[c] = z;
+        else row16[c] = half_bits_rn(z);
+      }
+      status[b] = st;
+    }
   });
   return LLA_OK;
 }

@@ -193,6 +193,15 @@ class HyperpriorClipCompressor(ClipCompressor):
         raise NotImplementedError("HyperpriorClipCompressor has no host decoder: " + _WHY_NO_CPU)
 
     # ------------------------------------------------------------------ datasets
+    def open_dataset(self, file, label_file=None, device=None):
+        """Not available for hyperprior containers yet (``NotImplementedError``)."""
+        raise NotImplementedError(
+            "HyperpriorClipCompressor.open_dataset: a hyperprior container holds TWO records per image (z string, side "
+            "string), and a z record can only be decoded with the table rows and means that the hyper-synthesis network "
+            "(z_encoder) derives from its decoded side record; lla_rans_decode_gather decodes one self-contained record per "
+            "row. Random access to such files needs a gather of the side records, the fp32 MLP, then a gathered "
+            "conditional decode: a later change. Use decompress_dataset(is_cpu=False).")
+
     @torch.no_grad()
     def decompress_dataset(self, file, label_file=None, is_info=True, is_cpu=False, *, batch_size=65536):
         """Decompress a file written by ``compress_dataset`` -> float32 [N,512] ndarray (and the labels).

@@ -1,0 +1,185 @@
+"""``CompressedLatents`` -- a compressed dataset that stays compressed and serves minibatches.
+
+The reference reads a ``.bin`` container back in one piece (``decompress_dataset``, hub/compressor.py:209-254: every
+record in file order, stacked into a host float32 [N,512] array, 2 KB per image against the ~190 B it takes on disk).
+The consumer the representations are compressed FOR -- a downstream predictor trained from the compressed copy --
+draws shuffled minibatches and wants them on the device.  This class keeps the container body and its record offsets
+resident (in HBM, or in host memory for ``device="cpu"``) and decodes the rows of any index vector with one launch of
+``lla_rans_decode_gather`` (gather + rANS decode + dequantise, csrc/entropy.hip; ``lla_rans_decode_gather_host`` on the
+host): same values, bit for bit, as ``decompress_dataset(...)[indices]``.
+"""
+import ctypes
+
+import numpy as np
+import torch
+
+from . import _lib
+
+_DTYPES = {torch.float32: _lib.LLA_Z_F32, torch.float16: _lib.LLA_Z_F16}
+
+
+def _np_ptr(a):
+    return a.ctypes.data_as(ctypes.c_void_p)
+
+
+class CompressedLatents:
+    """``CompressedLatents(file, compressor, label_file=None, device=None)``
+
+    file         a container written by ``compress_dataset`` (one record per image).
+    compressor   the :class:`~lossyless_amd.compressor.ClipCompressor` whose tables coded it.
+    label_file   optional ``.npy`` of N labels, kept as an int64 tensor on ``device``.
+    device       where the compressed bytes live and the rows are produced; default: the compressor's device.
+                 ``"cpu"`` keeps numpy arrays and decodes with the library's host coder (no GPU needed).
+    """
+
+    def __init__(self, file, compressor, label_file=None, device=None):
+        device = compressor.device if device is None else device
+        self.device = torch.device(device)
+        if self.device.type == "cuda" and not torch.cuda.is_available():
+            raise RuntimeError("CompressedLatents on 'cuda' needs an MI355X (use device='cpu' for the host coder)")
+        if self.device.type == "cuda" and self.device.index is None:
+            self.device = torch.device("cuda", torch.cuda.current_device())
+        self.z_dim = int(compressor.z_dim)
+
+        blob = np.fromfile(str(file), dtype=np.uint8)
+        L = _lib.lib()
+        n = ctypes.c_uint32(0)
+        # (validates the count against the file size before anything is sized by it)
+        _lib.check(L.lla_container_index(_np_ptr(blob), blob.size, None, 0, ctypes.byref(n)), "lla_container_index")
+        self._n = int(n.value)
+        off = np.zeros(self._n + 1, dtype=np.uint64)
+        _lib.check(L.lla_container_index(_np_ptr(blob), blob.size, _np_ptr(off), off.size, ctypes.byref(n)),
+                   "lla_container_index")
+        body = blob[4:]
+        # padded as ClipCompressor._decode_records pads it: streams are read as whole 32-bit words
+        body = np.concatenate([body, np.zeros((-len(body)) % 4 + 4, np.uint8)])
+
+        t = compressor._tables()
+        names = ("cdf", "cdf_len", "offset", "bias", "exp_scale", "median")
+        self._W = int(t["W"])
+        if self.device.type == "cpu":
+            self._body, self._off = body, off
+            self._tab = {k: np.ascontiguousarray(t[k].detach().cpu().numpy()) for k in names}
+        else:
+            self._body = torch.from_numpy(body).to(self.device)
+            self._off = torch.from_numpy(off.astype(np.int64)).to(self.device)
+            self._tab = {k: t[k].detach().to(self.device).contiguous() for k in names}
+        self._labels = None
+        if label_file is not None:
+            y = np.load(label_file, allow_pickle=False).astype(np.int64)
+            if y.shape[0] != self._n:
+                raise ValueError(f"{label_file} holds {y.shape[0]} labels for {self._n} records")
+            self._labels = torch.from_numpy(y).to(self.device)
+
+    def __len__(self):
+        return self._n
+
+    @property
+    def nbytes(self):
+        """Compressed bytes resident: the container body and its record offsets."""
+        return int(self._body.nbytes + self._off.nbytes)
+
+    # ------------------------------------------------------------------ indexing
+    def _index(self, indices):
+        """-> int64 index tensor on ``self.device`` (1-D, contiguous)."""
+        if isinstance(indices, torch.Tensor):
+            idx = indices
+        else:
+            idx = torch.from_numpy(np.asarray(indices, dtype=np.int64))
+        if idx.dtype != torch.int64:
+            if idx.is_floating_point() or idx.dtype == torch.bool:
+                raise TypeError("indices must be integers")
+            idx = idx.to(torch.int64)
+        return idx.reshape(-1).to(self.device).contiguous()
+
+    def take(self, indices, dtype=torch.float32, out=None, check=True):
+        """Rows ``indices`` (list, numpy array or integer tensor on any device; repeats allowed) ->
+        ``[len(indices), 512]`` of ``dtype`` (float32 or float16) on ``self.device``, written into ``out`` if given.
+
+        ``check=True`` reads the per-row status back (one synchronisation): ``IndexError`` for an index outside
+        ``[0, N)`` -- negative indices do not wrap around -- and ``ValueError`` for a malformed stream.  With
+        ``check=False`` nothing is read back; such rows are all zero."""
+        if dtype not in _DTYPES:
+            raise TypeError("dtype must be torch.float32 or torch.float16")
+        idx = self._index(indices)
+        B, C = int(idx.numel()), self.z_dim
+        if out is None:
+            out = torch.empty((B, C), dtype=dtype, device=self.device)
+        elif (out.dtype != dtype or out.device != self.device or out.dim() != 2 or tuple(out.shape) != (B, C)
+              or out.stride(1) != 1 or (B > 1 and out.stride(0) < C)):
+            raise ValueError(f"out must be a [{B}, {C}] {dtype} tensor on {self.device} with contiguous rows")
+        if B == 0:
+            return out
+        ld = int(out.stride(0)) if B > 1 else C
+        status = torch.empty(B, dtype=torch.int32, device=self.device)
+        L, t = _lib.lib(), self._tab
+        if self.device.type == "cpu":
+            rc = L.lla_rans_decode_gather_host(
+                _np_ptr(self._body), _np_ptr(self._off), 1, self._n, _lib.ptr(idx), B, C, _np_ptr(t["cdf"]), self._W,
+                _np_ptr(t["cdf_len"]), _np_ptr(t["offset"]), _np_ptr(t["bias"]), _np_ptr(t["exp_scale"]),
+                _np_ptr(t["median"]), _lib.ptr(out), _DTYPES[dtype], ld, _lib.ptr(status))
+            _lib.check(rc, "lla_rans_decode_gather_host")
+        else:
+            with torch.cuda.device(self.device):
+                rc = L.lla_rans_decode_gather(
+                    _lib.ptr(self._body), _lib.ptr(self._off), 1, self._n, _lib.ptr(idx), B, C, _lib.ptr(t["cdf"]),
+                    self._W, _lib.ptr(t["cdf_len"]), _lib.ptr(t["offset"]), _lib.ptr(t["bias"]),
+                    _lib.ptr(t["exp_scale"]), _lib.ptr(t["median"]), _lib.ptr(out), _DTYPES[dtype], ld,
+                    _lib.ptr(status), _lib.stream_ptr(self.device))
+            _lib.check(rc, "lla_rans_decode_gather")
+        if check:
+            worst = int(status.max())
+            if worst == 2:
+                bad = int(idx[status == 2][0])
+                raise IndexError(f"index {bad} is out of range for {self._n} records (negative indices do not wrap)")
+            if worst != 0:
+                raise ValueError("malformed rANS stream in container")
+        return out
+
+    def __getitem__(self, key):
+        if isinstance(key, slice):
+            return self.take(torch.arange(*key.indices(self._n)))
+        if isinstance(key, (int, np.integer)):
+            return self.take([int(key)])[0]
+        return self.take(key)
+
+    def labels(self, indices):
+        """Labels of rows ``indices`` (int64 on ``self.device``); ``IndexError`` outside ``[0, N)``."""
+        if self._labels is None:
+            raise ValueError("no label file was given")
+        idx = self._index(indices)
+        if idx.numel() and (int(idx.min()) < 0 or int(idx.max()) >= self._n):
+            raise IndexError(f"index out of range for {self._n} records (negative indices do not wrap)")
+        return self._labels[idx]
+
+    def all(self, dtype=torch.float32):
+        """Every row in file order: ``take(arange(N))``."""
+        return self.take(torch.arange(self._n), dtype=dtype)
+
+    def batches(self, batch_size, shuffle=False, generator=None, drop_last=False, dtype=torch.float32,
+                decode_group=65536):
+        """Iterate over the dataset in minibatches: yields ``z`` (``[batch_size, 512]``, the last one shorter unless
+        ``drop_last``), or ``(z, y)`` when the object holds labels.
+
+        ``decode_group`` indices are decoded per launch and the minibatches are VIEWS of that buffer (valid until the
+        next group is decoded): one lane decodes one record, a serial chain of 512 symbols, so a launch of a few
+        hundred records is bound by that chain's latency and leaves most of the chip idle, while 65536 records fill
+        it.  The launch is therefore amortised over many minibatches; ``decode_group`` is rounded down to a multiple
+        of ``batch_size`` (at least one batch).  The batches do not depend on it.
+
+        With ``shuffle`` the order is ``torch.randperm(N, generator=generator)`` drawn on the CPU, so a seed gives the
+        same order whatever device the object lives on."""
+        batch_size = int(batch_size)
+        if batch_size < 1:
+            raise ValueError("batch_size must be positive")
+        order = torch.randperm(self._n, generator=generator) if shuffle else torch.arange(self._n)
+        group = max(int(decode_group) // batch_size, 1) * batch_size
+        for g0 in range(0, self._n, group):
+            idx = order[g0:g0 + group].to(self.device)
+            z = self.take(idx, dtype=dtype)
+            y = self._labels[idx] if self._labels is not None else None
+            for b0 in range(0, idx.numel(), batch_size):
+                if drop_last and b0 + batch_size > idx.numel():
+                    return
+                zb = z[b0:b0 + batch_size]
+                yield zb if y is None else (zb, y[b0:b0 + batch_size])
