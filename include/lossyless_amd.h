@@ -201,6 +201,23 @@ int lla_rans_decode_gather(const uint8_t *payload, const uint64_t *off, int reco
                            const int32_t *cdf_len, const int32_t *offset, const float *bias,
                            const float *exp_scale, const float *median, void *z_hat, int z_dtype,
                            size_t ld_out, int32_t *status, void *stream);
+/* lla_rans_decode_gather over every off_step-th record of an interleaved body: output row b is record
+ * off_first + index[b]*off_step of `off`, N is the number of IMAGES (index[b] in [0, N)), and `off` holds at least
+ * off_first + (N-1)*off_step + 2 entries.  The record number is computed in 64 bits and checked before anything is
+ * read.  lla_rans_decode_gather is off_first = 0, off_step = 1 of the same kernel.  off_first = 1, off_step = 2 walks
+ * the side records of a body written by lla_rans_compact_pairs, i.e. the first half of lossyless/rates.py:715-724
+ * (get_indexes_means_hat: EntropyBottleneck.decompress of the side strings) for the images a caller names.
+ * With a zero bias, a unit exp_scale and the bottleneck's medians the value written is
+ *   (float(sym) + median) / 1 - 0  ==  float(sym) + median      exactly: x / 1 and x - 0 round to x,
+ * which is s_hat; with ld_out = the padded K of z_encoder's first layer it lands in the zero-padded fp32 A matrix of
+ * that layer's lla_gemm_f32 (columns C .. ld_out-1 are never written and keep their zeros): no int32 symbols, no
+ * conversion pass, no padding copy.  HyperpriorLatents (lossyless_amd/latents.py) depends on that equality.
+ * LLA_EINVAL for off_first < 0 or off_step < 1. */
+int lla_rans_decode_gather_strided(const uint8_t *payload, const uint64_t *off, int record_prefix, int off_first,
+                                   int off_step, int N, const int64_t *index, int B, int C, const int32_t *cdf,
+                                   int W, const int32_t *cdf_len, const int32_t *offset, const float *bias,
+                                   const float *exp_scale, const float *median, void *z_hat, int z_dtype,
+                                   size_t ld_out, int32_t *status, void *stream);
 /* Host twin (host pointers, threaded over images): same values, same statuses. */
 int lla_rans_decode_gather_host(const uint8_t *payload, const uint64_t *off, int record_prefix, int N,
                                 const int64_t *index, int B, int C, const int32_t *cdf, int W,
@@ -257,6 +274,35 @@ int lla_gaussian_decode_dequantise(const uint8_t *payload, const uint64_t *off, 
                                    const float *scales, size_t ld_scales, const float *scale_table,
                                    float scale_bound, const int32_t *cdf, int T, int W, const int32_t *cdf_len,
                                    const int32_t *offset, float *z_hat, int32_t *status, void *stream);
+
+/* Random access into the z records of an interleaved body: the second half of lossyless/rates.py:715-724
+ * (GaussianConditional.decompress(z_strings, indexes, means=means_hat) + process_z_out) for the images a caller
+ * names.  Output row b is record off_first + index[b]*off_step of `off` (N images, `off` as in
+ * lla_rans_decode_gather_strided; off_first = 0, off_step = 2 for the z records), decoded exactly as
+ * lla_gaussian_decode_dequantise decodes it: row and mean from scales[b*ld_scales + c] -- indexed by the OUTPUT row b,
+ * not by the record: the caller's MLP ran on the gathered side information -- and
+ *   z_hat = (float(sym) + mean) / exp_scale - bias,
+ * written at z_hat + b*ld_out ELEMENTS (ld_out >= C) as fp32 (LLA_Z_F32: bit-equal to lla_gaussian_decode_dequantise
+ * on the same record and scales) or as that value rounded to nearest even (LLA_Z_F16).  Columns C .. ld_out-1 are
+ * never written.
+ * status_in [dev] B ints or NULL: a non-zero entry (the side pass's status of that row) means the row's scales are
+ * not to be trusted: nothing is read for it, the row is zeroed and the entry is copied to status[b].
+ * status [dev] B ints: 0 decoded; 1 stream overrun or unopenable (row zeroed); 2 index[b] outside [0, N) (nothing
+ * read, row zeroed).  Repeated indices are legal.  B == 0: LLA_OK, no launch.  LLA_EINVAL for off_first < 0 or
+ * off_step < 1. */
+int lla_gaussian_decode_gather(const uint8_t *payload, const uint64_t *off, int record_prefix, int off_first,
+                               int off_step, int N, const int64_t *index, int B, int C, const float *bias,
+                               const float *exp_scale, const float *scales, size_t ld_scales,
+                               const float *scale_table, float scale_bound, const int32_t *cdf, int T, int W,
+                               const int32_t *cdf_len, const int32_t *offset, void *z_hat, int z_dtype,
+                               size_t ld_out, const int32_t *status_in, int32_t *status, void *stream);
+
+/* What a launch of lla_gaussian_decode_gather on the CURRENT device asks for: returns the dynamic LDS request in
+ * bytes (0 for arguments the entry point refuses) and stores in *front (may be NULL) the bytes in front of the
+ * packed rows (affine, scale table, vote, staging).  The rows are searched in LDS when
+ *   *front + 8*ceil((T+1)/2) + 8*T + 2 * sum_t min(max(cdf_len[t], 3), W)  <=  the value returned,
+ * and in global memory otherwise (same results): a caller that depends on the LDS path checks this. */
+size_t lla_gaussian_decode_gather_lds_bytes(int C, int T, int W, int z_dtype, size_t *front);
 
 /* EntropyModel.dequantize + process_z_out (hub/compressor.py:111-115):
  * z_hat = (float(sym) + median) / exp_scale - bias, fp32 per operation. */

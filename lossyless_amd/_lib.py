@@ -52,6 +52,11 @@ _SIGNATURES = {
                                             _i, _vp, _vp, _vp, _vp, _vp]),
     "lla_rans_decode_batch": (_i, [_vp, _vp, _i, _i, _i, _vp, _i, _vp, _vp, _vp, _vp, _vp]),
     "lla_rans_decode_gather": (_i, [_vp, _vp, _i, _i, _vp, _i, _i, _vp, _i, _vp, _vp, _vp, _vp, _vp, _vp, _i, _sz, _vp, _vp]),
+    "lla_rans_decode_gather_strided": (_i, [_vp, _vp, _i, _i, _i, _i, _vp, _i, _i, _vp, _i, _vp, _vp, _vp, _vp, _vp, _vp, _i,
+                                            _sz, _vp, _vp]),
+    "lla_gaussian_decode_gather": (_i, [_vp, _vp, _i, _i, _i, _i, _vp, _i, _i, _vp, _vp, _vp, _sz, _vp, ctypes.c_float, _vp,
+                                        _i, _i, _vp, _vp, _vp, _i, _sz, _vp, _vp, _vp]),
+    "lla_gaussian_decode_gather_lds_bytes": (_sz, [_i, _i, _i, _i, _vp]),
     "lla_rans_decode_gather_host": (_i, [_vp, _vp, _i, _i, _vp, _i, _i, _vp, _i, _vp, _vp, _vp, _vp, _vp, _vp, _i, _sz, _vp]),
     "lla_rans_encode_indexed": (_i, [_vp, _vp, _i, _i, _vp, _i, _i, _vp, _vp, _vp, _sz, _vp, _vp]),
     "lla_rans_decode_indexed": (_i, [_vp, _vp, _i, _i, _i, _vp, _vp, _i, _i, _vp, _vp, _vp, _vp, _vp]),

@@ -408,7 +408,7 @@ __device__ __forceinline__ int32_t decode_symbol(DecState &s, const RowT *row, i
 }
 
 __device__ __forceinline__ bool open_stream(DecState &s, const uint8_t *payload, const uint64_t *off,
-                                            int skip, int i) {
+                                            int skip, size_t i) {
   const uint64_t begin = off[i] + (uint64_t)skip;
   const uint64_t endb = off[i + 1];
   s.w = reinterpret_cast<const uint32_t *>(payload + begin);
@@ -482,7 +482,7 @@ __device__ __forceinline__ void store_out4(__half *p, const float4 &v) {
 
 template <typename OutT>
 __global__ __launch_bounds__(kEncThreads) void rans_decode_gather_kernel(
-    const uint8_t *__restrict__ payload, const uint64_t *__restrict__ off, int skip, int N,
+    const uint8_t *__restrict__ payload, const uint64_t *__restrict__ off, int skip, int off_first, int off_step, int N,
     const int64_t *__restrict__ index, int B, int C, const int32_t *__restrict__ cdf, int W,
     const int32_t *__restrict__ cdf_len, const int32_t *__restrict__ offset, const float *__restrict__ bias,
     const float *__restrict__ exp_scale, const float *__restrict__ median, OutT *__restrict__ out, size_t ld_out,
@@ -508,9 +508,11 @@ __global__ __launch_bounds__(kEncThreads) void rans_decode_gather_kernel(
   bool live = false;
   DecState s;
   if (img < B) {
+    // image index[img] is record off_first + index * off_step: in 64 bits, and only once the index is known to be in
+    // [0, N) (the product is then below 2^62)
     const int64_t rec = index[img];
     if (rec < 0 || rec >= (int64_t)N) st = 2;
-    else if (!open_stream(s, payload, off, skip, (int)rec)) st = 1;
+    else if (!open_stream(s, payload, off, skip, (size_t)((int64_t)off_first + rec * (int64_t)off_step))) st = 1;
     live = st == 0;
   }
 
@@ -935,6 +937,175 @@ __global__ __launch_bounds__(kEncThreads) void gaussian_decode_kernel(
 }
 
 // ---------------------------------------------------------------------------
+// Gathered conditional decode (the second half of lossyless/rates.py:715-724 for the images a caller names): lane b
+// decodes record off_first + index[b] * off_step with the rows and means of scales row b, exactly as
+// gaussian_decode_kernel does (scale_rows, decode_symbol<true>, dequantise_one), but neither its scales nor its values
+// go lane by lane through 2 KB-apart rows.  Both take rans_decode_gather_kernel's staging (same 16-byte chunks, same
+// rotation by lane >> 1, four threads per 64-byte line):
+//   scales  global -> LDS: the workgroup reads the 256 x kGatherG block of group g + 1 with 16-byte loads (four
+//           consecutive threads cover the 64 contiguous bytes a row has in the group) BEFORE it decodes group g, and
+//           parks it after; every lane then takes its own row from LDS.  Two buffers: a fast wave parks group g + 1
+//           while a slow one may still be reading group g.
+//   values  LDS -> global: as in rans_decode_gather_kernel.
+// LDS in front of the packed rows: gauss_head_bytes + 16 + 3 x 256 x kGatherG x 4 = 4 352 + 16 + 49 152 bytes at C = 512,
+// T = 64.  No static LDS (the vote is a word of the dynamic block, not __syncthreads_or's array): the launch may ask for
+// the whole opt-in limit, as gaussian_decode_kernel does.
+// Every lane reaches every barrier; a lane without a record (past B, status_in set, index out of range, stream
+// unopenable) skips the decode and parks zeros.
+// ---------------------------------------------------------------------------
+constexpr size_t kGatherStageBytes = (size_t)kEncThreads * kGatherG * sizeof(float);
+__host__ __device__ inline size_t gauss_gather_front(int C, int T) {
+  return ((gauss_head_bytes(C, T) + 15u) & ~(size_t)15u) + 16 + 3 * kGatherStageBytes;   // (16: the overrun vote)
+}
+
+template <typename OutT>
+__global__ __launch_bounds__(kEncThreads) void gaussian_decode_gather_kernel(
+    const uint8_t *__restrict__ payload, const uint64_t *__restrict__ off, int skip, int off_first, int off_step, int N,
+    const int64_t *__restrict__ index, int B, int C, const float *__restrict__ bias,
+    const float *__restrict__ exp_scale, const float *__restrict__ scales, size_t ld_scales,
+    const float *__restrict__ scale_table, float scale_bound, const int32_t *__restrict__ cdf, int T, int W,
+    const int32_t *__restrict__ cdf_len, const int32_t *__restrict__ offset, OutT *__restrict__ out, size_t ld_out,
+    const int32_t *__restrict__ status_in, int32_t *__restrict__ status, unsigned lds_bytes) {
+  extern __shared__ __attribute__((aligned(16))) uint8_t smem[];
+  const AffineParams *aff = reinterpret_cast<const AffineParams *>(smem);
+  const float *stab = reinterpret_cast<const float *>(smem + (size_t)C * sizeof(AffineParams));
+  const size_t front = gauss_gather_front(C, T);     // (<= lds_bytes: checked by the launcher)
+  float4 *sstage = reinterpret_cast<float4 *>(smem + front - 3 * kGatherStageBytes);   // [2][256][kGatherG] scales
+  float4 *stage = reinterpret_cast<float4 *>(smem + front - kGatherStageBytes);        // [256][kGatherG] values
+  int *vote = reinterpret_cast<int *>(smem + front - 3 * kGatherStageBytes - 16);
+  stage_gauss_head(smem, C, T, bias, exp_scale, scale_table);
+  if (threadIdx.x == 0) *vote = 0;
+  __syncthreads();
+  const PackedRows rows = stage_packed_rows(smem + front, lds_bytes - (unsigned)front, cdf, T, W, cdf_len, offset);
+
+  const int lane = threadIdx.x;
+  const int row0 = blockIdx.x * kEncThreads;
+  const int img = row0 + lane;
+  int st = 0;
+  bool live = false;
+  DecState s;
+  if (img < B) {
+    const int64_t rec = index[img];
+    if (status_in && status_in[img] != 0) st = status_in[img];
+    else if (rec < 0 || rec >= (int64_t)N) st = 2;
+    else if (!open_stream(s, payload, off, skip, (size_t)((int64_t)off_first + rec * (int64_t)off_step))) st = 1;
+    live = st == 0;
+  }
+
+  constexpr int kChunks = kGatherG / 4;                 // 16-byte chunks per staged line
+  constexpr int kPasses = kEncThreads / 64;             // 4 threads per row, 64 rows per pass
+  const int rot = lane >> 1;
+  const int wr = lane >> 2, wj = lane & 3;
+  const bool vec_ok = (reinterpret_cast<uintptr_t>(out) % (4 * sizeof(OutT)) == 0) && (ld_out % 4 == 0);
+  const bool vec_in = ((reinterpret_cast<uintptr_t>(scales) & 15u) == 0) && (ld_scales % 4 == 0);
+  const int rows_here = min(kEncThreads, B - row0);
+
+  // this thread's share of the scales block of the group at c0: chunk wj of rows p * 64 + wr (zeros outside B x C)
+  auto fetch = [&](int c0, float4 (&q)[kPasses]) {
+    const int c = c0 + 4 * wj;
+#pragma unroll
+    for (int p = 0; p < kPasses; ++p) {
+      const int r = p * 64 + wr;
+      q[p] = float4{0.f, 0.f, 0.f, 0.f};
+      if (r < rows_here && c < C) {
+        const float *src = scales + (size_t)(row0 + r) * ld_scales + c;
+        if (vec_in && c + 3 < C) {
+          q[p] = *reinterpret_cast<const float4 *>(src);
+        } else {
+          q[p].x = src[0];
+          if (c + 1 < C) q[p].y = src[1];
+          if (c + 2 < C) q[p].z = src[2];
+          if (c + 3 < C) q[p].w = src[3];
+        }
+      }
+    }
+  };
+  auto park = [&](float4 *buf, const float4 (&q)[kPasses]) {
+#pragma unroll
+    for (int p = 0; p < kPasses; ++p) {
+      const int r = p * 64 + wr;
+      buf[r * kChunks + ((wj + (r >> 1)) & 3)] = q[p];
+    }
+  };
+
+  float4 nx[kPasses];
+  fetch(0, nx);
+  park(sstage, nx);
+  __syncthreads();
+
+  int g = 0;
+  for (int c0 = 0; c0 < C; c0 += kGatherG, ++g) {
+    const float4 *sbuf = sstage + (size_t)(g & 1) * kEncThreads * kChunks;
+    const bool more = c0 + kGatherG < C;               // (uniform)
+    if (more) fetch(c0 + kGatherG, nx);                // in flight under this group's decode
+
+    // the lane's own line, one 16-byte chunk (four channels) at a time as gaussian_decode_kernel walks a row: the rows
+    // of four elements are counted together, the next chunk's scales are requested ahead of the serial decode.  (Not
+    // unrolled over the chunks: sixteen copies of the tree search would not help a chain that waits on the LDS.)
+    float4 qs = sbuf[lane * kChunks + (rot & 3)];
+#pragma unroll 1
+    for (int j = 0; j < kChunks; ++j) {
+      const float sv[4] = {qs.x, qs.y, qs.z, qs.w};
+      if (j + 1 < kChunks) qs = sbuf[lane * kChunks + ((j + 1 + rot) & 3)];
+      float v[4] = {0.f, 0.f, 0.f, 0.f};
+      if (live) {
+        int t[4];
+        scale_rows<4>(stab, T, scale_bound, sv, t);
+#pragma unroll
+        for (int k = 0; k < 4; ++k) {
+          const int c = c0 + 4 * j + k;
+          if (c >= C) break;
+          int32_t sym;
+          if (rows.in_lds) {
+            const int2 q = rows.par[t[k]];
+            sym = decode_symbol<true>(s, rows.tab + rows.rowoff[t[k]], q.x) + q.y;
+          } else {
+            sym = decode_symbol<true>(s, cdf + (size_t)t[k] * W, min(max(cdf_len[t[k]], 3), W)) + offset[t[k]];
+          }
+          const AffineParams a = aff[c];
+          v[k] = dequantise_one((float)sym, a.bias, a.es, sv[k]);   // (sym + mean) / exp_scale - bias
+        }
+      }
+      stage[lane * kChunks + ((j + rot) & 3)] = float4{v[0], v[1], v[2], v[3]};
+    }
+    if (more) park(sstage + (size_t)((g + 1) & 1) * kEncThreads * kChunks, nx);
+    __syncthreads();
+    const int c = c0 + 4 * wj;
+#pragma unroll
+    for (int p = 0; p < kPasses; ++p) {
+      const int r = p * 64 + wr;
+      if (r < rows_here && c < C) {
+        const float4 q = stage[r * kChunks + ((wj + (r >> 1)) & 3)];
+        OutT *dst = out + (size_t)(row0 + r) * ld_out + c;
+        if (vec_ok && c + 3 < C) {
+          store_out4(dst, q);
+        } else {
+          store_out(dst, q.x);
+          if (c + 1 < C) store_out(dst + 1, q.y);
+          if (c + 2 < C) store_out(dst + 2, q.z);
+          if (c + 3 < C) store_out(dst + 3, q.w);
+        }
+      }
+    }
+    __syncthreads();
+  }
+
+  if (live && s.pos > s.nwords) st = 1;
+  if (img < B && status) status[img] = st;
+  // an overrun is known only now, after other lanes have written the row: vote, fence, zero (rans_decode_gather_kernel)
+  if (live && st == 1) *vote = 1;
+  __syncthreads();
+  if (*vote) {
+    __threadfence();
+    __syncthreads();
+    if (live && st == 1) {
+      OutT *dst = out + (size_t)img * ld_out;
+      for (int c = 0; c < C; ++c) store_out(dst + c, 0.f);
+    }
+  }
+}
+
+// ---------------------------------------------------------------------------
 // compaction: lengths -> exclusive offsets (wave scans) -> wave-per-image copy
 // ---------------------------------------------------------------------------
 constexpr int kScanThreads = 1024;
@@ -1232,12 +1403,13 @@ int lla_rans_decode_batch(const uint8_t *payload, const uint64_t *off, int recor
                                        symbols_out, status, stream);
 }
 
-int lla_rans_decode_gather(const uint8_t *payload, const uint64_t *off, int record_prefix, int N,
-                           const int64_t *index, int B, int C, const int32_t *cdf, int W,
-                           const int32_t *cdf_len, const int32_t *offset, const float *bias,
-                           const float *exp_scale, const float *median, void *z_hat, int z_dtype,
-                           size_t ld_out, int32_t *status, void *stream) {
+int lla_rans_decode_gather_strided(const uint8_t *payload, const uint64_t *off, int record_prefix, int off_first,
+                                   int off_step, int N, const int64_t *index, int B, int C, const int32_t *cdf,
+                                   int W, const int32_t *cdf_len, const int32_t *offset, const float *bias,
+                                   const float *exp_scale, const float *median, void *z_hat, int z_dtype,
+                                   size_t ld_out, int32_t *status, void *stream) {
   if (z_dtype != LLA_Z_F16 && z_dtype != LLA_Z_F32) return LLA_EINVAL;
+  if (off_first < 0 || off_step < 1) return LLA_EINVAL;
   if (B == 0) return LLA_OK;
   if (!payload || !off || !index || !bias || !exp_scale || !median || !z_hat || !status || N < 0 ||
       !table_args_ok(B, C, W, cdf, cdf_len, offset) || ld_out < (size_t)C)
@@ -1248,13 +1420,22 @@ int lla_rans_decode_gather(const uint8_t *payload, const uint64_t *off, int reco
   const int skip = record_prefix ? 4 : 0;
   if (z_dtype == LLA_Z_F16)
     rans_decode_gather_kernel<__half><<<grid, kEncThreads, lds, as_stream(stream)>>>(
-        payload, off, skip, N, index, B, C, cdf, W, cdf_len, offset, bias, exp_scale, median,
+        payload, off, skip, off_first, off_step, N, index, B, C, cdf, W, cdf_len, offset, bias, exp_scale, median,
         reinterpret_cast<__half *>(z_hat), ld_out, status);
   else
     rans_decode_gather_kernel<float><<<grid, kEncThreads, lds, as_stream(stream)>>>(
-        payload, off, skip, N, index, B, C, cdf, W, cdf_len, offset, bias, exp_scale, median,
+        payload, off, skip, off_first, off_step, N, index, B, C, cdf, W, cdf_len, offset, bias, exp_scale, median,
         reinterpret_cast<float *>(z_hat), ld_out, status);
   return check_launch();
+}
+
+int lla_rans_decode_gather(const uint8_t *payload, const uint64_t *off, int record_prefix, int N,
+                           const int64_t *index, int B, int C, const int32_t *cdf, int W,
+                           const int32_t *cdf_len, const int32_t *offset, const float *bias,
+                           const float *exp_scale, const float *median, void *z_hat, int z_dtype,
+                           size_t ld_out, int32_t *status, void *stream) {
+  return lla_rans_decode_gather_strided(payload, off, record_prefix, 0, 1, N, index, B, C, cdf, W, cdf_len, offset,
+                                        bias, exp_scale, median, z_hat, z_dtype, ld_out, status, stream);
 }
 
 int lla_rans_encode_indexed(const int32_t *symbols, const int32_t *indexes, int B, int n,
@@ -1329,6 +1510,46 @@ int lla_gaussian_decode_dequantise(const uint8_t *payload, const uint64_t *off, 
   gaussian_decode_kernel<<<grid, kEncThreads, lds, as_stream(stream)>>>(
       payload, off + off_first, record_prefix ? 4 : 0, off_step, B, C, bias, exp_scale, scales, ld_scales,
       scale_table, scale_bound, cdf, T, W, cdf_len, offset, z_hat, status, lds);
+  return check_launch();
+}
+
+size_t lla_gaussian_decode_gather_lds_bytes(int C, int T, int W, int z_dtype, size_t *front) {
+  if (front) *front = 0;
+  if ((z_dtype != LLA_Z_F16 && z_dtype != LLA_Z_F32) || C <= 0 || T <= 0 || W < 3 || gauss_head_bytes(C, T) > 32 * 1024)
+    return 0;
+  const size_t fr = gauss_gather_front(C, T);
+  const void *kernel = z_dtype == LLA_Z_F16 ? reinterpret_cast<const void *>(gaussian_decode_gather_kernel<__half>)
+                                            : reinterpret_cast<const void *>(gaussian_decode_gather_kernel<float>);
+  if (fr > dynamic_lds_limit(kernel)) return 0;
+  if (front) *front = fr;
+  return packed_rows_lds(kernel, fr, T, W);
+}
+
+int lla_gaussian_decode_gather(const uint8_t *payload, const uint64_t *off, int record_prefix, int off_first,
+                               int off_step, int N, const int64_t *index, int B, int C, const float *bias,
+                               const float *exp_scale, const float *scales, size_t ld_scales,
+                               const float *scale_table, float scale_bound, const int32_t *cdf, int T, int W,
+                               const int32_t *cdf_len, const int32_t *offset, void *z_hat, int z_dtype,
+                               size_t ld_out, const int32_t *status_in, int32_t *status, void *stream) {
+  if (z_dtype != LLA_Z_F16 && z_dtype != LLA_Z_F32) return LLA_EINVAL;
+  if (off_first < 0 || off_step < 1) return LLA_EINVAL;
+  if (B == 0) return LLA_OK;
+  if (B < 0 || N < 0 || C <= 0 || T <= 0 || W < 3 || !payload || !off || !index || !bias || !exp_scale || !scales ||
+      ld_scales < (size_t)C || !scale_table || !cdf || !cdf_len || !offset || !z_hat || ld_out < (size_t)C || !status)
+    return LLA_EINVAL;
+  // (52 KiB in front of the rows: a gfx950 has 160; 0 = the head or the front does not fit)
+  const unsigned lds = (unsigned)lla_gaussian_decode_gather_lds_bytes(C, T, W, z_dtype, nullptr);
+  if (lds == 0) return LLA_EINVAL;
+  const int grid = (B + kEncThreads - 1) / kEncThreads;
+  const int skip = record_prefix ? 4 : 0;
+  if (z_dtype == LLA_Z_F16)
+    gaussian_decode_gather_kernel<__half><<<grid, kEncThreads, lds, as_stream(stream)>>>(
+        payload, off, skip, off_first, off_step, N, index, B, C, bias, exp_scale, scales, ld_scales, scale_table,
+        scale_bound, cdf, T, W, cdf_len, offset, reinterpret_cast<__half *>(z_hat), ld_out, status_in, status, lds);
+  else
+    gaussian_decode_gather_kernel<float><<<grid, kEncThreads, lds, as_stream(stream)>>>(
+        payload, off, skip, off_first, off_step, N, index, B, C, bias, exp_scale, scales, ld_scales, scale_table,
+        scale_bound, cdf, T, W, cdf_len, offset, reinterpret_cast<float *>(z_hat), ld_out, status_in, status, lds);
   return check_launch();
 }
 

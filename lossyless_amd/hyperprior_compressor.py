@@ -194,13 +194,20 @@ class HyperpriorClipCompressor(ClipCompressor):
 
     # ------------------------------------------------------------------ datasets
     def open_dataset(self, file, label_file=None, device=None):
-        """Not available for hyperprior containers yet (``NotImplementedError``)."""
-        raise NotImplementedError(
-            "HyperpriorClipCompressor.open_dataset: a hyperprior container holds TWO records per image (z string, side "
-            "string), and a z record can only be decoded with the table rows and means that the hyper-synthesis network "
-            "(z_encoder) derives from its decoded side record; lla_rans_decode_gather decodes one self-contained record per "
-            "row. Random access to such files needs a gather of the side records, the fp32 MLP, then a gathered "
-            "conditional decode: a later change. Use decompress_dataset(is_cpu=False).")
+        """The container ``file`` as a :class:`~lossyless_amd.latents.HyperpriorLatents`: it stays compressed in HBM and
+        serves the rows of any index vector, bit-equal to ``decompress_dataset(file)[indices]``.  GPU only: the object
+        always lives on this compressor's device (it reads the compressor's tables and MLP there; ``device`` only says
+        GPU or CPU); ``device="cpu"``, or a compressor on the CPU, raises ``NotImplementedError`` before the file is
+        touched."""
+        here = torch.device(self.device)
+        want = here if device is None else torch.device(device)
+        if here.type != "cuda" or want.type != "cuda":
+            raise NotImplementedError(
+                "HyperpriorClipCompressor.open_dataset on the CPU: a hyperprior container holds two records per image (z "
+                "string, side string), and a z record can only be decoded with the table rows and means that z_encoder "
+                "derives from its decoded side record; " + _WHY_NO_CPU)
+        from .latents import HyperpriorLatents
+        return HyperpriorLatents(file, self, label_file=label_file)
 
     @torch.no_grad()
     def decompress_dataset(self, file, label_file=None, is_info=True, is_cpu=False, *, batch_size=65536):

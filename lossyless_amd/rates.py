@@ -355,16 +355,22 @@ class MLP(nn.Module):
         X2 = X.reshape(-1, shape[-1])
         if not X2.is_cuda:
             return self.module(X2.float()).reshape(*shape[:-1], -1)
-        L, dev = _lib.lib(), X2.device
-        packs = self._pack(dev)
-        rows = X2.shape[0]
-        half = self.precision == "fp16"
-        at = torch.float16 if half else torch.float32
-        a = torch.zeros((rows, packs[0][5]), dtype=at, device=dev)
+        packs = self._pack(X2.device)
+        at = torch.float16 if self.precision == "fp16" else torch.float32
+        a = torch.zeros((X2.shape[0], packs[0][5]), dtype=at, device=X2.device)
         a[:, :packs[0][3]] = X2.to(at)
+        out_dim = packs[-1][2]
+        return self._layers(a, packs)[:, :out_dim].float().reshape(*shape[:-1], out_dim)
+
+    def _layers(self, a, packs, bufs=None):
+        """The Linear (+ ReLU) layers on a padded input ``a`` [rows, Kpad of the first layer] -> the last layer's padded
+        output [rows, Npad].  ``bufs``: one [rows, Npad] tensor per layer to write into instead of allocating."""
+        L, dev = _lib.lib(), a.device
+        rows = a.shape[0]
+        half = self.precision == "fp16"
         for i, (w, b, n, k, npad, kpad) in enumerate(packs):
             last = i == len(packs) - 1
-            c = torch.empty((rows, npad), dtype=at, device=dev)
+            c = torch.empty((rows, npad), dtype=a.dtype, device=dev) if bufs is None else bufs[i]
             if half:
                 rc = L.lla_gemm_f16_ex(_lib.ptr(a), a.shape[1], _lib.ptr(w), _lib.ptr(b), _lib.ptr(c), npad, None, 0,
                                        rows, npad, kpad, _lib.LLA_EPI_F16 if last else _lib.LLA_EPI_RELU_F16,
@@ -376,8 +382,29 @@ class MLP(nn.Module):
                                     rows, npad, kpad, 0 if last else 1, _lib.stream_ptr(dev))
                 _lib.check(rc, "lla_gemm_f32")
             a = c          # (Npad is a valid Kpad of the next layer; padding columns are 0: zero weights, zero bias)
-        out_dim = packs[-1][2]
-        return a[:, :out_dim].float().reshape(*shape[:-1], out_dim)
+        return a
+
+    def padded_shapes(self, device):
+        """-> (Kpad of the first layer, [Npad of every layer]) of the fp32 device path: what a caller of
+        :meth:`forward_padded` sizes its buffers by."""
+        packs = self._pack(torch.device(device))
+        return packs[0][5], [p[4] for p in packs]
+
+    def forward_padded(self, a, bufs=None):
+        """``forward`` for a caller that already holds the input as the first GEMM wants it: ``a`` is a contiguous fp32
+        device matrix [rows, Kpad] whose columns beyond the input width are zero (``padded_shapes``).  Nothing is copied:
+        returns the last layer's padded output [rows, Npad] (the result is its leading ``out_dim`` columns, row stride
+        Npad), written into ``bufs[-1]`` when ``bufs`` (one [rows, Npad_i] fp32 tensor per layer) is given.  The same GEMM
+        calls as ``forward`` on the same values: the same bits."""
+        if self.precision != "fp32":
+            raise NotImplementedError("forward_padded runs the fp32 MLP only")
+        packs = self._pack(a.device)
+        if a.dtype != torch.float32 or a.dim() != 2 or a.shape[1] != packs[0][5] or not a.is_contiguous():
+            raise ValueError(f"a must be a contiguous fp32 [rows, {packs[0][5]}] matrix")
+        _lib.require_cuda(a, "a")
+        if bufs is not None and [tuple(b.shape) for b in bufs] != [(a.shape[0], p[4]) for p in packs]:
+            raise ValueError("bufs must hold one [rows, Npad] tensor per layer")
+        return self._layers(a, packs, bufs)
 
 
 class HRateHyperprior(HRateEstimator):
