@@ -544,6 +544,27 @@ int lla_gemm_plan(int epi, int amode, int M, int N, int K, int lda, int ldc, int
 int lla_gemm_f32(const float *A, int lda, const float *W, int ldw, const float *bias, float *C, int ldc,
                  int M, int N, int K, int relu, void *stream);
 
+/* One data pass of a linear probe (lossyless_amd/csrc/probe.hip): the sums that the LinearSVC objective -- squared hinge,
+ * one-vs-rest, the third step of the reference's workflow (README.md:74-82: LinearSVC(C=7e-3).fit(Z, Y) on the
+ * decompressed features) -- needs from B rows, for all K classifiers at once, on the fp32 matrix cores.
+ *   z [B][C] (pitch ld_z elements; LLA_Z_F32, or LLA_Z_F16 widened exactly), y[i] a class index: y_ik = +1 iff
+ *   y[i] == k, so a label outside [0, K) is negative for every classifier (two classes: K = 1, label 0 = positive).
+ *   s_ik = z_i . W_k + b_k,  m_ik = max(0, 1 - y_ik s_ik);  W, V, out_W are [K][C] with pitch ld_w.
+ *   V == NULL (gradient):      out_loss[k] = sum_i m_ik^2, out_W[k] = sum_i (-2 y_ik m_ik) z_i, out_b[k] = sum_i (-2 y_ik m_ik)
+ *   V != NULL (Hessian-vector): t_ik = [m_ik > 0] (z_i . V_k + vb_k), out_W[k] = sum_i 2 t_ik z_i, out_b[k] = sum_i 2 t_ik;
+ *                               out_loss is not touched (may be NULL).
+ * The factor C of the objective and its 1/2 |.|^2 terms are the caller's.  accumulate = 1 adds this call's totals to what
+ * the outputs hold (a dataset walked in decode groups).  No floating-point atomics: workgroups leave partial sums in
+ * `workspace` (lla_svm_pass_workspace_bytes(C, K) bytes; 0 for a refused shape) and a second kernel adds them in a fixed
+ * order, the loss in double: the same inputs give the same bits.
+ * C % 8 == 0, 8 <= C <= 1024, K >= 1, ld_z >= C, ld_w >= C, pitches multiples of 4, z 16-byte (fp16: 8-byte) and W / V
+ * 16-byte aligned; anything else is LLA_EINVAL, decided before any device call.  B == 0: LLA_OK (the outputs are zeroed
+ * unless accumulate is set, then nothing is touched). */
+size_t lla_svm_pass_workspace_bytes(int C, int K);
+int lla_svm_pass(const void *z, int z_dtype, int ld_z, const int32_t *y, int B, int C, const float *W, const float *b,
+                 const float *V, const float *vb, int K, int ld_w, float *out_W, float *out_b, double *out_loss,
+                 int accumulate, void *workspace, void *stream);
+
 /* out[n][H][W][ldc] (first cout channels) = relu(conv3x3(in, stride 1, pad 1) + bias) as an IMPLICIT GEMM:
  * `in` is NHWC fp16 [n][H][W][pitch] (first cin channels used; cin % 64 == 0, or cin == 32), weights fp16
  * [cout][K] with K = 9 cin rounded up to a multiple of 64 (zero padded) in the order (kh, kw, c), bias fp32

@@ -1,0 +1,313 @@
+// One data pass of a linear probe on the compressed representations (gfx950): the squared-hinge sums that
+// `LinearSVC(C).fit(Z, Y)` needs -- the third step of the reference's published workflow, after compress_dataset and
+// decompress_dataset (README.md:74-82 of the reference; notebooks/Hub.ipynb:415) -- for all K one-vs-rest
+// classifiers at once, from rows that a decode group of CompressedLatents / HyperpriorLatents has just left in HBM.
+//
+//   s_ik = z_i . W_k + b_k      y_ik = +1 iff y[i] == k      m_ik = max(0, 1 - y_ik s_ik)
+//   gradient mode (V == NULL):   out_loss[k] = sum_i m_ik^2,   out_W[k] = sum_i (-2 y_ik m_ik) z_i,   out_b[k] = sum_i (-2 y_ik m_ik)
+//   Hessian-vector mode:         t_ik = [m_ik > 0] (z_i . V_k + vb_k),   out_W[k] = sum_i 2 t_ik z_i,   out_b[k] = sum_i 2 t_ik
+//
+// Shape of the kernel.  A persistent workgroup (4 waves) owns one tile of 32 classes and walks row tiles of 32 rows:
+//   1. the row tile is staged in LDS once, as fp32 (fp16 rows are widened exactly), pitch C + 4 floats;
+//   2. scores: S[32 classes][32 rows] = W_tile Z_tile^T on v_mfma_f32_32x32x2_f32, the C dimension dealt to the four waves
+//      in groups of 8 and their partial tiles added through LDS in a fixed order;
+//   3. residuals r_ik (-2 y m, or 2 t) in registers, one (row, 4 classes) per thread, written to LDS [row][class];
+//   4. gradient: G[32 classes][C] += R^T Z_tile, a second MFMA whose operands are both in LDS; each wave keeps its
+//      C / 4 columns of the slice in accumulator registers over ALL its row tiles (64 VGPRs at C = 512).
+// z is read from HBM once per class tile; scores and residuals never leave the chip.  At C <= 512 the workgroup needs
+// 78.6 KB of LDS, so two of them share a CU and one's staging runs beside the other's MFMAs.
+//
+// Determinism: no floating-point atomics.  Every workgroup writes its partial sums to the workspace and
+// svm_reduce_kernel adds them in workgroup order (the loss in double); the number of workgroups is a function of
+// (B, K) alone, so two calls on the same inputs give the same bits.
+//
+// Arithmetic: exact fp32 products, fp32 accumulation (the MFMA is an fma chain), as gemm_f32.hip.
+#include "common.h"
+
+#include <hip/hip_fp16.h>
+
+namespace lla {
+namespace {
+
+typedef float f32x4 __attribute__((ext_vector_type(4)));
+typedef float f32x16 __attribute__((ext_vector_type(16)));
+
+constexpr int kRows = 32;          // rows per staged tile
+constexpr int kClasses = 32;       // classes per workgroup
+constexpr int kZPad = 4;           // floats: 16-byte reads of one column group from 32 rows touch 16 distinct slots
+constexpr int kRPitch = kClasses + 1;
+constexpr int kResident = 512;     // workgroups the chip holds at two per CU: the grid is cut to it
+
+__host__ __device__ inline int lds_floats(int C) { return kRows * (C + kZPad) + 2 * kRows * kClasses + kRows * kRPitch; }
+inline int class_tiles(int K) { return (K + kClasses - 1) / kClasses; }
+inline int walkers_max(int K) { const int w = kResident / class_tiles(K); return w < 1 ? 1 : w; }
+
+// HV: Hessian-vector mode.  NT: 32-column tiles of the gradient slice per wave (C <= 128 NT).
+// Workspace: part_W [class tile][walker][32][C], part_b / part_l [class tile][walker][32].
+template <bool HV, int NT>
+__global__ __launch_bounds__(256) void svm_pass_kernel(const void *__restrict__ z, int z_f16, int ld_z,
+                                                       const int32_t *__restrict__ y, int B, int C,
+                                                       const float *__restrict__ W, const float *__restrict__ bias,
+                                                       const float *__restrict__ V, const float *__restrict__ vbias,
+                                                       int K, int ld_w, float *__restrict__ part_W,
+                                                       float *__restrict__ part_b, float *__restrict__ part_l) {
+  extern __shared__ __align__(16) float lds[];
+  constexpr int NSLOT = HV ? 1 : 2;            // score partials kept apart in LDS (HV holds two products: same bytes)
+  const int pitch = C + kZPad;
+  float *Zs = lds;                             // [32 rows][pitch]
+  float *Sp = Zs + kRows * pitch;              // [product][slot][32 classes][32 rows]
+  float *Rs = Sp + 2 * kRows * kClasses;       // [32 rows][33]
+
+  const int tid = threadIdx.x, lane = tid & 63, wid = tid >> 6;
+  const int r32 = lane & 31, hk = lane >> 5;
+  const int ct = blockIdx.y, P = gridDim.x, p = blockIdx.x;
+  const int k0 = ct * kClasses;
+
+  // scores: "A" lane l = W[k0 + (l & 31)][c + (l >> 5)], "B" lane l = Z[row (l & 31)][c + (l >> 5)]  (gemm_f32.hip)
+  int n = k0 + r32;
+  if (n >= K) n = K - 1;                       // clamped classes are computed and masked below
+  const float *wp = W + (size_t)n * ld_w + 4 * hk;
+  const float *vp = HV ? V + (size_t)n * ld_w + 4 * hk : nullptr;
+
+  // residuals: this thread's row of the tile and its four classes
+  const int rr = tid & 31, cl0 = tid >> 5;
+  float bk[4], vbk[4];
+  bool c_ok[4];
+#pragma unroll
+  for (int j = 0; j < 4; ++j) {
+    const int c = k0 + cl0 + 8 * j;
+    c_ok[j] = c < K;
+    bk[j] = c_ok[j] ? bias[c] : 0.f;
+    vbk[j] = (HV && c_ok[j]) ? vbias[c] : 0.f;
+  }
+
+  f32x16 acc[NT];
+#pragma unroll
+  for (int t = 0; t < NT; ++t)
+#pragma unroll
+    for (int r = 0; r < 16; ++r) acc[t][r] = 0.f;
+  float lacc[4] = {0.f, 0.f, 0.f, 0.f}, bacc[4] = {0.f, 0.f, 0.f, 0.f};
+
+  const int ntiles = (B + kRows - 1) / kRows;
+  const int ngroups = C >> 3, c4n = C >> 2;
+  for (int tile = p; tile < ntiles; tile += P) {
+    const int row0 = tile * kRows;
+    // 1. stage the row tile (rows beyond B are zeros: they contribute exactly nothing)
+    for (int i = tid; i < kRows * c4n; i += 256) {
+      const int row = i / c4n, c4 = i - row * c4n;
+      f32x4 v = {0.f, 0.f, 0.f, 0.f};
+      if (row0 + row < B) {
+        const size_t at = (size_t)(row0 + row) * ld_z + 4 * c4;
+        if (z_f16) {
+          const uint2 raw = *reinterpret_cast<const uint2 *>(static_cast<const __half *>(z) + at);
+          const __half2 lo = __builtin_bit_cast(__half2, raw.x), hi = __builtin_bit_cast(__half2, raw.y);
+          v = f32x4{__low2float(lo), __high2float(lo), __low2float(hi), __high2float(hi)};
+        } else {
+          v = *reinterpret_cast<const f32x4 *>(static_cast<const float *>(z) + at);
+        }
+      }
+      *reinterpret_cast<f32x4 *>(Zs + row * pitch + 4 * c4) = v;
+    }
+    __syncthreads();
+
+    // 2. scores of the tile: this wave's column groups
+    f32x16 s, tv;
+#pragma unroll
+    for (int r = 0; r < 16; ++r) s[r] = 0.f, tv[r] = 0.f;
+    for (int g = wid; g < ngroups; g += 4) {
+      const f32x4 a = *reinterpret_cast<const f32x4 *>(Zs + r32 * pitch + 8 * g + 4 * hk);
+      const f32x4 w = *reinterpret_cast<const f32x4 *>(wp + 8 * g);
+#pragma unroll
+      for (int j = 0; j < 4; ++j) s = __builtin_amdgcn_mfma_f32_32x32x2f32(w[j], a[j], s, 0, 0, 0);
+      if (HV) {
+        const f32x4 v = *reinterpret_cast<const f32x4 *>(vp + 8 * g);
+#pragma unroll
+        for (int j = 0; j < 4; ++j) tv = __builtin_amdgcn_mfma_f32_32x32x2f32(v[j], a[j], tv, 0, 0, 0);
+      }
+    }
+    // the four partial tiles, added in wave order: register r of lane l is class 8 (r >> 2) + 4 (l >> 5) + (r & 3), row l & 31
+#pragma unroll
+    for (int stage = 0; stage < 4 / NSLOT; ++stage) {
+      if (wid / NSLOT == stage) {
+        float *dst = Sp + (wid % NSLOT) * (kRows * kClasses);
+#pragma unroll
+        for (int r = 0; r < 16; ++r) {
+          const int at = (8 * (r >> 2) + 4 * hk + (r & 3)) * kRows + r32;
+          if (stage == 0) {
+            dst[at] = s[r];
+            if (HV) dst[kRows * kClasses + at] = tv[r];
+          } else {
+            dst[at] += s[r];
+            if (HV) dst[kRows * kClasses + at] += tv[r];
+          }
+        }
+      }
+      __syncthreads();
+    }
+
+    // 3. residuals
+    {
+      const bool row_ok = row0 + rr < B;
+      const int yy = row_ok ? y[row0 + rr] : -1;
+#pragma unroll
+      for (int j = 0; j < 4; ++j) {
+        const int cl = cl0 + 8 * j;
+        float sc = Sp[cl * kRows + rr];
+        if (NSLOT == 2) sc += Sp[kRows * kClasses + cl * kRows + rr];
+        sc += bk[j];
+        const float ys = (yy == k0 + cl) ? 1.f : -1.f;
+        float m = 1.f - ys * sc;
+        m = (m > 0.f && row_ok && c_ok[j]) ? m : 0.f;
+        float r;
+        if (HV) {
+          const float t = Sp[kRows * kClasses + cl * kRows + rr] + vbk[j];
+          r = m > 0.f ? 2.f * t : 0.f;
+        } else {
+          r = -2.f * ys * m;
+          lacc[j] += m * m;
+        }
+        bacc[j] += r;
+        Rs[rr * kRPitch + cl] = r;
+      }
+    }
+    __syncthreads();
+
+    // 4. gradient slice: "A" lane l = R[row 2 s + (l >> 5)][class l & 31], "B" lane l = Z[row 2 s + (l >> 5)][column]
+#pragma unroll 4
+    for (int s2 = 0; s2 < kRows / 2; ++s2) {
+      const float a = Rs[(2 * s2 + hk) * kRPitch + r32];
+      const float *zrow = Zs + (2 * s2 + hk) * pitch;
+#pragma unroll
+      for (int t = 0; t < NT; ++t) {
+        const int c0 = (wid + 4 * t) * 32;
+        if (c0 < C) {
+          int cc = c0 + r32;
+          if (cc > C - 1) cc = C - 1;          // clamped columns are computed and not stored
+          acc[t] = __builtin_amdgcn_mfma_f32_32x32x2f32(a, zrow[cc], acc[t], 0, 0, 0);
+        }
+      }
+    }
+    __syncthreads();                           // the next tile's staging overwrites Zs, Sp and Rs
+  }
+
+  // this workgroup's partial sums -> workspace (classes beyond K hold exact zeros and are never read)
+  float *pw = part_W + (size_t)(ct * P + p) * kClasses * C;
+#pragma unroll
+  for (int t = 0; t < NT; ++t) {
+    const int cc = (wid + 4 * t) * 32 + r32;
+    if (cc < C) {
+#pragma unroll
+      for (int r = 0; r < 16; ++r) pw[(size_t)(8 * (r >> 2) + 4 * hk + (r & 3)) * C + cc] = acc[t][r];
+    }
+  }
+#pragma unroll
+  for (int j = 0; j < 4; ++j) {
+    Sp[(cl0 + 8 * j) * kRows + rr] = bacc[j];
+    if (!HV) Sp[kRows * kClasses + (cl0 + 8 * j) * kRows + rr] = lacc[j];
+  }
+  __syncthreads();
+  if (tid < (HV ? 32 : 64)) {
+    const float *src = Sp + (tid >> 5) * (kRows * kClasses) + (tid & 31) * kRows;
+    float sum = 0.f;
+    for (int r = 0; r < kRows; ++r) sum += src[r];
+    (tid < 32 ? part_b : part_l)[(size_t)(ct * P + p) * kClasses + (tid & 31)] = sum;
+  }
+}
+
+// sum over walkers 0 .. P-1 of src[p * stride], added in that order; the loads go out eight at a time (a thread that
+// waited for each one before asking for the next spent 0.35 ms on 512 partial sums)
+template <typename T>
+__device__ __forceinline__ T ordered_sum(const float *__restrict__ src, size_t stride, int P) {
+  T sum = 0;
+  int p = 0;
+  for (; p + 8 <= P; p += 8) {
+    float v[8];
+#pragma unroll
+    for (int j = 0; j < 8; ++j) v[j] = src[(size_t)(p + j) * stride];
+#pragma unroll
+    for (int j = 0; j < 8; ++j) sum += (T)v[j];
+  }
+  for (; p < P; ++p) sum += (T)src[(size_t)p * stride];
+  return sum;
+}
+
+// out (+)= the partial sums of walkers 0 .. P-1, in that order.  One thread per (class, column); columns C and C + 1
+// of a class are its out_b and out_loss.
+__global__ __launch_bounds__(64) void svm_reduce_kernel(const float *__restrict__ part_W, const float *__restrict__ part_b,
+                                                        const float *__restrict__ part_l, int P, int C, int K, int ld_w,
+                                                        float *__restrict__ out_W, float *__restrict__ out_b,
+                                                        double *__restrict__ out_loss, int accumulate) {
+  const long long idx = (long long)blockIdx.x * 64 + threadIdx.x;
+  if (idx >= (long long)K * (C + 2)) return;
+  const int k = (int)(idx / (C + 2)), c = (int)(idx - (long long)k * (C + 2));
+  const int ct = k / kClasses, i = k - ct * kClasses;
+  if (c < C) {
+    const float sum = ordered_sum<float>(part_W + ((size_t)ct * P * kClasses + i) * C + c, (size_t)kClasses * C, P);
+    float *o = out_W + (size_t)k * ld_w + c;
+    *o = accumulate ? *o + sum : sum;
+  } else if (c == C) {
+    const float sum = ordered_sum<float>(part_b + (size_t)ct * P * kClasses + i, kClasses, P);
+    out_b[k] = accumulate ? out_b[k] + sum : sum;
+  } else if (out_loss) {
+    const double sum = ordered_sum<double>(part_l + (size_t)ct * P * kClasses + i, kClasses, P);
+    out_loss[k] = accumulate ? out_loss[k] + sum : sum;
+  }
+}
+
+template <bool HV>
+const void *pass_kernel(int C) {
+  if (C <= 128) return reinterpret_cast<const void *>(&svm_pass_kernel<HV, 1>);
+  if (C <= 256) return reinterpret_cast<const void *>(&svm_pass_kernel<HV, 2>);
+  if (C <= 512) return reinterpret_cast<const void *>(&svm_pass_kernel<HV, 4>);
+  return reinterpret_cast<const void *>(&svm_pass_kernel<HV, 8>);
+}
+
+bool shape_ok(int C, int K) {
+  return C >= 8 && C <= 1024 && (C & 7) == 0 && K >= 1 && class_tiles(K) <= 65535;
+}
+
+}  // namespace
+}  // namespace lla
+
+using namespace lla;
+
+extern "C" size_t lla_svm_pass_workspace_bytes(int C, int K) {
+  if (!shape_ok(C, K)) return 0;
+  return (size_t)class_tiles(K) * walkers_max(K) * kClasses * (C + 2) * sizeof(float);
+}
+
+extern "C" int lla_svm_pass(const void *z, int z_dtype, int ld_z, const int32_t *y, int B, int C, const float *W,
+                            const float *b, const float *V, const float *vb, int K, int ld_w, float *out_W, float *out_b,
+                            double *out_loss, int accumulate, void *workspace, void *stream) {
+  if (!shape_ok(C, K) || B < 0 || ld_z < C || ld_w < C || (ld_z & 3) || (ld_w & 3) ||
+      (z_dtype != LLA_Z_F32 && z_dtype != LLA_Z_F16))
+    return LLA_EINVAL;
+  if (!W || !b || !out_W || !out_b || !workspace || (V && !vb) || (!V && !out_loss) || (B > 0 && (!z || !y)))
+    return LLA_EINVAL;
+  const uintptr_t z_align = z_dtype == LLA_Z_F32 ? 15 : 7;
+  if (((uintptr_t)z & z_align) || ((uintptr_t)W & 15) || ((uintptr_t)V & 15) || ((uintptr_t)workspace & 3))
+    return LLA_EINVAL;
+  if (B == 0 && accumulate) return LLA_OK;
+
+  const int nct = class_tiles(K);
+  const int ntiles = (B + kRows - 1) / kRows;
+  const int P = ntiles < walkers_max(K) ? ntiles : walkers_max(K);
+  float *part_W = static_cast<float *>(workspace);
+  float *part_b = part_W + (size_t)nct * walkers_max(K) * kClasses * C;
+  float *part_l = part_b + (size_t)nct * walkers_max(K) * kClasses;
+  hipStream_t st = as_stream(stream);
+  if (P > 0) {
+    const void *kernel = V ? pass_kernel<true>(C) : pass_kernel<false>(C);
+    const size_t lds_bytes = (size_t)lds_floats(C) * sizeof(float);
+    if (lds_bytes > dynamic_lds_limit(kernel)) return LLA_ECAP;
+    const int z_f16 = z_dtype == LLA_Z_F16;
+    void *args[] = {(void *)&z, (void *)&z_f16, (void *)&ld_z, (void *)&y, (void *)&B, (void *)&C, (void *)&W, (void *)&b,
+                    (void *)&V, (void *)&vb, (void *)&K, (void *)&ld_w, (void *)&part_W, (void *)&part_b, (void *)&part_l};
+    hipError_t e = hipLaunchKernel(kernel, dim3(P, nct), dim3(256), args, lds_bytes, st);
+    if (e != hipSuccess) return hip_fail(e);
+  }
+  const long long n_out = (long long)K * (C + 2);
+  svm_reduce_kernel<<<(unsigned)((n_out + 63) / 64), 64, 0, st>>>(part_W, part_b, part_l, P, C, K, ld_w, out_W, out_b,
+                                                                     V ? nullptr : out_loss, accumulate);
+  return check_launch();
+}

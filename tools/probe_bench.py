@@ -1,0 +1,173 @@
+"""The linear probe's data pass, measured (MI355X; writes its table to stdout and, with --out, to a file).
+
+N records stay resident on the device, as in tools/latents_bench.py.  For K = 10 and K = 1000 classes at C = 512:
+
+(a)  one gradient pass of ``lla_svm_pass`` over the N rows already decoded (fp32, resident),
+(c)  the same quantities from the parts the library offered before: ``lla_gemm_f32`` for the scores (K padded to a
+     multiple of 8), torch elementwise ops for the residuals and the loss, ``R.T @ Z`` and ``R.sum(0)`` in torch,
+(a') a whole streamed pass over a ``CompressedLatents`` -- ``take`` of a decode group into one reused buffer, then
+     ``lla_svm_pass(accumulate=1)`` -- against the ``take`` calls alone.
+
+Every arm is warmed up, then timed with device events; the arms are interleaved and the round is repeated ``--reps``
+times.  (a) is checked against (c) before anything is timed.  Bar: the median of (a) may not exceed the median of (c)
+by more than the spread of (c)'s own runs.
+
+Reference point, reported and not gated: wall time of ``LinearProbe.fit`` on an STL10-shaped problem (5000 x 512,
+K = 10) next to scikit-learn's ``LinearSVC(C=7e-3).fit`` on the same rows on this host, when scikit-learn is installed.
+
+usage (GPU box): python tools/probe_bench.py [--records 131072] [--reps 3] [--out profiles/linear_probe.txt]
+"""
+import argparse
+import os
+import sys
+import tempfile
+import time
+
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+
+import torch  # noqa: E402
+
+import hubconf  # noqa: E402
+from latents_bench import interleaved, med  # noqa: E402
+from lossyless_amd import LinearProbe, _lib  # noqa: E402
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--records", type=int, default=131072)
+    ap.add_argument("--reps", type=int, default=3)
+    ap.add_argument("--inner", type=int, default=0, help="calls per timed window (0: 40 at K = 10, 8 at K = 1000)")
+    ap.add_argument("--out", default=None)
+    args = ap.parse_args()
+    if not torch.cuda.is_available():
+        sys.exit("probe_bench.py measures on an MI355X: no GPU here, nothing measured")
+    lines = []
+
+    def say(s=""):
+        print(s, flush=True)
+        lines.append(s)
+
+    dev = torch.device("cuda", torch.cuda.current_device())
+    comp, _ = hubconf.clip_compressor_b005(device="cuda", clip_weights="synthetic")
+    eb, t = comp.entropy_bottleneck, comp._tables()
+    L, N, C = _lib.lib(), args.records, comp.z_dim
+    g = torch.Generator().manual_seed(0)
+    z = (torch.randn(N, C, generator=g) * 0.5).to(dev)
+    payload, offsets, _ = eb.encode_device(z, t, record_prefix=True)
+    torch.cuda.synchronize(dev)
+    total = int(offsets[-1])
+    with tempfile.TemporaryDirectory() as d:      # the container file CompressedLatents opens: be32(N) + the body
+        f = os.path.join(d, "Z.bin")
+        with open(f, "wb") as fh:
+            fh.write(N.to_bytes(4, "big"))
+            fh.write(payload[:total].cpu().numpy().tobytes())
+        ds = comp.open_dataset(f)
+    del payload, offsets, z
+    Z = ds.all()
+    say(f"device: {torch.cuda.get_device_name(dev)}   N = {N} records resident, {ds.nbytes / 2**20:.1f} MiB compressed against "
+        f"{N * C * 4 / 2**20:.0f} MiB of fp32 rows; C = {C}")
+    st = _lib.stream_ptr(dev)
+    group = 65536
+    buf = torch.empty((min(group, N), C), dtype=torch.float32, device=dev)
+    idxs = [(g0, torch.arange(g0, min(g0 + group, N), device=dev)) for g0 in range(0, N, group)]
+
+    for K in (10, 1000):
+        inner = args.inner or (40 if K <= 32 else 8)
+        y = torch.randint(0, K, (N,), generator=g).to(torch.int32).to(dev)
+        W = (torch.randn(K, C, generator=g) * 0.03).to(dev)
+        b = (torch.randn(K, generator=g) * 0.1).to(dev)
+        ws = torch.empty(int(L.lla_svm_pass_workspace_bytes(C, K)), dtype=torch.uint8, device=dev)
+        oW, ob = torch.empty((K, C), device=dev), torch.empty(K, device=dev)
+        ol = torch.empty(K, dtype=torch.float64, device=dev)
+
+        def fused(rows=Z, labels=y, acc=0):
+            rc = L.lla_svm_pass(_lib.ptr(rows), _lib.LLA_Z_F32, C, _lib.ptr(labels), rows.shape[0], C, _lib.ptr(W), _lib.ptr(b),
+                                None, None, K, C, _lib.ptr(oW), _lib.ptr(ob), _lib.ptr(ol), acc, _lib.ptr(ws), st)
+            _lib.check(rc, "lla_svm_pass")
+
+        npad = -(-K // 8) * 8
+        Wp, bp = torch.zeros((npad, C), device=dev), torch.zeros(npad, device=dev)
+        Wp[:K], bp[:K] = W, b
+        S = torch.empty((N, npad), device=dev)
+        cls = torch.arange(npad, device=dev, dtype=torch.int32)[None, :]
+        parts = {}
+
+        def from_parts():
+            rc = L.lla_gemm_f32(_lib.ptr(Z), C, _lib.ptr(Wp), C, _lib.ptr(bp), _lib.ptr(S), npad, N, npad, C, 0, st)
+            _lib.check(rc, "lla_gemm_f32")
+            ys = torch.where(y[:, None] == cls, 1.0, -1.0)
+            m = (1.0 - ys * S).clamp_min_(0.0)
+            m[:, K:] = 0.0
+            R = -2.0 * ys * m
+            parts["loss"], parts["W"], parts["b"] = (m * m).sum(0, dtype=torch.float64), R.T @ Z, R.sum(0)
+
+        def take_only():
+            for _, idx in idxs:
+                ds.take(idx, out=buf[:idx.numel()], check=False)
+
+        def streamed():
+            oW.zero_(), ob.zero_(), ol.zero_()
+            for g0, idx in idxs:
+                rows = ds.take(idx, out=buf[:idx.numel()], check=False)
+                fused(rows, y[g0:g0 + idx.numel()], 1)
+
+        # same sums from both paths, before anything is timed (fp32 in different orders: relative to the absolute sums)
+        fused(), from_parts()
+        torch.cuda.synchronize(dev)
+        scale = float(parts["W"].abs().max())
+        err = float((oW - parts["W"][:K]).abs().max()) / scale
+        lerr = float(((ol - parts["loss"][:K]).abs() / parts["loss"][:K]).max())
+        assert err < 1e-4 and lerr < 1e-5, f"arms disagree: {err:.2e} {lerr:.2e}"
+        first = oW.clone()
+        streamed()
+        torch.cuda.synchronize(dev)
+        assert float((oW - first).abs().max()) / scale < 1e-4, "the streamed pass disagrees"
+
+        arms = {"(a) lla_svm_pass, rows resident": fused, "(c) gemm_f32 + torch + R.T @ Z": from_parts,
+                "(a') streamed: take + lla_svm_pass": streamed, "     take alone": take_only}
+        times = interleaved(arms, inner, args.reps, dev)
+        say()
+        say(f"K = {K}: ms per pass over {N} rows, device events over {inner} back-to-back calls, {args.reps} interleaved runs"
+            f"   (max |(a) - (c)| / max |(c)| = {err:.1e})")
+        for k, ts in times.items():
+            runs = "  ".join(f"{x:9.4f}" for x in ts)
+            say(f"    {k:38s} {runs}   median {med(ts):9.4f} ms")
+        a, c = times["(a) lla_svm_pass, rows resident"], times["(c) gemm_f32 + torch + R.T @ Z"]
+        flop = 4.0 * N * C * (-(-K // 32) * 32)
+        say(f"    (a): {N * C * 4 * -(-K // 32) / med(a) / 1e9:.2f} TB/s of z read ({-(-K // 32)} class tile(s)), "
+            f"{flop / med(a) / 1e9:.1f} TFLOP/s on the padded tiles")
+        ok = med(a) <= med(c) + (max(c) - min(c))
+        say(f"    (a) / (c) medians = {med(a) / med(c):.3f};  spread of (c) = {max(c) - min(c):.4f} ms;  "
+            f"(a) - (c) = {med(a) - med(c):+.4f} ms   -> bar {'MET' if ok else 'MISSED'}")
+
+    # reference point: an STL10-shaped fit
+    n, k = 5000, 10
+    labels = torch.arange(n) % k
+    mu = torch.randn(k, C, generator=g) * 0.1
+    X = (mu[labels] + torch.randn(n, C, generator=g) * 0.5)
+    Xd = X.to(dev)
+    LinearProbe().fit(Xd[:512], labels[:512])            # (code objects loaded)
+    torch.cuda.synchronize(dev)
+    t0 = time.perf_counter()
+    p = LinearProbe().fit(Xd, labels)
+    torch.cuda.synchronize(dev)
+    fit_s = time.perf_counter() - t0
+    say()
+    say(f"STL10-shaped fit ({n} x {C}, K = {k}): LinearProbe.fit {fit_s:.3f} s wall, {p.n_passes_} passes, converged {p.converged_}, "
+        f"train accuracy {p.score(Xd, labels):.4f}")
+    try:
+        from sklearn.svm import LinearSVC
+        t0 = time.perf_counter()
+        clf = LinearSVC(C=7e-3).fit(X.numpy(), labels.numpy())
+        say(f"    scikit-learn LinearSVC(C=7e-3).fit on this host: {time.perf_counter() - t0:.3f} s wall, train accuracy "
+            f"{clf.score(X.numpy(), labels.numpy()):.4f}   (reported, not gated)")
+    except ImportError:
+        say("    scikit-learn is not installed here: no host reference")
+    if args.out:
+        with open(args.out, "w") as fh:
+            fh.write("\n".join(lines) + "\n")
+
+
+if __name__ == "__main__":
+    main()

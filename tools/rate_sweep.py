@@ -64,6 +64,9 @@ def main():
     ap.add_argument("--workers", type=int, default=16, help="DataLoader workers of the -shaped modes")
     ap.add_argument("--check", type=int, default=4096,
                     help="-shaped modes: samples whose decoded rows are compared with compressor(X)")
+    ap.add_argument("--device-probe", action="store_true",
+                    help="also fit lossyless_amd.LinearProbe on the device from the container kept compressed "
+                         "(adds linear_probe_accuracy and linear_probe_fit_s)")
     args = ap.parse_args()
 
     weights = os.environ.get("LOSSYLESS_CLIP_WEIGHTS", "synthetic")
@@ -112,6 +115,7 @@ def main():
             ref = _represent(comp, train, idx, args.batch)
             assert np.array_equal(Z[idx], ref)
             acc = "skipped: labels / test split not given"
+            probe = {}
             if Y is not None and test is not None and Yt is not None:
                 from sklearn.svm import LinearSVC
                 ft = os.path.join(d, "Zt.bin")
@@ -119,13 +123,20 @@ def main():
                 Zt = comp.decompress_dataset(ft, is_info=False)
                 clf = LinearSVC(C=7e-3).fit(Z, Y)          # README.md:75
                 acc = float(clf.score(Zt, Yt))
+                if args.device_probe:
+                    from lossyless_amd import LinearProbe
+                    t0 = time.perf_counter()
+                    fitted = LinearProbe(C=7e-3).fit(comp.open_dataset(f), np.asarray(Y))   # the same objective, on the device
+                    torch.cuda.synchronize()
+                    probe = dict(linear_probe_fit_s=round(time.perf_counter() - t0, 3),
+                                 linear_probe_accuracy=float(fitted.score(comp.open_dataset(ft), np.asarray(Yt))))
         print(json.dumps(dict(rate_point=name, data=data, clip_weights=weights, images=n,
                               call=("Dataset(transform=RawRGB) -> compress_dataset(dataset, file, label_file, "
                                     f"dict(batch_size={args.batch}, num_workers={args.workers}))") if shaped
                               else "tensor fast path",
                               bits_per_img=round(bits, 2), encode_img_per_sec=round(n / enc, 1),
                               decode_img_per_sec=round(n / dec, 1), round_trip="exact",
-                              round_trip_samples=int(len(idx)), linear_svc_accuracy=acc)), flush=True)
+                              round_trip_samples=int(len(idx)), linear_svc_accuracy=acc, **probe)), flush=True)
 
 
 if __name__ == "__main__":
