@@ -565,6 +565,23 @@ int lla_svm_pass(const void *z, int z_dtype, int ld_z, const int32_t *y, int B, 
                  const float *V, const float *vb, int K, int ld_w, float *out_W, float *out_b, double *out_loss,
                  int accumulate, void *workspace, void *stream);
 
+/* The same pass over J independent problems in the place of the K classes: every (candidate, fold, class) of a
+ * cross-validated search over C and class_weight (the reference's utils/Z_linear_eval.py:62-93) in the passes of one fit.
+ * Problem j has a positive class, a held-out fold and one weight per sign:
+ *   y_ij = +1 iff y[i] == col_class[j];  c_ij = 0 if fold != NULL and fold[i] == col_held[j], else col_cpos[j] where
+ *   y_ij = +1 and col_cneg[j] where y_ij = -1  (liblinear's class weights: C w[k] for the rows of class k, C for the rest).
+ *   V == NULL:  out_loss[j] = sum_i c_ij m_ij^2, out_W[j] = sum_i c_ij (-2 y_ij m_ij) z_i, out_b[j] = sum_i c_ij (-2 y_ij m_ij)
+ *   V != NULL:  out_W[j] = sum_i 2 c_ij t_ij z_i, out_b[j] = sum_i 2 c_ij t_ij.
+ * W, V, out_W are [J][C], the col_* arrays [J], fold [B] (NULL: no row is held out); all on the device.  The weight is one
+ * more fp32 multiply of the residual and of m^2; grid, workspace layout and order of the sums are those of lla_svm_pass
+ * for K = J, so fold == NULL, col_class = 0 .. J-1 and unit weights return its bits.  Same shape rules and refusals;
+ * a NULL col_* pointer is LLA_EINVAL.  lla_svm_grid_pass_workspace_bytes(C, J) == lla_svm_pass_workspace_bytes(C, J). */
+size_t lla_svm_grid_pass_workspace_bytes(int C, int J);
+int lla_svm_grid_pass(const void *z, int z_dtype, int ld_z, const int32_t *y, const int32_t *fold, int B, int C,
+                      const float *W, const float *b, const float *V, const float *vb, int J, int ld_w,
+                      const int32_t *col_class, const int32_t *col_held, const float *col_cpos, const float *col_cneg,
+                      float *out_W, float *out_b, double *out_loss, int accumulate, void *workspace, void *stream);
+
 /* out[n][H][W][ldc] (first cout channels) = relu(conv3x3(in, stride 1, pad 1) + bias) as an IMPLICIT GEMM:
  * `in` is NHWC fp16 [n][H][W][pitch] (first cin channels used; cin % 64 == 0, or cin == 32), weights fp16
  * [cout][K] with K = 9 cin rounded up to a multiple of 64 (zero padded) in the order (kh, kw, c), bias fp32

@@ -22,6 +22,14 @@
 // (B, K) alone, so two calls on the same inputs give the same bits.
 //
 // Arithmetic: exact fp32 products, fp32 accumulation (the MFMA is an fma chain), as gemm_f32.hip.
+//
+// The grid pass (lla_svm_grid_pass; GRID below) is the same walk over J independent problems in the place of the K
+// classes: problem j has its own positive class, its own held-out fold and one weight per sign,
+//   y_ij = +1 iff y[i] == col_class[j]      c_ij = 0 if fold[i] == col_held[j], else col_cpos[j] / col_cneg[j] by the sign
+//   out_loss[j] = sum_i c_ij m_ij^2,   residual c_ij (-2 y_ij m_ij)   or   c_ij 2 t_ij
+// -- every (candidate, fold, class) of a cross-validated search over C and class_weight in the passes of one fit.  The
+// four numbers of a column live in registers next to its intercept; the weight is one multiply of the residual and of
+// the loss term in step 3, so unit weights and no fold give the bits of lla_svm_pass.
 #include "common.h"
 
 #include <hip/hip_fp16.h>
@@ -42,15 +50,26 @@ __host__ __device__ inline int lds_floats(int C) { return kRows * (C + kZPad) + 
 inline int class_tiles(int K) { return (K + kClasses - 1) / kClasses; }
 inline int walkers_max(int K) { const int w = kResident / class_tiles(K); return w < 1 ? 1 : w; }
 
-// HV: Hessian-vector mode.  NT: 32-column tiles of the gradient slice per wave (C <= 128 NT).
+// The columns of a grid pass: what makes problem j of lla_svm_grid_pass differ from class j of lla_svm_pass.
+struct GridCols {
+  const int32_t *fold;       // [B] or NULL: no row is held out
+  const int32_t *col_class;  // [J]
+  const int32_t *col_held;   // [J]
+  const float *col_cpos;     // [J]
+  const float *col_cneg;     // [J]
+};
+
+// HV: Hessian-vector mode.  NT: 32-column tiles of the gradient slice per wave (C <= 128 NT).  GRID: the columns are
+// the problems of `cols` (K is their number J); otherwise column k is class k, nothing is held out and every weight is 1.
 // Workspace: part_W [class tile][walker][32][C], part_b / part_l [class tile][walker][32].
-template <bool HV, int NT>
+template <bool HV, int NT, bool GRID>
 __global__ __launch_bounds__(256) void svm_pass_kernel(const void *__restrict__ z, int z_f16, int ld_z,
                                                        const int32_t *__restrict__ y, int B, int C,
                                                        const float *__restrict__ W, const float *__restrict__ bias,
                                                        const float *__restrict__ V, const float *__restrict__ vbias,
                                                        int K, int ld_w, float *__restrict__ part_W,
-                                                       float *__restrict__ part_b, float *__restrict__ part_l) {
+                                                       float *__restrict__ part_b, float *__restrict__ part_l,
+                                                       GridCols cols) {
   extern __shared__ __align__(16) float lds[];
   constexpr int NSLOT = HV ? 1 : 2;            // score partials kept apart in LDS (HV holds two products: same bytes)
   const int pitch = C + kZPad;
@@ -73,13 +92,20 @@ __global__ __launch_bounds__(256) void svm_pass_kernel(const void *__restrict__ 
   const int rr = tid & 31, cl0 = tid >> 5;
   float bk[4], vbk[4];
   bool c_ok[4];
+  int ccls[4], cheld[4];                       // GRID: the column's positive class and held-out fold,
+  float cpos[4], cneg[4];                      //       its weight for positive and for negative rows
 #pragma unroll
   for (int j = 0; j < 4; ++j) {
     const int c = k0 + cl0 + 8 * j;
     c_ok[j] = c < K;
     bk[j] = c_ok[j] ? bias[c] : 0.f;
     vbk[j] = (HV && c_ok[j]) ? vbias[c] : 0.f;
+    ccls[j] = (GRID && c_ok[j]) ? cols.col_class[c] : c;
+    cheld[j] = (GRID && c_ok[j]) ? cols.col_held[c] : 0;
+    cpos[j] = (GRID && c_ok[j]) ? cols.col_cpos[c] : 0.f;
+    cneg[j] = (GRID && c_ok[j]) ? cols.col_cneg[c] : 0.f;
   }
+  const bool folds = GRID && cols.fold != nullptr;
 
   f32x16 acc[NT];
 #pragma unroll
@@ -149,22 +175,26 @@ __global__ __launch_bounds__(256) void svm_pass_kernel(const void *__restrict__ 
     {
       const bool row_ok = row0 + rr < B;
       const int yy = row_ok ? y[row0 + rr] : -1;
+      const int ff = (folds && row_ok) ? cols.fold[row0 + rr] : 0;
 #pragma unroll
       for (int j = 0; j < 4; ++j) {
         const int cl = cl0 + 8 * j;
         float sc = Sp[cl * kRows + rr];
         if (NSLOT == 2) sc += Sp[kRows * kClasses + cl * kRows + rr];
         sc += bk[j];
-        const float ys = (yy == k0 + cl) ? 1.f : -1.f;
+        const float ys = (yy == ccls[j]) ? 1.f : -1.f;
         float m = 1.f - ys * sc;
         m = (m > 0.f && row_ok && c_ok[j]) ? m : 0.f;
+        const float cw = (folds && ff == cheld[j]) ? 0.f : (ys > 0.f ? cpos[j] : cneg[j]);      // GRID only
         float r;
         if (HV) {
           const float t = Sp[kRows * kClasses + cl * kRows + rr] + vbk[j];
           r = m > 0.f ? 2.f * t : 0.f;
+          if (GRID) r *= cw;
         } else {
           r = -2.f * ys * m;
-          lacc[j] += m * m;
+          if (GRID) r *= cw;
+          lacc[j] += GRID ? m * m * cw : m * m;
         }
         bacc[j] += r;
         Rs[rr * kRPitch + cl] = r;
@@ -254,12 +284,12 @@ __global__ __launch_bounds__(64) void svm_reduce_kernel(const float *__restrict_
   }
 }
 
-template <bool HV>
+template <bool HV, bool GRID>
 const void *pass_kernel(int C) {
-  if (C <= 128) return reinterpret_cast<const void *>(&svm_pass_kernel<HV, 1>);
-  if (C <= 256) return reinterpret_cast<const void *>(&svm_pass_kernel<HV, 2>);
-  if (C <= 512) return reinterpret_cast<const void *>(&svm_pass_kernel<HV, 4>);
-  return reinterpret_cast<const void *>(&svm_pass_kernel<HV, 8>);
+  if (C <= 128) return reinterpret_cast<const void *>(&svm_pass_kernel<HV, 1, GRID>);
+  if (C <= 256) return reinterpret_cast<const void *>(&svm_pass_kernel<HV, 2, GRID>);
+  if (C <= 512) return reinterpret_cast<const void *>(&svm_pass_kernel<HV, 4, GRID>);
+  return reinterpret_cast<const void *>(&svm_pass_kernel<HV, 8, GRID>);
 }
 
 bool shape_ok(int C, int K) {
@@ -276,14 +306,18 @@ extern "C" size_t lla_svm_pass_workspace_bytes(int C, int K) {
   return (size_t)class_tiles(K) * walkers_max(K) * kClasses * (C + 2) * sizeof(float);
 }
 
-extern "C" int lla_svm_pass(const void *z, int z_dtype, int ld_z, const int32_t *y, int B, int C, const float *W,
-                            const float *b, const float *V, const float *vb, int K, int ld_w, float *out_W, float *out_b,
-                            double *out_loss, int accumulate, void *workspace, void *stream) {
+namespace {
+
+// Both entry points: the argument checks, the persistent pass and the ordered reduction.  `cols` == nullptr: lla_svm_pass.
+int svm_pass_launch(const void *z, int z_dtype, int ld_z, const int32_t *y, int B, int C, const float *W, const float *b,
+                    const float *V, const float *vb, int K, int ld_w, const GridCols *cols, float *out_W, float *out_b,
+                    double *out_loss, int accumulate, void *workspace, void *stream) {
   if (!shape_ok(C, K) || B < 0 || ld_z < C || ld_w < C || (ld_z & 3) || (ld_w & 3) ||
       (z_dtype != LLA_Z_F32 && z_dtype != LLA_Z_F16))
     return LLA_EINVAL;
   if (!W || !b || !out_W || !out_b || !workspace || (V && !vb) || (!V && !out_loss) || (B > 0 && (!z || !y)))
     return LLA_EINVAL;
+  if (cols && (!cols->col_class || !cols->col_held || !cols->col_cpos || !cols->col_cneg)) return LLA_EINVAL;
   const uintptr_t z_align = z_dtype == LLA_Z_F32 ? 15 : 7;
   if (((uintptr_t)z & z_align) || ((uintptr_t)W & 15) || ((uintptr_t)V & 15) || ((uintptr_t)workspace & 3))
     return LLA_EINVAL;
@@ -297,12 +331,15 @@ extern "C" int lla_svm_pass(const void *z, int z_dtype, int ld_z, const int32_t 
   float *part_l = part_b + (size_t)nct * walkers_max(K) * kClasses;
   hipStream_t st = as_stream(stream);
   if (P > 0) {
-    const void *kernel = V ? pass_kernel<true>(C) : pass_kernel<false>(C);
+    const void *kernel = cols ? (V ? pass_kernel<true, true>(C) : pass_kernel<false, true>(C))
+                              : (V ? pass_kernel<true, false>(C) : pass_kernel<false, false>(C));
     const size_t lds_bytes = (size_t)lds_floats(C) * sizeof(float);
     if (lds_bytes > dynamic_lds_limit(kernel)) return LLA_ECAP;
     const int z_f16 = z_dtype == LLA_Z_F16;
+    GridCols gc = cols ? *cols : GridCols{nullptr, nullptr, nullptr, nullptr, nullptr};
     void *args[] = {(void *)&z, (void *)&z_f16, (void *)&ld_z, (void *)&y, (void *)&B, (void *)&C, (void *)&W, (void *)&b,
-                    (void *)&V, (void *)&vb, (void *)&K, (void *)&ld_w, (void *)&part_W, (void *)&part_b, (void *)&part_l};
+                    (void *)&V, (void *)&vb, (void *)&K, (void *)&ld_w, (void *)&part_W, (void *)&part_b, (void *)&part_l,
+                    (void *)&gc};
     hipError_t e = hipLaunchKernel(kernel, dim3(P, nct), dim3(256), args, lds_bytes, st);
     if (e != hipSuccess) return hip_fail(e);
   }
@@ -310,4 +347,26 @@ extern "C" int lla_svm_pass(const void *z, int z_dtype, int ld_z, const int32_t 
   svm_reduce_kernel<<<(unsigned)((n_out + 63) / 64), 64, 0, st>>>(part_W, part_b, part_l, P, C, K, ld_w, out_W, out_b,
                                                                      V ? nullptr : out_loss, accumulate);
   return check_launch();
+}
+
+}  // namespace
+
+extern "C" int lla_svm_pass(const void *z, int z_dtype, int ld_z, const int32_t *y, int B, int C, const float *W,
+                            const float *b, const float *V, const float *vb, int K, int ld_w, float *out_W, float *out_b,
+                            double *out_loss, int accumulate, void *workspace, void *stream) {
+  return svm_pass_launch(z, z_dtype, ld_z, y, B, C, W, b, V, vb, K, ld_w, nullptr, out_W, out_b, out_loss, accumulate,
+                         workspace, stream);
+}
+
+// The grid is the one lla_svm_pass launches for K = J: a function of (B, J) alone.
+extern "C" size_t lla_svm_grid_pass_workspace_bytes(int C, int J) { return lla_svm_pass_workspace_bytes(C, J); }
+
+extern "C" int lla_svm_grid_pass(const void *z, int z_dtype, int ld_z, const int32_t *y, const int32_t *fold, int B, int C,
+                                 const float *W, const float *b, const float *V, const float *vb, int J, int ld_w,
+                                 const int32_t *col_class, const int32_t *col_held, const float *col_cpos,
+                                 const float *col_cneg, float *out_W, float *out_b, double *out_loss, int accumulate,
+                                 void *workspace, void *stream) {
+  const GridCols cols = {fold, col_class, col_held, col_cpos, col_cneg};
+  return svm_pass_launch(z, z_dtype, ld_z, y, B, C, W, b, V, vb, J, ld_w, &cols, out_W, out_b, out_loss, accumulate,
+                         workspace, stream);
 }

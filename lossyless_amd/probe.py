@@ -9,7 +9,7 @@ intercept carried as one more feature of value 1 and regularised with the weight
 
 for all classes at once, from a :class:`~lossyless_amd.latents.CompressedLatents` / ``HyperpriorLatents`` that stays
 compressed in HBM: a pass walks the rows in file order, one decode group at a time (``take`` into one reused buffer), and
-hands each group to ``lla_svm_pass`` (csrc/probe.hip), which adds that group's share of the loss, the gradient or a
+hands each group to ``lla_svm_grid_pass`` (csrc/probe.hip), which adds that group's share of the loss, the gradient or a
 generalised-Hessian-vector product to the running totals.  No N x K state lives between passes.
 
 The solver is a truncated Newton-CG (Jacobi-preconditioned by the data's column scales), batched over the classes (every class is its own strongly convex problem; all of
@@ -17,6 +17,11 @@ them advance in the same pass), with a per-class backtracking line search.  It i
 
 CPU data (or latents opened with ``device="cpu"``) run the same solver over a float64 torch evaluation of the same two
 quantities: no GPU needed, and the oracle of the GPU tests.
+
+What a pass walks is a set of J *problems* (:class:`_Problems`), not K classes: problem j separates one class from the
+rest on the rows outside one held-out fold, with liblinear's class weights (``C w[k]`` for the rows of class k, ``C`` for
+the others).  A plain fit is K problems with nothing held out; :class:`LinearProbeCV` lays every (candidate, fold, class)
+of a search over ``C`` and ``class_weight`` side by side and solves them in the same passes (``lla_svm_grid_pass``).
 """
 import warnings
 
@@ -95,17 +100,89 @@ class _Rows:
             self.latents.release()
 
 
+class _Problems:
+    """J independent problems that share the rows of a walk.  Problem j: positive class ``cls[j]``, the rows of fold
+    ``held[j]`` left out (``_NO_FOLD``: none), weight ``scale[j] * wpos[j]`` on its positive rows and ``scale[j] * wneg[j]``
+    on the others; ``group[j]`` says which problems form one classifier (they share a stopping rule).  ``scale`` is the C
+    of the objective and is applied to a pass's totals; ``wpos`` / ``wneg`` are the class weights and go into the pass, so
+    that without class weights a pass multiplies by 1.0 and adds what ``lla_svm_pass`` adds."""
+
+    def __init__(self, cls, held, wpos, wneg, scale, group):
+        self.cls, self.held = torch.as_tensor(cls, dtype=torch.int32), torch.as_tensor(held, dtype=torch.int32)
+        self.wpos, self.wneg = torch.as_tensor(wpos, dtype=torch.float64), torch.as_tensor(wneg, dtype=torch.float64)
+        self.scale, self.group = torch.as_tensor(scale, dtype=torch.float64), torch.as_tensor(group, dtype=torch.int64)
+        self.J = int(self.cls.numel())
+        self.n_groups = int(self.group.max()) + 1
+
+    def on(self, sums, device):
+        """What the solver reads from a sums object: J, the groups, the totals' scale and the largest weight per problem."""
+        sums.J, sums.n_groups = self.J, self.n_groups
+        sums.group = self.group.to(device)
+        sums.scale = self.scale.to(device)
+        sums.cmax = (self.scale * torch.maximum(self.wpos, self.wneg)).to(device)
+
+
+_NO_FOLD = -2            # a held-out fold id that no row carries (fold ids are >= -1)
+
+
+def _class_weights(class_weight, classes, counts):
+    """liblinear's w[k] for the sorted labels ``classes`` (numpy) with ``counts`` rows each (the rows actually fitted)."""
+    K = len(classes)
+    if class_weight is None:
+        return torch.ones(K, dtype=torch.float64)
+    if isinstance(class_weight, str):
+        if class_weight != "balanced":
+            raise ValueError(f"class_weight must be None, 'balanced' or a dict, got {class_weight!r}")
+        return counts.sum().double() / (K * counts.double())
+    w = torch.ones(K, dtype=torch.float64)
+    for label, value in dict(class_weight).items():
+        at = np.nonzero(classes == label)[0]
+        if at.size != 1:
+            raise ValueError(f"class_weight names the label {label!r}, which the data does not have")
+        if not float(value) > 0:
+            raise ValueError("class weights must be positive")
+        w[int(at[0])] = float(value)
+    return w
+
+
+def _one_classifier(w, Cw, held, group):
+    """The problems of one classifier with class weights w [K] -> lists (cls, held, wpos, wneg, scale, group).  Two classes
+    are one problem: class index 0 is the positive class ``classes_[1]`` (see ``_class_indexes``) and carries w[1]."""
+    K = int(w.numel())
+    if K == 2:
+        return [0], [held], [float(w[1])], [float(w[0])], [Cw], [group]
+    return list(range(K)), [held] * K, w.tolist(), [1.0] * K, [Cw] * K, [group] * K
+
+
+def _class_indexes(y):
+    """labels [N] -> (sorted unique labels, class index per row as the passes want it, problems per classifier)."""
+    classes = torch.unique(y)
+    if classes.numel() < 2:
+        raise ValueError("LinearProbe needs at least two classes")
+    idx = torch.searchsorted(classes, y)
+    if classes.numel() == 2:                # one classifier; index 0 = the positive class, classes_[1]
+        return classes, 1 - idx, 1
+    return classes, idx, int(classes.numel())
+
+
 class _HostSums:
-    """float64 torch evaluation of the two quantities ``lla_svm_pass`` computes (the CPU path; the GPU tests' oracle)."""
+    """float64 torch evaluation of the two quantities ``lla_svm_grid_pass`` computes (the CPU path; the GPU tests' oracle)."""
     dtype = torch.float64
     slack = 1e-14
 
-    def __init__(self, rows, y, K):
-        self.rows, self.y, self.K = rows, y, K
+    def __init__(self, rows, y, prob, fold=None):
+        self.rows, self.y, self.prob, self.fold = rows, y, prob, fold
+        prob.on(self, rows.device)
         self.n_passes = 0
 
     def _signs(self, g0, g):
-        return torch.where(self.y[g0:g0 + g, None] == torch.arange(self.K)[None, :], 1.0, -1.0).to(torch.float64)
+        """-> (y_ij, c_ij / scale_j) for the rows g0 .. g0 + g - 1."""
+        p = self.prob
+        ys = torch.where(self.y[g0:g0 + g, None] == p.cls[None, :], 1.0, -1.0).to(torch.float64)
+        c = torch.where(ys > 0, p.wpos[None, :], p.wneg[None, :])
+        if self.fold is not None:
+            c = torch.where(self.fold[g0:g0 + g, None] == p.held[None, :], torch.zeros((), dtype=torch.float64), c)
+        return ys, c
 
     def column_squares(self):
         sq = torch.zeros(self.rows.dim, dtype=torch.float64)
@@ -115,65 +192,72 @@ class _HostSums:
         return sq
 
     def gradient(self, W, b):
-        loss, gW, gb = torch.zeros(self.K, dtype=torch.float64), torch.zeros_like(W), torch.zeros_like(b)
+        loss, gW, gb = torch.zeros(self.J, dtype=torch.float64), torch.zeros_like(W), torch.zeros_like(b)
         for g0, z in self.rows.groups():
             z = z.to(torch.float64)
-            ys = self._signs(g0, z.shape[0])
+            ys, c = self._signs(g0, z.shape[0])
             m = (1.0 - ys * (z @ W.T + b)).clamp_min(0.0)
-            r = -2.0 * ys * m
-            loss += (m * m).sum(0)
+            r = -2.0 * ys * m * c
+            loss += (m * m * c).sum(0)
             gW += r.T @ z
             gb += r.sum(0)
         self.n_passes += 1
-        return loss, gW, gb
+        return self.scale * loss, self.scale[:, None] * gW, self.scale * gb
 
     def hessian_vector(self, W, b, V, vb):
         hW, hb = torch.zeros_like(W), torch.zeros_like(b)
         for g0, z in self.rows.groups():
             z = z.to(torch.float64)
-            ys = self._signs(g0, z.shape[0])
+            ys, c = self._signs(g0, z.shape[0])
             active = (1.0 - ys * (z @ W.T + b)) > 0
-            t = 2.0 * torch.where(active, z @ V.T + vb, torch.zeros((), dtype=torch.float64))
+            t = 2.0 * torch.where(active, z @ V.T + vb, torch.zeros((), dtype=torch.float64)) * c
             hW += t.T @ z
             hb += t.sum(0)
         self.n_passes += 1
-        return hW, hb
+        return self.scale[:, None] * hW, self.scale * hb
 
 
 class _DeviceSums:
-    """The same two quantities from ``lla_svm_pass``, one call per decode group, accumulated on the device."""
+    """The same two quantities from ``lla_svm_grid_pass``, one call per decode group, accumulated on the device."""
     dtype = torch.float32
     slack = 1e-6          # Armijo slack, relative to f: the fp32 loss sums of two passes differ by rounding at this level
 
-    def __init__(self, rows, y, K):
+    def __init__(self, rows, y, prob, fold=None):
         C, dev = rows.dim, rows.device
         if C % 8 or not 8 <= C <= 1024:
             raise ValueError(f"the device probe needs a feature width that is a multiple of 8 in [8, 1024], got {C}")
-        self.rows, self.K, self.C, self.device = rows, K, C, dev
+        self.rows, self.C, self.device = rows, C, dev
+        prob.on(self, dev)
         self.y = y.to(torch.int32).to(dev).contiguous()
+        self.fold = None if fold is None else fold.to(torch.int32).to(dev).contiguous()
+        self.cols = [prob.cls.to(dev), prob.held.to(dev), prob.wpos.to(torch.float32).to(dev),
+                     prob.wneg.to(torch.float32).to(dev)]
+        self.scale32 = self.scale.to(torch.float32)
         self.L = _lib.lib()
-        nbytes = int(self.L.lla_svm_pass_workspace_bytes(C, K))
+        nbytes = int(self.L.lla_svm_grid_pass_workspace_bytes(C, self.J))
         if nbytes == 0:
-            raise ValueError(f"lla_svm_pass refuses C = {C}, K = {K}")
+            raise ValueError(f"lla_svm_grid_pass refuses C = {C}, J = {self.J}")
         self.ws = torch.empty(nbytes, dtype=torch.uint8, device=dev)
         self.n_passes = 0
 
     def _pass(self, W, b, V, vb):
-        K, C = self.K, self.C
-        oW = torch.zeros((K, C), dtype=torch.float32, device=self.device)
-        ob = torch.zeros(K, dtype=torch.float32, device=self.device)
-        loss = torch.zeros(K, dtype=torch.float64, device=self.device) if V is None else None
+        J, C = self.J, self.C
+        oW = torch.zeros((J, C), dtype=torch.float32, device=self.device)
+        ob = torch.zeros(J, dtype=torch.float32, device=self.device)
+        loss = torch.zeros(J, dtype=torch.float64, device=self.device) if V is None else None
+        cols = [_lib.ptr(t) for t in self.cols]
         with torch.cuda.device(self.device):
             st = _lib.stream_ptr(self.device)
             for g0, z in self.rows.groups():
                 g = int(z.shape[0])
                 zt = _lib.LLA_Z_F16 if z.dtype == torch.float16 else _lib.LLA_Z_F32
-                rc = self.L.lla_svm_pass(_lib.ptr(z), zt, int(z.stride(0)) if g > 1 else C, _lib.ptr(self.y[g0:g0 + g]), g, C,
-                                         _lib.ptr(W), _lib.ptr(b), _lib.ptr(V), _lib.ptr(vb), K, C, _lib.ptr(oW),
-                                         _lib.ptr(ob), _lib.ptr(loss), 1, _lib.ptr(self.ws), st)
-                _lib.check(rc, "lla_svm_pass")
+                fold = None if self.fold is None else self.fold[g0:g0 + g]
+                rc = self.L.lla_svm_grid_pass(_lib.ptr(z), zt, int(z.stride(0)) if g > 1 else C, _lib.ptr(self.y[g0:g0 + g]),
+                                              _lib.ptr(fold), g, C, _lib.ptr(W), _lib.ptr(b), _lib.ptr(V), _lib.ptr(vb), J, C,
+                                              *cols, _lib.ptr(oW), _lib.ptr(ob), _lib.ptr(loss), 1, _lib.ptr(self.ws), st)
+                _lib.check(rc, "lla_svm_grid_pass")
         self.n_passes += 1
-        return loss, oW, ob
+        return (None if loss is None else self.scale * loss), self.scale32[:, None] * oW, self.scale32 * ob
 
     def column_squares(self):
         sq = torch.zeros(self.C, dtype=torch.float64, device=self.device)
@@ -189,32 +273,36 @@ class _DeviceSums:
         return self._pass(W.contiguous(), b.contiguous(), V.contiguous(), vb.contiguous())[1:]
 
 
-def _newton_cg(sums, K, dim, n_rows, device, Cw, tol, max_iter):
-    """Batched truncated Newton-CG on f_k = 1/2 (|w|^2 + b^2) + Cw loss_k -> (W, b, f [K] float64, converged).
-    One host synchronisation per CG iteration and per line-search step."""
-    dt = sums.dtype
-    W, b = torch.zeros((K, dim), dtype=dt, device=device), torch.zeros(K, dtype=dt, device=device)
+def _newton_cg(sums, dim, n_rows, device, tol, max_iter):
+    """Batched truncated Newton-CG on the J problems of ``sums``, f_j = 1/2 (|w|^2 + b^2) + (weighted loss)_j
+    -> (W, b, f [J] float64, converged [groups] bool).  A problem stops once its gradient's sup norm is within ``tol`` of
+    the largest gradient at 0 among the problems of its group (one classifier).  One host synchronisation per CG
+    iteration and per line-search step."""
+    dt, J = sums.dtype, sums.J
+    W, b = torch.zeros((J, dim), dtype=dt, device=device), torch.zeros(J, dtype=dt, device=device)
 
     def evaluate(W, b):
         loss, gW, gb = sums.gradient(W, b)
-        f = 0.5 * ((W.double() ** 2).sum(1) + b.double() ** 2) + Cw * loss
-        return f, W + Cw * gW, b + Cw * gb
+        f = 0.5 * ((W.double() ** 2).sum(1) + b.double() ** 2) + loss
+        return f, W + gW, b + gb
 
-    def sup(gW, gb):          # per-class sup norm of the gradient
+    def sup(gW, gb):          # per-problem sup norm of the gradient
         return torch.maximum(gW.abs().amax(1), gb.abs())
 
-    # Jacobi preconditioner from the column scales of the data: 1 + 2 Cw sum_i z_ic^2 bounds the Hessian's diagonal for
-    # every class and every active set (the intercept's column is all ones), so one vector serves the whole solve
-    mW = (1.0 + 2.0 * Cw * sums.column_squares()).to(dt)[None, :]
-    mb = 1.0 + 2.0 * Cw * n_rows
+    # Jacobi preconditioner from the column scales of the data: 1 + 2 c_j sum_i z_ic^2, c_j the larger of the problem's
+    # two weights and the sum over ALL rows, bounds the Hessian's diagonal for every problem, every active set and every
+    # held-out fold (the intercept's column is all ones), so one vector of column scales serves the whole solve
+    mW = (1.0 + (2.0 * sums.cmax)[:, None] * sums.column_squares()[None, :]).to(dt)
+    mb = (1.0 + 2.0 * sums.cmax * n_rows).to(dt)
     f, gW, gb = evaluate(W, b)
-    g0 = float(sup(gW, gb).max())
+    g0 = torch.zeros(sums.n_groups, dtype=dt, device=device).scatter_reduce(0, sums.group, sup(gW, gb), "amax")
+    stop_at = (tol * g0.double())[sums.group].to(dt)
     for _ in range(int(max_iter)):
-        live = sup(gW, gb) > tol * g0    # classes still short of the stopping rule; the others stay where they are
+        live = sup(gW, gb) > stop_at     # problems still short of the stopping rule; the others stay where they are
         if not bool(live.any()):
             break
         lv = live.to(dt)
-        # preconditioned CG on H d = -g, H v = v + Cw (generalised Hessian sums)(v), all classes in one pass
+        # preconditioned CG on H d = -g, H v = v + (weighted generalised Hessian sums)(v), all problems in one pass
         dW, db = torch.zeros_like(W), torch.zeros_like(b)
         rW, rb = -gW * lv[:, None], -gb * lv
         yW, yb = rW / mW, rb / mb
@@ -223,7 +311,7 @@ def _newton_cg(sums, K, dim, n_rows, device, Cw, tol, max_iter):
         stop = _CG_TOL ** 2 * rs
         for _cg in range(_CG_MAX):
             hW, hb = sums.hessian_vector(W, b, pW, pb)
-            hW, hb = pW + Cw * hW, pb + Cw * hb
+            hW, hb = pW + hW, pb + hb
             busy = (rs > stop).to(dt)
             alpha = busy * rs / ((pW * hW).sum(1) + pb * hb).clamp_min(torch.finfo(dt).tiny)
             dW += alpha[:, None] * pW
@@ -237,9 +325,9 @@ def _newton_cg(sums, K, dim, n_rows, device, Cw, tol, max_iter):
             beta = busy * rs2 / rs.clamp_min(torch.finfo(dt).tiny)
             pW, pb = yW + beta[:, None] * pW, yb + beta * pb
             rs = torch.where(busy > 0, rs2, rs)
-        # per-class backtracking: a class keeps its step length once the Armijo condition holds for it
+        # per-problem backtracking: a problem keeps its step length once the Armijo condition holds for it
         gd = ((gW * dW).sum(1) + gb * db).double()
-        t = torch.ones(K, dtype=dt, device=device)
+        t = torch.ones(J, dtype=dt, device=device)
         for _ls in range(_BACKTRACKS):
             W2, b2 = W + t[:, None] * dW, b + t * db
             f2, gW2, gb2 = evaluate(W2, b2)
@@ -247,25 +335,41 @@ def _newton_cg(sums, K, dim, n_rows, device, Cw, tol, max_iter):
             if bool(ok.all()):
                 break
             t = torch.where(ok, t, t * 0.5)
-        else:                            # classes whose step never passed stay where they were
+        else:                            # problems whose step never passed stay where they were
             t = torch.where(ok, t, torch.zeros_like(t))
             W2, b2 = W + t[:, None] * dW, b + t * db
             f2, gW2, gb2 = evaluate(W2, b2)
         W, b, f, gW, gb = W2, b2, f2, gW2, gb2
         if not bool((t > 0).any()):      # nothing moved: rounding has the last word
             break
-    converged = bool((sup(gW, gb) <= tol * g0).all())
-    return W, b, f, converged
+    short = torch.zeros(sums.n_groups, dtype=dt, device=device).index_add_(0, sums.group, (sup(gW, gb) > stop_at).to(dt))
+    return W, b, f, (short == 0).cpu()
+
+
+def _labels_of(data, labels, n):
+    if labels is None:
+        if not _is_latents(data) or data._labels is None:
+            raise ValueError("no labels: pass labels=, or open the latents with a label_file")
+        labels = data._labels
+    y = labels.detach().cpu() if isinstance(labels, torch.Tensor) else torch.from_numpy(np.asarray(labels))
+    y = y.reshape(-1)
+    if y.is_floating_point() or y.dtype == torch.bool:
+        raise TypeError("labels must be integers")
+    if y.numel() != n:
+        raise ValueError(f"{y.numel()} labels for {n} rows")
+    return y.to(torch.int64)
 
 
 class LinearProbe:
-    """``LinearProbe(C=7e-3, tol=1e-4, max_iter=100)``: scikit-learn's ``LinearSVC(C)`` objective (its defaults: squared
-    hinge, L2, one-vs-rest, regularised intercept), solved where the data lives.
+    """``LinearProbe(C=7e-3, tol=1e-4, max_iter=100, class_weight=None)``: scikit-learn's ``LinearSVC(C)`` objective (its
+    defaults: squared hinge, L2, one-vs-rest, regularised intercept), solved where the data lives.  ``class_weight`` is
+    ``LinearSVC``'s: ``None``, ``"balanced"`` (``n / (K count_k)``) or a ``{label: weight}`` dict (labels left out weigh 1);
+    the classifier of class k weighs the rows of class k by ``C w[k]`` and all other rows by ``C``, as liblinear does.
 
     ``fit(data, labels=None, rows_per_pass=65536, keep_rows=False)``
         data    a ``CompressedLatents`` / ``HyperpriorLatents`` (its own labels unless ``labels`` is given), or a
                 ``[N, C]`` tensor / array together with ``labels``.
-        rows_per_pass   rows decoded (``take``) and handed to ``lla_svm_pass`` at a time; statuses are checked on the
+        rows_per_pass   rows decoded (``take``) and handed to ``lla_svm_grid_pass`` at a time; statuses are checked on the
                 first pass only.
         keep_rows       decode once and keep the fp32 rows (N x C x 4 bytes) instead of decoding every pass.
     Stops when ``|grad f|_inf <= tol |grad f(0)|_inf``; warns and sets ``converged_ = False`` at ``max_iter`` Newton steps.
@@ -275,54 +379,39 @@ class LinearProbe:
     ``converged_``.  ``decision_function`` returns ``[N, K]`` (``[N]`` for two classes), fp32 from ``lla_gemm_f32`` on the
     device and float64 on the CPU; ``predict`` returns labels, ``score`` the mean accuracy."""
 
-    def __init__(self, C=7e-3, tol=1e-4, max_iter=100):
+    def __init__(self, C=7e-3, tol=1e-4, max_iter=100, class_weight=None):
         if not C > 0 or not tol > 0 or int(max_iter) < 1:
             raise ValueError("C and tol must be positive, max_iter at least 1")
-        self.C, self.tol, self.max_iter = float(C), float(tol), int(max_iter)
+        if not (class_weight is None or class_weight == "balanced" or isinstance(class_weight, dict)):
+            raise ValueError(f"class_weight must be None, 'balanced' or a dict, got {class_weight!r}")
+        self.C, self.tol, self.max_iter, self.class_weight = float(C), float(tol), int(max_iter), class_weight
         self.coef_ = self.intercept_ = self.classes_ = None
 
     # ------------------------------------------------------------------ labels
-    @staticmethod
-    def _labels_of(data, labels, n):
-        if labels is None:
-            if not _is_latents(data) or data._labels is None:
-                raise ValueError("no labels: pass labels=, or open the latents with a label_file")
-            labels = data._labels
-        y = labels.detach().cpu() if isinstance(labels, torch.Tensor) else torch.from_numpy(np.asarray(labels))
-        y = y.reshape(-1)
-        if y.is_floating_point() or y.dtype == torch.bool:
-            raise TypeError("labels must be integers")
-        if y.numel() != n:
-            raise ValueError(f"{y.numel()} labels for {n} rows")
-        return y.to(torch.int64)
+    _labels_of = staticmethod(_labels_of)
 
     # ------------------------------------------------------------------ fit
     def fit(self, data, labels=None, rows_per_pass=65536, keep_rows=False):
         rows = _Rows(data, rows_per_pass, keep_rows)
         y = self._labels_of(data, labels, rows.n)
-        classes = torch.unique(y)           # sorted
-        if classes.numel() < 2:
-            raise ValueError("LinearProbe needs at least two classes")
-        idx = torch.searchsorted(classes, y)
-        if classes.numel() == 2:            # one classifier; label 0 = the positive class, classes_[1]
-            K, idx = 1, 1 - idx
-        else:
-            K = int(classes.numel())
+        classes, idx, _ = _class_indexes(y)
+        counts = torch.bincount(torch.searchsorted(classes, y), minlength=int(classes.numel()))
+        prob = _Problems(*_one_classifier(_class_weights(self.class_weight, classes.numpy(), counts), self.C, _NO_FOLD, 0))
         try:
-            if rows.device.type == "cuda":
-                sums = _DeviceSums(rows, idx, K)
-            else:
-                sums = _HostSums(rows, idx, K)
-            W, b, f, converged = _newton_cg(sums, K, rows.dim, rows.n, rows.device, self.C, self.tol, self.max_iter)
+            sums = (_DeviceSums if rows.device.type == "cuda" else _HostSums)(rows, idx, prob)
+            W, b, f, converged = _newton_cg(sums, rows.dim, rows.n, rows.device, self.tol, self.max_iter)
         finally:
             rows.close()
-        self.coef_, self.intercept_ = W.to(torch.float32), b.to(torch.float32)
-        self.classes_ = classes.numpy()
-        self.n_passes_, self.objective_, self.converged_ = sums.n_passes, float(f.sum()), converged
-        self._packed = None
-        if not converged:
+        self._set(W, b, classes, sums.n_passes, float(f.sum()), bool(converged.all()))
+        if not self.converged_:
             warnings.warn(f"LinearProbe stopped short of tol = {self.tol} after {self.max_iter} Newton steps", RuntimeWarning)
         return self
+
+    def _set(self, W, b, classes, n_passes, objective, converged):
+        self.coef_, self.intercept_ = W.to(torch.float32), b.to(torch.float32)
+        self.classes_ = classes.numpy()
+        self.n_passes_, self.objective_, self.converged_ = n_passes, objective, converged
+        self._packed = None
 
     # ------------------------------------------------------------------ predict
     def _pack(self, dev):
@@ -379,3 +468,181 @@ class LinearProbe:
         pred = self.predict(data, rows_per_pass)
         y = self._labels_of(data, labels, pred.numel()).to(pred.device)
         return float((pred == y).double().mean())
+
+
+class LinearProbeCV:
+    """``LinearProbeCV(candidates, cv=5, tol=1e-4, max_iter=100, refit=True, max_problems=4096)``: the search the reference
+    evaluates a compressor with (its utils/Z_linear_eval.py:62-93: ``RandomizedSearchCV`` over ``C`` and ``class_weight``,
+    scored by accuracy, the winner refitted), with every (candidate, fold, class) solved in the same passes over the data.
+
+    candidates  a sequence of ``(C, class_weight)``; ``LinearProbeCV.sample(n, seed)`` draws the reference's distribution.
+    cv          an int: stratified and unshuffled -- the r-th row, in file order, of each class goes to fold ``r % cv``;
+                or an int array ``[N]`` of fold ids, -1 for a row that always trains and never validates (scikit-learn's
+                ``PredefinedSplit``).  ``"balanced"`` weights are counted on the training part of each fold.
+    refit       also fit every candidate on all rows, in the same passes: ``best_estimator_`` costs no second solve.
+    max_problems  problems (classifiers x classes) solved side by side; more are solved in batches of whole classifiers.
+
+    ``fit(data, labels=None, rows_per_pass=65536, keep_rows=False)`` takes what ``LinearProbe.fit`` takes.  Afterwards:
+    ``cv_scores_`` float64 ``[candidates, folds]`` (accuracy on the held-out rows), ``mean_scores_``, ``best_index_`` (the
+    first maximum, as scikit-learn ranks), ``best_params_``, ``fold_coef_`` / ``fold_intercept_`` fp32
+    ``[candidates, folds, K or 1, C]``, ``best_estimator_`` (a fitted ``LinearProbe``; ``None`` without ``refit``),
+    ``classes_``, ``folds_`` (the fold ids), ``n_passes_``, ``converged_`` bool ``[candidates, folds (+ 1 with refit)]``."""
+
+    def __init__(self, candidates, cv=5, tol=1e-4, max_iter=100, refit=True, max_problems=4096):
+        self.candidates = [(float(C), cw) for C, cw in candidates]
+        if not self.candidates:
+            raise ValueError("no candidates")
+        for C, cw in self.candidates:
+            LinearProbe(C=C, tol=tol, max_iter=max_iter, class_weight=cw)        # (its checks)
+        if int(max_problems) < 1:
+            raise ValueError("max_problems must be at least 1")
+        self.cv, self.tol, self.max_iter = cv, float(tol), int(max_iter)
+        self.refit, self.max_problems = bool(refit), int(max_problems)
+        self.cv_scores_ = self.best_estimator_ = None
+
+    @staticmethod
+    def sample(n, seed, low=1e-3, high=1.0):
+        """n candidates as the reference draws them: C log-uniform in [low, high], class_weight a coin between
+        ``"balanced"`` and ``None``."""
+        if not 0 < low <= high:
+            raise ValueError("need 0 < low <= high")
+        rng = np.random.default_rng(seed)
+        Cs = np.exp(rng.uniform(np.log(low), np.log(high), size=int(n))).clip(low, high)
+        coins = rng.integers(0, 2, size=int(n))
+        return [(float(C), "balanced" if coin else None) for C, coin in zip(Cs, coins)]
+
+    # ------------------------------------------------------------------ folds
+    def _folds_of(self, cls_idx, n_classes):
+        """-> (fold id per row int64 [N], sorted fold ids); raises if a training part lacks a class or a fold is empty."""
+        N = int(cls_idx.numel())
+        if isinstance(self.cv, (int, np.integer)):
+            cv = int(self.cv)
+            if cv < 2:
+                raise ValueError("cv must be at least 2")
+            order = torch.argsort(cls_idx, stable=True)                         # file order within each class
+            counts = torch.bincount(cls_idx, minlength=n_classes)
+            rank = torch.arange(N) - (torch.cumsum(counts, 0) - counts)[cls_idx[order]]
+            fold = torch.empty(N, dtype=torch.int64)
+            fold[order] = rank % cv
+            ids = list(range(cv))
+        else:
+            fold = torch.as_tensor(np.asarray(self.cv.cpu() if isinstance(self.cv, torch.Tensor) else self.cv))
+            if fold.is_floating_point() or fold.dtype == torch.bool or fold.dim() != 1 or fold.numel() != N:
+                raise ValueError(f"cv must be an int or an int array of {N} fold ids")
+            fold = fold.to(torch.int64)
+            if int(fold.min()) < -1 or int(fold.max()) >= 2 ** 31 - 1:
+                raise ValueError("fold ids must be >= -1 (-1: always train)")
+            ids = [int(v) for v in torch.unique(fold) if int(v) >= 0]
+            if not ids:
+                raise ValueError("no row is ever held out")
+        train_counts = []
+        for f in ids:
+            if not bool((fold == f).any()):
+                raise ValueError(f"fold {f} holds no row")
+            c = torch.bincount(cls_idx[fold != f], minlength=n_classes)
+            if bool((c == 0).any()):
+                raise ValueError(f"the training part of fold {f} lacks a class")
+            train_counts.append(c)
+        return fold, ids, train_counts
+
+    # ------------------------------------------------------------------ fit
+    def fit(self, data, labels=None, rows_per_pass=65536, keep_rows=False):
+        rows = _Rows(data, rows_per_pass, keep_rows)
+        y = _labels_of(data, labels, rows.n)
+        classes, idx, Kp = _class_indexes(y)
+        sorted_idx = torch.searchsorted(classes, y)
+        n_classes = int(classes.numel())
+        fold, ids, train_counts = self._folds_of(sorted_idx, n_classes)
+        all_counts = torch.bincount(sorted_idx, minlength=n_classes)
+        nc, nf = len(self.candidates), len(ids)
+        per = nf + int(self.refit)
+        # one classifier (group) per (candidate, fold), then per candidate one with nothing held out
+        layout = [(c, f) for c in range(nc) for f in range(per)]
+        step = max(self.max_problems // Kp, 1)
+        device = rows.device
+        Sums = _DeviceSums if device.type == "cuda" else _HostSums
+        coef = torch.empty((nc, per, Kp, rows.dim), dtype=torch.float32, device=device)
+        icpt = torch.empty((nc, per, Kp), dtype=torch.float32, device=device)
+        objective = torch.empty((nc, per), dtype=torch.float64)
+        converged = torch.empty((nc, per), dtype=torch.bool)
+        self.n_passes_ = 0
+        try:
+            for at in range(0, len(layout), step):
+                batch, cols = layout[at:at + step], [[] for _ in range(6)]
+                for g, (c, f) in enumerate(batch):
+                    Cw, cw = self.candidates[c]
+                    w = _class_weights(cw, classes.numpy(), train_counts[f] if f < nf else all_counts)
+                    for dst, src in zip(cols, _one_classifier(w, Cw, ids[f] if f < nf else _NO_FOLD, g)):
+                        dst += src
+                sums = Sums(rows, idx, _Problems(*cols), fold)
+                W, b, fv, conv = _newton_cg(sums, rows.dim, rows.n, device, self.tol, self.max_iter)
+                self.n_passes_ += sums.n_passes
+                for g, (c, f) in enumerate(batch):
+                    coef[c, f], icpt[c, f] = W[g * Kp:(g + 1) * Kp], b[g * Kp:(g + 1) * Kp]
+                    objective[c, f], converged[c, f] = float(fv[g * Kp:(g + 1) * Kp].sum()), bool(conv[g])
+            held = torch.tensor(ids, dtype=torch.int64).repeat(nc)
+            right = self._score(rows, coef[:, :nf].reshape(nc * nf * Kp, rows.dim), icpt[:, :nf].reshape(-1), idx, fold, held, Kp)
+            self.n_passes_ += 1
+        finally:
+            rows.close()
+        n_held = torch.stack([(fold == f).sum() for f in ids]).double()
+        self.cv_scores_ = right.reshape(nc, nf).double() / n_held[None, :]
+        self.mean_scores_ = self.cv_scores_.mean(1)
+        self.best_index_ = int(self.mean_scores_.argmax())                       # the first maximum
+        self.best_params_ = dict(zip(("C", "class_weight"), self.candidates[self.best_index_]))
+        self.fold_coef_, self.fold_intercept_ = coef[:, :nf].contiguous(), icpt[:, :nf].contiguous()
+        self.classes_, self.folds_, self.converged_ = classes.numpy(), list(ids), converged
+        self.best_estimator_ = None
+        if self.refit:
+            best = LinearProbe(C=self.best_params_["C"], tol=self.tol, max_iter=self.max_iter,
+                               class_weight=self.best_params_["class_weight"])
+            best._set(coef[self.best_index_, nf].clone(), icpt[self.best_index_, nf].clone(), classes, self.n_passes_,
+                      float(objective[self.best_index_, nf]), bool(converged[self.best_index_, nf]))
+            self.best_estimator_ = best
+        if not bool(converged.all()):
+            warnings.warn(f"LinearProbeCV: {int((~converged).sum())} of {converged.numel()} classifiers stopped short of "
+                          f"tol = {self.tol} after {self.max_iter} Newton steps", RuntimeWarning)
+        return self
+
+    @staticmethod
+    def _score(rows, W, b, idx, fold, held, Kp):
+        """One walk: the scores of all problems (``lla_gemm_f32`` on the device, float64 on the CPU), the argmax within
+        each classifier, and per classifier the number of rows of its held-out fold it gets right -> int64 [classifiers]
+        on the CPU.  Reduced per decode group (in slices of it where [rows, problems] would be large)."""
+        dev, (J, C) = rows.device, W.shape
+        G = J // Kp
+        idx, fold, held = idx.to(dev), fold.to(dev), held.to(dev)
+        right = torch.zeros(G, dtype=torch.int64, device=dev)
+
+        def count(S, r0):
+            S = S.reshape(S.shape[0], G, Kp)
+            pred = torch.where(S[:, :, 0] > 0, 0, 1) if Kp == 1 else S.argmax(2)
+            n = S.shape[0]
+            hit = (pred == idx[r0:r0 + n, None]) & (fold[r0:r0 + n, None] == held[None, :])
+            right.add_(hit.sum(0))
+
+        if dev.type == "cuda":
+            if C % 8:
+                raise ValueError("the device path needs a feature width that is a multiple of 8")
+            npad = -(-J // 8) * 8
+            w, bp = torch.zeros((npad, C), dtype=torch.float32, device=dev), torch.zeros(npad, dtype=torch.float32, device=dev)
+            w[:J], bp[:J] = W, b
+            piece = max(min((1 << 25) // npad, rows.group), 1)
+            out = torch.empty((min(piece, max(rows.n, 1)), npad), dtype=torch.float32, device=dev)
+            L = _lib.lib()
+            with torch.cuda.device(dev):
+                for g0, z in rows.groups():
+                    z = z if z.dtype == torch.float32 else z.float()
+                    z = z if z.stride(1) == 1 and z.stride(0) % 4 == 0 else z.contiguous()
+                    for r0 in range(0, int(z.shape[0]), piece):
+                        zz = z[r0:r0 + piece]
+                        n = int(zz.shape[0])
+                        rc = L.lla_gemm_f32(_lib.ptr(zz), int(zz.stride(0)) if n > 1 else C, _lib.ptr(w), C, _lib.ptr(bp),
+                                            _lib.ptr(out), npad, n, npad, C, 0, _lib.stream_ptr(dev))
+                        _lib.check(rc, "lla_gemm_f32")
+                        count(out[:n, :J], g0 + r0)
+        else:
+            W64, b64 = W.to(torch.float64), b.to(torch.float64)
+            for g0, z in rows.groups():
+                count(z.to(torch.float64) @ W64.T + b64, g0)
+        return right.cpu()

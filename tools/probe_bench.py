@@ -15,7 +15,18 @@ by more than the spread of (c)'s own runs.
 Reference point, reported and not gated: wall time of ``LinearProbe.fit`` on an STL10-shaped problem (5000 x 512,
 K = 10) next to scikit-learn's ``LinearSVC(C=7e-3).fit`` on the same rows on this host, when scikit-learn is installed.
 
+``--grid`` measures the cross-validated search instead: K = 10, 8 candidates x 5 folds = 400 problems,
+
+(g)  one ``lla_svm_grid_pass`` over all N rows, every problem masking its own held-out fold,
+(s)  what the library offered before: 40 ``lla_svm_pass(K = 10)`` calls, each over a contiguous copy of that fold's
+     training rows (the copies are made outside the timed region),
+both with the rows resident and streamed (``take`` of the rows a call needs, then the pass); a scale arm (K = 1000,
+2 candidates x 2 folds = 4000 problems) is reported only.  Bar: the median of (g) lies below the median of (s) by more
+than the spread of (s)'s own runs, resident and streamed.  Reported, not gated: wall time of ``LinearProbeCV.fit`` at the
+STL10 shape against the same search as a loop of ``LinearProbe.fit``.
+
 usage (GPU box): python tools/probe_bench.py [--records 131072] [--reps 3] [--out profiles/linear_probe.txt]
+                 python tools/probe_bench.py --grid --out profiles/linear_probe_cv.txt
 """
 import argparse
 import os
@@ -30,7 +41,144 @@ import torch  # noqa: E402
 
 import hubconf  # noqa: E402
 from latents_bench import interleaved, med  # noqa: E402
-from lossyless_amd import LinearProbe, _lib  # noqa: E402
+from lossyless_amd import LinearProbe, LinearProbeCV, _lib  # noqa: E402
+
+
+def grid_arms(args, say, dev, ds, Z, g):
+    """The --grid table (module docstring)."""
+    L, st = _lib.lib(), _lib.stream_ptr(dev)
+    N, C = Z.shape
+    group = 65536
+    buf = torch.empty((min(group, N), C), dtype=torch.float32, device=dev)
+    pieces = lambda idx: [idx[i:i + group] for i in range(0, idx.numel(), group)]       # noqa: E731
+    for K, n_cand, n_fold, gated in ((10, 8, 5, True), (1000, 2, 2, False)):
+        G = n_cand * n_fold
+        J = G * K
+        inner = args.inner or (10 if gated else 4)
+        y = torch.randint(0, K, (N,), generator=g).to(torch.int32).to(dev)
+        fold = (torch.arange(N) % n_fold).to(torch.int32).to(dev)
+        W = (torch.randn(J, C, generator=g) * 0.03).to(dev)
+        b = (torch.randn(J, generator=g) * 0.1).to(dev)
+        # problem (candidate c, fold f, class k) is column (c n_fold + f) K + k; candidate c weighs its positives by 1 + c / 8
+        cols = [torch.arange(K, dtype=torch.int32).repeat(G).to(dev),
+                torch.arange(n_fold, dtype=torch.int32).repeat_interleave(K).repeat(n_cand).to(dev),
+                (1.0 + torch.arange(n_cand) / 8.0).repeat_interleave(n_fold * K).to(dev), torch.ones(J, device=dev)]
+        ws = torch.empty(int(L.lla_svm_grid_pass_workspace_bytes(C, J)), dtype=torch.uint8, device=dev)
+        oW, ob = torch.empty((J, C), device=dev), torch.empty(J, device=dev)
+        ol = torch.empty(J, dtype=torch.float64, device=dev)
+
+        def grid(rows=Z, labels=y, folds=fold, acc=0):
+            rc = L.lla_svm_grid_pass(_lib.ptr(rows), _lib.LLA_Z_F32, C, _lib.ptr(labels), _lib.ptr(folds), rows.shape[0], C,
+                                     _lib.ptr(W), _lib.ptr(b), None, None, J, C, *[_lib.ptr(t) for t in cols], _lib.ptr(oW),
+                                     _lib.ptr(ob), _lib.ptr(ol), acc, _lib.ptr(ws), st)
+            _lib.check(rc, "lla_svm_grid_pass")
+
+        # (s): the parent's path.  One contiguous copy of every fold's training rows, one call per (candidate, fold)
+        train_idx = [torch.nonzero(fold != f)[:, 0] for f in range(n_fold)]
+        train_rows = [Z[idx] for idx in train_idx] if gated or N * C * 4 * n_fold <= 2 ** 31 else None
+        train_y = [y[idx].contiguous() for idx in train_idx]
+        ws1 = torch.empty(int(L.lla_svm_pass_workspace_bytes(C, K)), dtype=torch.uint8, device=dev)
+        sW, sb = torch.empty((J, C), device=dev), torch.empty(J, device=dev)
+        sl = torch.empty(J, dtype=torch.float64, device=dev)
+
+        def one(rows, labels, at, acc):
+            rc = L.lla_svm_pass(_lib.ptr(rows), _lib.LLA_Z_F32, C, _lib.ptr(labels), rows.shape[0], C, _lib.ptr(W[at:at + K]),
+                                _lib.ptr(b[at:at + K]), None, None, K, C, _lib.ptr(sW[at:at + K]), _lib.ptr(sb[at:at + K]),
+                                _lib.ptr(sl[at:at + K]), acc, _lib.ptr(ws1), st)
+            _lib.check(rc, "lla_svm_pass")
+
+        def loop():
+            for c in range(n_cand):
+                for f in range(n_fold):
+                    one(train_rows[f], train_y[f], (c * n_fold + f) * K, 0)
+
+        idxs = [(g0, torch.arange(g0, min(g0 + group, N), device=dev)) for g0 in range(0, N, group)]
+        train_pieces = [[(p, y[p].contiguous()) for p in pieces(idx)] for idx in train_idx]
+
+        def grid_streamed():
+            oW.zero_(), ob.zero_(), ol.zero_()
+            for g0, idx in idxs:
+                rows = ds.take(idx, out=buf[:idx.numel()], check=False)
+                grid(rows, y[g0:g0 + idx.numel()], fold[g0:g0 + idx.numel()], 1)
+
+        def loop_streamed():
+            sW.zero_(), sb.zero_(), sl.zero_()
+            for c in range(n_cand):
+                for f in range(n_fold):
+                    for idx, labels in train_pieces[f]:
+                        one(ds.take(idx, out=buf[:idx.numel()], check=False), labels, (c * n_fold + f) * K, 1)
+
+        # the same sums from both paths before anything is timed: (s) unweighted, so (g)'s positives are compared through
+        # the weight -- the loss is linear in it only per sign, so the check is on candidate 0 (weight 1) for every fold
+        grid(), loop()
+        torch.cuda.synchronize(dev)
+        first = n_fold * K
+        scale = float(sW[:first].abs().max())
+        err = float((oW[:first] - sW[:first]).abs().max()) / scale
+        lerr = float(((ol[:first] - sl[:first]).abs() / sl[:first]).max())
+        assert err < 1e-4 and lerr < 1e-5, f"arms disagree: {err:.2e} {lerr:.2e}"
+        arms = {"(g) one lla_svm_grid_pass, rows resident": grid, f"(s) {G} lla_svm_pass calls, rows resident": loop}
+        if gated:
+            keep = oW.clone()
+            grid_streamed()
+            torch.cuda.synchronize(dev)
+            assert float((oW - keep).abs().max()) / scale < 1e-4, "the streamed grid pass disagrees"
+            arms["(g') streamed: take + lla_svm_grid_pass"] = grid_streamed
+            arms[f"(s') streamed: {G} x (take + lla_svm_pass)"] = loop_streamed
+        times = interleaved(arms, inner, args.reps, dev)
+        say()
+        say(f"K = {K}, {n_cand} candidates x {n_fold} folds = {J} problems ({-(-J // 32)} problem tiles): ms per pass over {N} rows, "
+            f"device events over {inner} back-to-back passes, {args.reps} interleaved runs   (max |(g) - (s)| / max |(s)| = {err:.1e})")
+        for k, ts in times.items():
+            runs = "  ".join(f"{x:9.4f}" for x in ts)
+            say(f"    {k:46s} {runs}   median {med(ts):9.4f} ms")
+        names = list(times)
+        for gk, sk in zip(names[0::2], names[1::2]):
+            gt, stt = times[gk], times[sk]
+            spread = max(stt) - min(stt)
+            verdict = ("MET" if med(gt) < med(stt) - spread else "MISSED") if gated else "reported only"
+            say(f"    {gk[:4].strip()} / {sk[:4].strip()} medians = {med(gt) / med(stt):.3f};  spread of {sk[:4].strip()} = {spread:.4f} ms;  "
+                f"{sk[:4].strip()} - {gk[:4].strip()} = {med(stt) - med(gt):+.4f} ms   -> bar {verdict}")
+        gt = times[names[0]]
+        say(f"    (g): {4.0 * N * C * (-(-J // 32) * 32) / med(gt) / 1e9:.1f} TFLOP/s on the padded tiles, z read {-(-J // 32)} times "
+            f"({N * C * 4 * -(-J // 32) / med(gt) / 1e9:.2f} TB/s, mostly from cache)")
+        del train_rows, train_pieces, W, oW, sW
+
+    # whole call at the STL10 shape: the search in shared passes against the same search as a loop of fits
+    n, k, C = 5000, 10, Z.shape[1]
+    labels = torch.arange(n) % k
+    mu = torch.randn(k, C, generator=g) * 0.1
+    Xd = (mu[labels] + torch.randn(n, C, generator=g) * 0.5).to(dev)
+    cands = LinearProbeCV.sample(8, seed=0)
+    LinearProbeCV(cands[:2], cv=5).fit(Xd[:512], labels[:512])            # (code objects loaded)
+    torch.cuda.synchronize(dev)
+    t0 = time.perf_counter()
+    cv = LinearProbeCV(cands, cv=5).fit(Xd, labels)
+    torch.cuda.synchronize(dev)
+    cv_s = time.perf_counter() - t0
+    fold = torch.empty(n, dtype=torch.int64)
+    for c in range(k):                                                   # the r-th row of a class goes to fold r % 5
+        at = torch.nonzero(labels == c)[:, 0]
+        fold[at] = torch.arange(at.numel()) % 5
+    t0 = time.perf_counter()
+    passes, scores = 0, torch.zeros(len(cands), 5, dtype=torch.float64)
+    for c, (Cw, cw) in enumerate(cands):
+        for f in range(5):
+            tr, te = torch.nonzero(fold != f)[:, 0].to(dev), torch.nonzero(fold == f)[:, 0].to(dev)
+            p = LinearProbe(C=Cw, class_weight=cw).fit(Xd[tr], labels[tr.cpu()])
+            scores[c, f] = p.score(Xd[te], labels[te.cpu()])
+            passes += p.n_passes_ + 1
+    best = int(scores.mean(1).argmax())
+    p = LinearProbe(C=cands[best][0], class_weight=cands[best][1]).fit(Xd, labels)
+    torch.cuda.synchronize(dev)
+    loop_s = time.perf_counter() - t0
+    say()
+    say(f"STL10-shaped search ({n} x {C}, K = {k}, 8 candidates x 5 folds + refit): LinearProbeCV.fit {cv_s:.3f} s wall, "
+        f"{cv.n_passes_} passes, all converged {bool(cv.converged_.all())}, best {cv.best_index_} "
+        f"(mean accuracy {float(cv.mean_scores_[cv.best_index_]):.4f})")
+    say(f"    the same search as a loop of LinearProbe.fit (40 fits + scores + 1 refit): {loop_s:.3f} s wall, {passes + p.n_passes_} passes, "
+        f"best {best} (mean accuracy {float(scores.mean(1)[best]):.4f}); max |score difference| "
+        f"{float((scores - cv.cv_scores_).abs().max()):.4f}   (reported, not gated)")
 
 
 def main():
@@ -38,6 +186,7 @@ def main():
     ap.add_argument("--records", type=int, default=131072)
     ap.add_argument("--reps", type=int, default=3)
     ap.add_argument("--inner", type=int, default=0, help="calls per timed window (0: 40 at K = 10, 8 at K = 1000)")
+    ap.add_argument("--grid", action="store_true", help="measure the cross-validated search (lla_svm_grid_pass) instead")
     ap.add_argument("--out", default=None)
     args = ap.parse_args()
     if not torch.cuda.is_available():
@@ -71,6 +220,13 @@ def main():
     group = 65536
     buf = torch.empty((min(group, N), C), dtype=torch.float32, device=dev)
     idxs = [(g0, torch.arange(g0, min(g0 + group, N), device=dev)) for g0 in range(0, N, group)]
+
+    if args.grid:
+        grid_arms(args, say, dev, ds, Z, g)
+        if args.out:
+            with open(args.out, "w") as fh:
+                fh.write("\n".join(lines) + "\n")
+        return
 
     for K in (10, 1000):
         inner = args.inner or (40 if K <= 32 else 8)

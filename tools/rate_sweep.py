@@ -67,6 +67,11 @@ def main():
     ap.add_argument("--device-probe", action="store_true",
                     help="also fit lossyless_amd.LinearProbe on the device from the container kept compressed "
                          "(adds linear_probe_accuracy and linear_probe_fit_s)")
+    ap.add_argument("--device-probe-cv", type=int, default=0, metavar="N",
+                    help="also run the reference's search (utils/Z_linear_eval.py: N draws of C ~ loguniform(1e-3, 1) and "
+                         "class_weight, 5-fold up to 50 000 rows, one train / validation split above) with "
+                         "lossyless_amd.LinearProbeCV on the device (adds linear_probe_cv_best, _validation_accuracy, "
+                         "_accuracy and _fit_s)")
     args = ap.parse_args()
 
     weights = os.environ.get("LOSSYLESS_CLIP_WEIGHTS", "synthetic")
@@ -130,6 +135,18 @@ def main():
                     torch.cuda.synchronize()
                     probe = dict(linear_probe_fit_s=round(time.perf_counter() - t0, 3),
                                  linear_probe_accuracy=float(fitted.score(comp.open_dataset(ft), np.asarray(Yt))))
+                if args.device_probe_cv:
+                    from lossyless_amd import LinearProbeCV
+                    # above 50 000 rows the reference validates on one predefined split: every tenth row here
+                    folds = 5 if n <= 50000 else np.where(np.arange(n) % 10 == 0, 0, -1)
+                    t0 = time.perf_counter()
+                    cv = LinearProbeCV(LinearProbeCV.sample(args.device_probe_cv, seed=0), cv=folds)
+                    cv.fit(comp.open_dataset(f), np.asarray(Y))
+                    torch.cuda.synchronize()
+                    probe.update(linear_probe_cv_fit_s=round(time.perf_counter() - t0, 3),
+                                 linear_probe_cv_best=dict(cv.best_params_),
+                                 linear_probe_cv_validation_accuracy=float(cv.mean_scores_[cv.best_index_]),
+                                 linear_probe_cv_accuracy=float(cv.best_estimator_.score(comp.open_dataset(ft), np.asarray(Yt))))
         print(json.dumps(dict(rate_point=name, data=data, clip_weights=weights, images=n,
                               call=("Dataset(transform=RawRGB) -> compress_dataset(dataset, file, label_file, "
                                     f"dict(batch_size={args.batch}, num_workers={args.workers}))") if shaped
