@@ -626,6 +626,23 @@ int lla_patch_embed_f16(const void *images, int layout, int B, const void *conv_
 /* y16[r][:] = LayerNorm(x32[r*row_stride : +768]) * w + b, eps 1e-5. */
 int lla_layernorm768(const float *x, size_t row_stride, const float *w, const float *b,
                      void *y16, int rows, void *stream);
+/* The tower's residual GEMM with the LayerNorm that follows in its epilogue (out-proj + ln_2, c_proj + ln_1 of the next
+ * block: clip ResidualAttentionBlock, hub/compressor.py:93), as the tower's layer loop launches it:
+ *   x[M][768] (fp32, in place) += A[M][K] (fp16, row stride lda) * W[768][K]^T (fp16) + bias (fp32 [768] or NULL)
+ *   h16[M][768] (fp16) = LayerNorm(x) * gamma + beta, eps 1e-5 -- the bits lla_layernorm768 gives on the updated x
+ * on the four-wave kernel, followed by the clean-up kernel (walking the other way) for the row tiles whose three column
+ * tiles did not find each other's partial sums in time.  wait_cycles: as LLA_TOWER_OPT_LNX_WAIT (the tower's default is
+ * 24000; 0: look once; < 0: every row tile through the clean-up kernel; every wait is bounded).  rev 0 / 1: first / last
+ * rows first.  Every combination gives the same bits.
+ * M % 256 == 0 (M = 256, one row tile, is valid), 256 <= K, K % 64 == 0, lda >= K, lda % 8 == 0, M * 768 < 2^32 and the
+ * operands within 32-bit byte offsets (M * lda < 2^31): exactly the shapes lla_gemm_plan answers LLA_OK to for epi 9,
+ * N = ldc = 768.  All pointers 16-byte aligned.  Anything else is LLA_EINVAL, decided before any device call.
+ * workspace [dev] lla_gemm_resid_layernorm768_workspace_bytes(M) bytes (0 for a refused M), contents irrelevant: the call
+ * zeroes the words it reads before it writes them and tags what it publishes with an epoch of its own. */
+size_t lla_gemm_resid_layernorm768_workspace_bytes(int M);
+int lla_gemm_resid_layernorm768(const void *A, int lda, const void *W, const float *bias, float *x, const float *gamma,
+                                const float *beta, void *h16, int M, int K, int wait_cycles, int rev, void *workspace,
+                                void *stream);
 /* qkv fp16 [B*50][2304] -> o fp16 [B*50][768]; 12 heads of 64, softmax(QK^T/8)V. */
 int lla_attention50(const void *qkv, void *o, int B, void *stream);
 

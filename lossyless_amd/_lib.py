@@ -107,6 +107,8 @@ _SIGNATURES = {
     "lla_rn50_workspace_bytes": (_sz, [_i]),
     "lla_rn50_forward": (_i, [_vp, _i, _vp, _vp, _sz, _i, _vp, _vp, _vp]),
     "lla_layernorm768": (_i, [_vp, _sz, _vp, _vp, _vp, _i, _vp]),
+    "lla_gemm_resid_layernorm768_workspace_bytes": (_sz, [_i]),
+    "lla_gemm_resid_layernorm768": (_i, [_vp, _i, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _vp, _vp]),
     "lla_attention50": (_i, [_vp, _vp, _i, _vp]),
 }
 EXPORTS = tuple(sorted(_SIGNATURES))

@@ -185,7 +185,8 @@ __device__ __forceinline__ float quick_gelu(float x) {
 //     order (DPP xor 1, xor 2, half mirror, row mirror, then (r0 + r1) + (r2 + r3)).
 //   * mean = S / 768 (as a multiply), var = max(Q / 768 - mean^2, 0), rstd = 1 / sqrt(var + 1e-5): one pass over the
 //     row instead of the two of rounds 1-4 (fp32: Q / 768 and mean^2 differ by many orders less than their 2^-24
-//     resolution unless |mean| >> sigma, which a residual stream is not; tests/test_gpu_vit.py bounds it at 36 sigma).
+//     resolution unless |mean| >> sigma, which a residual stream is not; tests/test_gpu_tower_gemms.py
+//     (test_layernorm_under_a_row_offset) holds every path to the fp16 output bound up to |mean| = 36 sigma).
 //   * y = ((x - mean) * rstd) * gamma + beta, four separately rounded fp32 operations (-ffp-contract=off), then fp16.
 // ---------------------------------------------------------------------------
 __device__ __forceinline__ void ln_finish(float S, float Q, float &mean, float &rstd) {

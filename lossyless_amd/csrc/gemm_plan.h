@@ -113,9 +113,11 @@ inline bool w8_takes(const GemmShape &s) {
 inline int w8_grid(const GemmShape &s, int cus) { return balanced_grid(ceil_div(s.M, 256) * (s.N / 256), cus); }
 
 // gemm_q4_kernel: A_PLAIN operands, whole 256-row tiles only; EPI_RESID_LNX exchanges a row's sums among its three column tiles
+// (and, like every fp32 epilogue, addresses C with 32-bit element offsets: plan_gemm asks the same of EPI_RESID before it
+// comes here; a tower slice is far below it, lla_gemm_resid_layernorm768 takes any M)
 inline bool q4_takes(const GemmShape &s) {
   const bool epi_ok = s.epi == EPI_F16 || s.epi == EPI_QGELU || s.epi == EPI_RESID ||
-                      (s.epi == EPI_RESID_LNX && s.N == kWidth && s.ldc == kWidth);
+                      (s.epi == EPI_RESID_LNX && s.N == kWidth && s.ldc == kWidth && (size_t)s.M * (size_t)kWidth < (1ull << 32));
   return s.amode == A_PLAIN && epi_ok && s.M > 0 && !(s.M & 255) && !(s.N & 255) && s.N <= 3072 && !(s.K & 63) && s.K >= kPpMinK &&
          s.lda >= s.K && !(s.lda & 7) && panel_offsets_fit(s, LLA_Q4_BUFDMA);
 }

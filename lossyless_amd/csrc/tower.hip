@@ -327,6 +327,60 @@ static unsigned next_lnx_epoch() {
   return e ? e : counter.fetch_add(1u, std::memory_order_relaxed) + 1u;
 }
 
+// x += A W^T + b on the four-wave kernel with the LayerNorm that follows in its epilogue (EPI_RESID_LNX, gemm_q4.hip), and
+// behind it lnx_cleanup_kernel for the row tiles whose column tiles missed each other: ONE statement of the sequence for the
+// tower's layer loop and for lla_gemm_resid_layernorm768.  g: the residual GEMM (C = x [M][768] fp32, rev = its direction);
+// part: [M / 256][3][256] granules of 16 bytes; words: {flag [M / 256][3], done [M / 256][3]} of THIS launch, zeroed by the
+// caller on `st` before; the launch gets a fresh epoch.  cleanup_rev: the direction of the clean-up kernel.
+static int resid_layernorm_gemm(GemmParams g, const float *gamma, const float *beta, f16 *h, float *part, unsigned *words,
+                                int wait, int cleanup_rev, hipStream_t st, Profiler *prof) {
+  const int tiles_m = g.M / 256;
+  g.lnx_g = gamma; g.lnx_b = beta; g.lnx_h = h; g.lnx_part = part;
+  g.lnx_flag = words;
+  g.lnx_done = words + (size_t)tiles_m * 3;
+  g.lnx_wait = wait;
+  g.lnx_epoch = next_lnx_epoch();
+  {
+    ProfScope scope(prof, st, LLA_PROF_GEMM, 2.0 * g.M * g.N * g.K);
+    const int rc2 = launch_q4(EPI_RESID_LNX, g, st);
+    if (rc2 != LLA_OK) return rc2;
+  }
+#if LLA_LNX_SYNC
+  if (hipStreamSynchronize(st) != hipSuccess) return hip_fail(hipGetLastError());   // (A/B only: common.h)
+#endif
+  return lnx_cleanup_impl(reinterpret_cast<const float *>(g.C), g.lnx_done, gamma, beta, h, tiles_m, cleanup_rev, g.lnx_epoch,
+                          st, prof);
+}
+
+size_t lla_gemm_resid_layernorm768_workspace_bytes(int M) {
+  if (M <= 0 || (M & 255)) return 0;
+  return (size_t)(M / 256) * (3 * 256 * 16 + 6 * sizeof(unsigned));
+}
+
+int lla_gemm_resid_layernorm768(const void *A, int lda, const void *W, const float *bias, float *x, const float *gamma,
+                                const float *beta, void *h16, int M, int K, int wait_cycles, int rev, void *workspace,
+                                void *stream) {
+  GemmParams g{};
+  g.A = reinterpret_cast<const f16 *>(A);
+  g.W = reinterpret_cast<const f16 *>(W);
+  g.bias = bias;
+  g.C = x;
+  g.M = M; g.N = kWidth; g.K = K; g.lda = lda; g.ldc = kWidth;
+  g.rev = rev;
+  if (!q4_takes(gemm_shape(EPI_RESID_LNX, A_PLAIN, g)) || (rev != 0 && rev != 1)) return LLA_EINVAL;
+  if (!A || !W || !x || !gamma || !beta || !h16 || !workspace) return LLA_EINVAL;
+  auto misaligned = [](const void *p) { return (reinterpret_cast<uintptr_t>(p) & 15u) != 0; };
+  if (misaligned(A) || misaligned(W) || misaligned(bias) || misaligned(x) || misaligned(gamma) || misaligned(beta) ||
+      misaligned(h16) || misaligned(workspace))
+    return LLA_EINVAL;
+  const int tiles_m = M / 256;
+  float *const part = reinterpret_cast<float *>(workspace);
+  unsigned *const words = reinterpret_cast<unsigned *>(part + (size_t)tiles_m * 3 * 256 * 4);
+  hipStream_t st = as_stream(stream);
+  if (hipMemsetAsync(words, 0, (size_t)tiles_m * 6 * sizeof(unsigned), st) != hipSuccess) return hip_fail(hipGetLastError());
+  return resid_layernorm_gemm(g, gamma, beta, reinterpret_cast<f16 *>(h16), part, words, wait_cycles, rev ^ 1, st, nullptr);
+}
+
 int lla_tower_set_option(void *tower, int option, int value) {
   Lanes *l = reinterpret_cast<Lanes *>(tower);
   if (!l) return LLA_EINVAL;
@@ -495,23 +549,11 @@ static int vit_forward_impl(const void *images, int layout, int B, const void *w
     if (lnx && hipMemsetAsync(lnx_words, 0, (size_t)(2 * kLayers - 1) * tiles_m * 6 * sizeof(unsigned), st) != hipSuccess)
       return hip_fail(hipGetLastError());
     auto lnx_gemm = [&](GemmParams g, const float *gamma, const float *beta, int &d) -> int {
-      g.lnx_g = gamma; g.lnx_b = beta; g.lnx_h = ws.xh; g.lnx_part = lnx_part;
-      g.lnx_flag = lnx_words + (size_t)lnx_launch * tiles_m * 6;
-      g.lnx_done = g.lnx_flag + (size_t)tiles_m * 3;
-      g.lnx_wait = tower ? tower->lnx_wait : kLnxWaitDefault;
-      g.lnx_epoch = next_lnx_epoch();
+      unsigned *const words = lnx_words + (size_t)lnx_launch * tiles_m * 6;
       ++lnx_launch;
       d ^= zig; g.rev = d;
-      {
-        ProfScope scope(prof, st, LLA_PROF_GEMM, 2.0 * g.M * g.N * g.K);
-        const int rc2 = launch_q4(EPI_RESID_LNX, g, st);
-        if (rc2 != LLA_OK) return rc2;
-      }
-#if LLA_LNX_SYNC
-      if (hipStreamSynchronize(st) != hipSuccess) return hip_fail(hipGetLastError());   // (A/B only: common.h)
-#endif
-      d ^= zig;
-      return lnx_cleanup_impl(ws.x, g.lnx_done, gamma, beta, ws.xh, tiles_m, d, g.lnx_epoch, st, prof);
+      d ^= zig;       // (the clean-up kernel walks the other way)
+      return resid_layernorm_gemm(g, gamma, beta, ws.xh, lnx_part, words, tower ? tower->lnx_wait : kLnxWaitDefault, d, st, prof);
     };
     bool ln1_by_gemm = false;          // ln_1 of this block was written to ws.xh by the c_proj GEMM of the block before
     for (int l = 0; l < kLayers; ++l) {

@@ -637,7 +637,7 @@ def _expected_plan(epi, amode, M, N, K, lda, ldc, chunk, cus):
     four_wave = M % 256 == 0 and N % 256 == 0 and N <= 3072 and K >= 256 and lda >= K and lda % 8 == 0 and panel
     tiles4 = (M // 256) * (N // 256)
     if epi == _LNX:
-        if not (four_wave and N == 768 and ldc == 768):
+        if not (four_wave and N == 768 and ldc == 768 and M * 768 < 2 ** 32):      # (32-bit element offsets into x)
             return refuse
         return (0, _GK["q4"], 256, 256) if cus == 256 and tiles4 > cus else persistent(_GK["q4"], N // 256, False, True)
     if chunk and (epi != _PATCH or chunk % 256 or M < 9000 or not wide3 or K < 256):
@@ -769,11 +769,35 @@ def test_gemm_selection_refusals():
     # operand panels within 32-bit byte offsets of A's base -- 14 080 images are the first slice of whole tiles beyond them
     lnx = lambda B, ldc=768: plan(_LNX, _PLAIN, 50 * B, 768, 3072, 3072, ldc, 0)[0]
     assert lnx(8704) == 0 and lnx(13824) == 0 and lnx(14080) == -1 and lnx(1000) == -1 and lnx(8704, ldc=1536) == -1
+    # ... through lla_gemm_resid_layernorm768 the kernel takes what the tower never asks of it: a single row tile, the
+    # shortest K -- and then rows enough to leave the epilogue's 32-bit element offsets into x (21 845 row tiles are the last)
+    lnx_k = lambda M, K, lda=None: plan(_LNX, _PLAIN, M, 768, K, lda or K, 768, 0)
+    assert lnx_k(256, 256) == (0, _GK["q4"], 256, 3) and lnx_k(768, 768) == (0, _GK["q4"], 256, 9)
+    assert lnx_k(21760, 256) == (0, _GK["q4"], 256, 255) and lnx_k(22016, 256) == (0, _GK["q4"], 256, 256)
+    assert lnx_k(256, 192)[0] == -1 and lnx_k(256, 256, lda=260)[0] == -1 and lnx_k(256, 256, lda=264)[0] == 0
+    assert lnx_k(256 * 21845, 256)[0] == 0 and lnx_k(256 * 21846, 256)[0] == -1
     # ... and what the eight- / four-wave kernels leave to the ping-pong kernel instead of refusing
     assert plan(_F16, _PLAIN, 12800, 3328, 768, 768, 3328, 0)[1] == _GK["pp"]                   # N > 3072
     assert plan(_RESID, _PLAIN, 12837, 768, 768, 768, 768, 0)[1] == _GK["pp"]                   # ragged M
     assert plan(_F16, _PLAIN, 1_000_000, 768, 3072, 3072, 768, 0)[1] == _GK["pp"]               # M lda 2 >= 2^32
     assert L.lla_gemm_plan(*ok, 0, None, None, None) == -1
+
+
+def test_resid_layernorm_door_decides_from_the_arguments_alone():
+    """lla_gemm_resid_layernorm768 takes what the plan takes for epi 9, N = ldc = 768, and says LLA_EINVAL to the rest before any
+    device call (there is no device here); its workspace is one 16-byte granule per row and column tile + 6 words per row tile."""
+    L = _lib.lib()
+    size = L.lla_gemm_resid_layernorm768_workspace_bytes
+    assert [size(M) for M in (-256, 0, 255, 256, 257, 768, 43776)] == [0, 0, 0, 12312, 0, 3 * 12312, 171 * 12312]
+    p = ctypes.c_void_p(1 << 20)        # (never dereferenced: every call below is refused)
+    call = lambda M, K, lda, rev=0, x=p, ws=p: L.lla_gemm_resid_layernorm768(p, lda, p, None, x, p, p, p, M, K, 24000, rev, ws, None)
+    for M, K, lda in [(0, 256, 256), (255, 256, 256), (-256, 256, 256), (256, 192, 192), (256, 288, 288), (256, 256, 248),
+                      (256, 256, 260), (256 * 21846, 256, 256), (50 * 14080, 3072, 3072)]:
+        assert call(M, K, lda) == -1, (M, K, lda)
+        assert _plan_answers(L, [(_LNX, _PLAIN, M, 768, K, lda, 768, 0)], (256,))[0][0] == (0 if M <= 0 else -1)
+    assert call(256, 256, 256, rev=2) == -1 and call(256, 256, 256, rev=-1) == -1
+    assert call(256, 256, 256, x=ctypes.c_void_p((1 << 20) + 4)) == -1 and call(256, 256, 256, x=None) == -1
+    assert call(256, 256, 256, ws=None) == -1 and call(256, 256, 256, ws=ctypes.c_void_p((1 << 20) + 8)) == -1
 
 
 _PLAN_CHILD = r"""
