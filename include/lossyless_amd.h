@@ -582,6 +582,26 @@ int lla_svm_grid_pass(const void *z, int z_dtype, int ld_z, const int32_t *y, co
                       const int32_t *col_class, const int32_t *col_held, const float *col_cpos, const float *col_cneg,
                       float *out_W, float *out_b, double *out_loss, int accumulate, void *workspace, void *stream);
 
+/* One data pass of L2-regularised multinomial logistic regression (softmax regression; CLIP's linear-probe protocol):
+ * lla_svm_pass's walk with the softmax residual in the place of the hinge's.
+ *   s_ik = z_i . W_k + b_k,  lse_i = log sum_k exp(s_ik) over the K classes,  p_ik = exp(s_ik - lse_i),
+ *   w_i = class_weight[y[i]] (class_weight [K] on the device, NULL = 1); a row whose label lies outside [0, K) has
+ *   w_i = 0 and contributes exactly nothing.
+ *   V == NULL (gradient):  r_ik = w_i (p_ik - [y_i = k]);  out_W[k] = sum_i r_ik z_i, out_b[k] = sum_i r_ik,
+ *                          out_loss[k] = sum_{i: y_i = k} w_i (lse_i - s_ik)  (the loss is their sum over k)
+ *   V != NULL (Hessian-vector):  t_ik = z_i . V_k + vb_k,  a_i = sum_k p_ik t_ik,  r_ik = w_i p_ik (t_ik - a_i);
+ *                          out_W, out_b as above, out_loss is not touched (may be NULL).
+ * The row maximum is always subtracted; expf / logf, no fast variants.  K <= 32: the row statistics are taken inside the
+ * pass (z is read once).  K > 32: a first kernel leaves lse [B] and a [B] in the workspace, which is why
+ * lla_softmax_pass_workspace_bytes takes B (the largest B of the calls that share the workspace; 0 for a refused shape).
+ * The factor C of the objective and its 1/2 |.|^2 terms are the caller's.  Shape and alignment rules, refusals
+ * (LLA_EINVAL before any device call), B == 0, accumulate, the workgroup-ordered reduction (no floating-point atomics,
+ * the loss in double, a grid that depends on (B, K) alone: the same inputs give the same bits): as lla_svm_pass. */
+size_t lla_softmax_pass_workspace_bytes(int C, int K, int B);
+int lla_softmax_pass(const void *z, int z_dtype, int ld_z, const int32_t *y, int B, int C, const float *W, const float *b,
+                     const float *V, const float *vb, int K, int ld_w, const float *class_weight, float *out_W,
+                     float *out_b, double *out_loss, int accumulate, void *workspace, void *stream);
+
 /* out[n][H][W][ldc] (first cout channels) = relu(conv3x3(in, stride 1, pad 1) + bias) as an IMPLICIT GEMM:
  * `in` is NHWC fp16 [n][H][W][pitch] (first cin channels used; cin % 64 == 0, or cin == 32), weights fp16
  * [cout][K] with K = 9 cin rounded up to a multiple of 64 (zero padded) in the order (kh, kw, c), bias fp32

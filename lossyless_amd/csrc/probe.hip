@@ -30,6 +30,17 @@
 // -- every (candidate, fold, class) of a cross-validated search over C and class_weight in the passes of one fit.  The
 // four numbers of a column live in registers next to its intercept; the weight is one multiply of the residual and of
 // the loss term in step 3, so unit weights and no fold give the bits of lla_svm_pass.
+//
+// The softmax pass (lla_softmax_pass; kSoftmax below) is the same walk for L2-regularised multinomial logistic regression
+// (CLIP's linear-probe protocol; the cross-entropy of the reference's predictors, lossyless/predictors.py:172-186):
+//   lse_i = log sum_k exp(s_ik)      p_ik = exp(s_ik - lse_i)      w_i = class_weight[y_i]  (0 for a label outside [0, K))
+//   gradient mode:        r_ik = w_i (p_ik - [y_i = k]),   out_loss[k] = sum_{i: y_i = k} w_i (lse_i - s_ik)
+//   Hessian-vector mode:  a_i = sum_k p_ik t_ik,   r_ik = w_i p_ik (t_ik - a_i)
+// Only step 3 differs, and it needs two numbers per row that couple all K classes.  K <= 32: the tile's 32 x 32 scores are
+// in LDS after step 2, so every thread reads the real classes of its row and takes max, sum and a_i itself -- K more expf
+// per thread, no barrier, no second kernel.  K > 32: softmax_rows_kernel runs first -- the same staging and the same score
+// MFMA over ALL class tiles of a row tile, a running (max, sum exp(s - max), sum exp(s - max) t) per thread over its classes,
+// merged per row at the end of the row tile -- and leaves lse[B], a[B] in the workspace for step 3 to read.
 #include "common.h"
 
 #include <hip/hip_fp16.h>
@@ -46,7 +57,12 @@ constexpr int kZPad = 4;           // floats: 16-byte reads of one column group 
 constexpr int kRPitch = kClasses + 1;
 constexpr int kResident = 512;     // workgroups the chip holds at two per CU: the grid is cut to it
 
-__host__ __device__ inline int lds_floats(int C) { return kRows * (C + kZPad) + 2 * kRows * kClasses + kRows * kRPitch; }
+enum { kHinge = 0, kGrid = 1, kSoftmax = 2 };      // what step 3 computes: lla_svm_pass, lla_svm_grid_pass, lla_softmax_pass
+
+// (the softmax pass keeps the tile's 32 b and 32 vb behind Rs)
+__host__ __device__ inline int lds_floats(int C, bool softmax = false) {
+  return kRows * (C + kZPad) + 2 * kRows * kClasses + kRows * kRPitch + (softmax ? 2 * kClasses : 0);
+}
 inline int class_tiles(int K) { return (K + kClasses - 1) / kClasses; }
 inline int walkers_max(int K) { const int w = kResident / class_tiles(K); return w < 1 ? 1 : w; }
 
@@ -59,23 +75,98 @@ struct GridCols {
   const float *col_cneg;     // [J]
 };
 
-// HV: Hessian-vector mode.  NT: 32-column tiles of the gradient slice per wave (C <= 128 NT).  GRID: the columns are
-// the problems of `cols` (K is their number J); otherwise column k is class k, nothing is held out and every weight is 1.
+// What makes a softmax pass differ: the row weights, and for K > 32 the row statistics softmax_rows_kernel left.
+struct SoftmaxRows {
+  const float *class_weight;  // [K] or NULL: every row weighs 1
+  const float *lse;           // [B]; NULL when one class tile holds all K classes: step 3 takes the statistics itself
+  const float *a;             // [B] (Hessian-vector mode)
+};
+
+// 1. rows row0 .. row0 + 31 -> Zs [32][C + kZPad] as fp32 (rows beyond B are zeros: they contribute exactly nothing)
+__device__ __forceinline__ void stage_rows(float *Zs, const void *__restrict__ z, int z_f16, int ld_z, int row0, int B,
+                                           int C, int tid) {
+  const int pitch = C + kZPad, c4n = C >> 2;
+  for (int i = tid; i < kRows * c4n; i += 256) {
+    const int row = i / c4n, c4 = i - row * c4n;
+    f32x4 v = {0.f, 0.f, 0.f, 0.f};
+    if (row0 + row < B) {
+      const size_t at = (size_t)(row0 + row) * ld_z + 4 * c4;
+      if (z_f16) {
+        const uint2 raw = *reinterpret_cast<const uint2 *>(static_cast<const __half *>(z) + at);
+        const __half2 lo = __builtin_bit_cast(__half2, raw.x), hi = __builtin_bit_cast(__half2, raw.y);
+        v = f32x4{__low2float(lo), __high2float(lo), __low2float(hi), __high2float(hi)};
+      } else {
+        v = *reinterpret_cast<const f32x4 *>(static_cast<const float *>(z) + at);
+      }
+    }
+    *reinterpret_cast<f32x4 *>(Zs + row * pitch + 4 * c4) = v;
+  }
+}
+
+// 2. scores of the staged tile against 32 classes: Sp [product][slot][32 classes][32 rows], the C dimension dealt to the
+// four waves in groups of 8 and the four partial tiles added in wave order (gradient mode leaves two slots for the reader
+// to add; HV holds two products in the same bytes).  wp / vp: this lane's row of W / V, + 4 (lane >> 5).  Ends on a barrier.
+template <bool HV>
+__device__ __forceinline__ void tile_scores(const float *Zs, float *Sp, const float *__restrict__ wp,
+                                            const float *__restrict__ vp, int C, int lane, int wid) {
+  constexpr int NSLOT = HV ? 1 : 2;
+  const int pitch = C + kZPad, ngroups = C >> 3;
+  const int r32 = lane & 31, hk = lane >> 5;
+  f32x16 s, tv;
+#pragma unroll
+  for (int r = 0; r < 16; ++r) s[r] = 0.f, tv[r] = 0.f;
+  for (int g = wid; g < ngroups; g += 4) {
+    const f32x4 a = *reinterpret_cast<const f32x4 *>(Zs + r32 * pitch + 8 * g + 4 * hk);
+    const f32x4 w = *reinterpret_cast<const f32x4 *>(wp + 8 * g);
+#pragma unroll
+    for (int j = 0; j < 4; ++j) s = __builtin_amdgcn_mfma_f32_32x32x2f32(w[j], a[j], s, 0, 0, 0);
+    if (HV) {
+      const f32x4 v = *reinterpret_cast<const f32x4 *>(vp + 8 * g);
+#pragma unroll
+      for (int j = 0; j < 4; ++j) tv = __builtin_amdgcn_mfma_f32_32x32x2f32(v[j], a[j], tv, 0, 0, 0);
+    }
+  }
+  // register r of lane l is class 8 (r >> 2) + 4 (l >> 5) + (r & 3), row l & 31
+#pragma unroll
+  for (int stage = 0; stage < 4 / NSLOT; ++stage) {
+    if (wid / NSLOT == stage) {
+      float *dst = Sp + (wid % NSLOT) * (kRows * kClasses);
+#pragma unroll
+      for (int r = 0; r < 16; ++r) {
+        const int at = (8 * (r >> 2) + 4 * hk + (r & 3)) * kRows + r32;
+        if (stage == 0) {
+          dst[at] = s[r];
+          if (HV) dst[kRows * kClasses + at] = tv[r];
+        } else {
+          dst[at] += s[r];
+          if (HV) dst[kRows * kClasses + at] += tv[r];
+        }
+      }
+    }
+    __syncthreads();
+  }
+}
+
+// HV: Hessian-vector mode.  NT: 32-column tiles of the gradient slice per wave (C <= 128 NT).  OBJ: kHinge -- column k is
+// class k, nothing is held out and every weight is 1; kGrid -- the columns are the problems of `cols` (K is their number J);
+// kSoftmax -- column k is class k and step 3 is the softmax residual of `sm`.
 // Workspace: part_W [class tile][walker][32][C], part_b / part_l [class tile][walker][32].
-template <bool HV, int NT, bool GRID>
+template <bool HV, int NT, int OBJ>
 __global__ __launch_bounds__(256) void svm_pass_kernel(const void *__restrict__ z, int z_f16, int ld_z,
                                                        const int32_t *__restrict__ y, int B, int C,
                                                        const float *__restrict__ W, const float *__restrict__ bias,
                                                        const float *__restrict__ V, const float *__restrict__ vbias,
                                                        int K, int ld_w, float *__restrict__ part_W,
                                                        float *__restrict__ part_b, float *__restrict__ part_l,
-                                                       GridCols cols) {
+                                                       GridCols cols, SoftmaxRows sm) {
   extern __shared__ __align__(16) float lds[];
   constexpr int NSLOT = HV ? 1 : 2;            // score partials kept apart in LDS (HV holds two products: same bytes)
+  constexpr bool GRID = OBJ == kGrid, SOFTMAX = OBJ == kSoftmax;
   const int pitch = C + kZPad;
   float *Zs = lds;                             // [32 rows][pitch]
   float *Sp = Zs + kRows * pitch;              // [product][slot][32 classes][32 rows]
   float *Rs = Sp + 2 * kRows * kClasses;       // [32 rows][33]
+  float *Bs = Rs + kRows * kRPitch;            // SOFTMAX: b and vb of the tile's classes, [2][32]
 
   const int tid = threadIdx.x, lane = tid & 63, wid = tid >> 6;
   const int r32 = lane & 31, hk = lane >> 5;
@@ -106,6 +197,10 @@ __global__ __launch_bounds__(256) void svm_pass_kernel(const void *__restrict__ 
     cneg[j] = (GRID && c_ok[j]) ? cols.col_cneg[c] : 0.f;
   }
   const bool folds = GRID && cols.fold != nullptr;
+  if (SOFTMAX && tid < kClasses) {             // (visible after the barrier that follows the first staging)
+    Bs[tid] = k0 + tid < K ? bias[k0 + tid] : 0.f;
+    Bs[kClasses + tid] = (HV && k0 + tid < K) ? vbias[k0 + tid] : 0.f;
+  }
 
   f32x16 acc[NT];
 #pragma unroll
@@ -115,64 +210,56 @@ __global__ __launch_bounds__(256) void svm_pass_kernel(const void *__restrict__ 
   float lacc[4] = {0.f, 0.f, 0.f, 0.f}, bacc[4] = {0.f, 0.f, 0.f, 0.f};
 
   const int ntiles = (B + kRows - 1) / kRows;
-  const int ngroups = C >> 3, c4n = C >> 2;
   for (int tile = p; tile < ntiles; tile += P) {
     const int row0 = tile * kRows;
-    // 1. stage the row tile (rows beyond B are zeros: they contribute exactly nothing)
-    for (int i = tid; i < kRows * c4n; i += 256) {
-      const int row = i / c4n, c4 = i - row * c4n;
-      f32x4 v = {0.f, 0.f, 0.f, 0.f};
-      if (row0 + row < B) {
-        const size_t at = (size_t)(row0 + row) * ld_z + 4 * c4;
-        if (z_f16) {
-          const uint2 raw = *reinterpret_cast<const uint2 *>(static_cast<const __half *>(z) + at);
-          const __half2 lo = __builtin_bit_cast(__half2, raw.x), hi = __builtin_bit_cast(__half2, raw.y);
-          v = f32x4{__low2float(lo), __high2float(lo), __low2float(hi), __high2float(hi)};
-        } else {
-          v = *reinterpret_cast<const f32x4 *>(static_cast<const float *>(z) + at);
-        }
-      }
-      *reinterpret_cast<f32x4 *>(Zs + row * pitch + 4 * c4) = v;
-    }
+    stage_rows(Zs, z, z_f16, ld_z, row0, B, C, tid);                 // 1.
     __syncthreads();
-
-    // 2. scores of the tile: this wave's column groups
-    f32x16 s, tv;
-#pragma unroll
-    for (int r = 0; r < 16; ++r) s[r] = 0.f, tv[r] = 0.f;
-    for (int g = wid; g < ngroups; g += 4) {
-      const f32x4 a = *reinterpret_cast<const f32x4 *>(Zs + r32 * pitch + 8 * g + 4 * hk);
-      const f32x4 w = *reinterpret_cast<const f32x4 *>(wp + 8 * g);
-#pragma unroll
-      for (int j = 0; j < 4; ++j) s = __builtin_amdgcn_mfma_f32_32x32x2f32(w[j], a[j], s, 0, 0, 0);
-      if (HV) {
-        const f32x4 v = *reinterpret_cast<const f32x4 *>(vp + 8 * g);
-#pragma unroll
-        for (int j = 0; j < 4; ++j) tv = __builtin_amdgcn_mfma_f32_32x32x2f32(v[j], a[j], tv, 0, 0, 0);
-      }
-    }
-    // the four partial tiles, added in wave order: register r of lane l is class 8 (r >> 2) + 4 (l >> 5) + (r & 3), row l & 31
-#pragma unroll
-    for (int stage = 0; stage < 4 / NSLOT; ++stage) {
-      if (wid / NSLOT == stage) {
-        float *dst = Sp + (wid % NSLOT) * (kRows * kClasses);
-#pragma unroll
-        for (int r = 0; r < 16; ++r) {
-          const int at = (8 * (r >> 2) + 4 * hk + (r & 3)) * kRows + r32;
-          if (stage == 0) {
-            dst[at] = s[r];
-            if (HV) dst[kRows * kClasses + at] = tv[r];
-          } else {
-            dst[at] += s[r];
-            if (HV) dst[kRows * kClasses + at] += tv[r];
-          }
-        }
-      }
-      __syncthreads();
-    }
+    tile_scores<HV>(Zs, Sp, wp, vp, C, lane, wid);                   // 2.
 
     // 3. residuals
-    {
+    if constexpr (SOFTMAX) {
+      const bool row_ok = row0 + rr < B;
+      const int yy = row_ok ? y[row0 + rr] : -1;
+      const bool live = yy >= 0 && yy < K;     // any other row weighs 0: it contributes exactly nothing
+      const float wi = live ? (sm.class_weight ? sm.class_weight[yy] : 1.f) : 0.f;
+      const auto score = [&](int cl) {         // (the additions in the order of the hinge passes)
+        float sc = Sp[cl * kRows + rr];
+        if (NSLOT == 2) sc += Sp[kRows * kClasses + cl * kRows + rr];
+        return sc + Bs[cl];
+      };
+      const auto tangent = [&](int cl) { return Sp[kRows * kClasses + cl * kRows + rr] + Bs[kClasses + cl]; };
+      float lse = 0.f, ai = 0.f;
+      if (sm.lse == nullptr) {                 // one class tile: the row's statistics from its real classes' scores in LDS
+        const int nreal = K - k0 < kClasses ? K - k0 : kClasses;
+        float mx = score(0);
+        for (int cl = 1; cl < nreal; ++cl) mx = fmaxf(mx, score(cl));
+        float se = 0.f, st = 0.f;
+        for (int cl = 0; cl < nreal; ++cl) {
+          const float e = expf(score(cl) - mx);
+          se += e;
+          if (HV) st += e * tangent(cl);
+        }
+        lse = mx + logf(se);
+        if (HV) ai = st / se;
+      } else if (row_ok) {
+        lse = sm.lse[row0 + rr];
+        if (HV) ai = sm.a[row0 + rr];
+      }
+#pragma unroll
+      for (int j = 0; j < 4; ++j) {
+        const int cl = cl0 + 8 * j;
+        const float sc = score(cl);
+        const bool own = live && yy == k0 + cl;
+        float r = 0.f;
+        if (live && c_ok[j]) {
+          const float pk = expf(sc - lse);
+          r = HV ? wi * pk * (tangent(cl) - ai) : wi * (pk - (own ? 1.f : 0.f));
+        }
+        if (!HV && own) lacc[j] += wi * (lse - sc);
+        bacc[j] += r;
+        Rs[rr * kRPitch + cl] = r;
+      }
+    } else {
       const bool row_ok = row0 + rr < B;
       const int yy = row_ok ? y[row0 + rr] : -1;
       const int ff = (folds && row_ok) ? cols.fold[row0 + rr] : 0;
@@ -244,6 +331,86 @@ __global__ __launch_bounds__(256) void svm_pass_kernel(const void *__restrict__ 
   }
 }
 
+// The row statistics of a softmax pass over more than one class tile: lse[i] = log sum_k exp(s_ik) and, in Hessian-vector
+// mode, a[i] = sum_k p_ik t_ik.  A persistent workgroup stages a row tile as step 1 does and takes the scores of every class
+// tile with the MFMA of step 2 (the same bits the pass kernel will see).  Thread (row, q) sees classes q + 8 j of every
+// tile -- at least four real ones in the first, which is full -- and keeps a running max m, sum exp(s - m) and
+// sum exp(s - m) t over them, rescaled when the max moves; classes beyond K are skipped, so m is finite from the first
+// tile on and no exponent is ever formed from two infinities.  The eight partial triples of a row are merged in the order
+// of q once per row tile.  The grid is a function of B alone.
+template <bool HV>
+__global__ __launch_bounds__(256) void softmax_rows_kernel(const void *__restrict__ z, int z_f16, int ld_z, int B, int C,
+                                                           const float *__restrict__ W, const float *__restrict__ bias,
+                                                           const float *__restrict__ V, const float *__restrict__ vbias,
+                                                           int K, int ld_w, float *__restrict__ lse,
+                                                           float *__restrict__ a) {
+  extern __shared__ __align__(16) float lds[];
+  constexpr int NSLOT = HV ? 1 : 2;
+  float *Zs = lds;
+  float *Sp = Zs + kRows * (C + kZPad);
+  const int tid = threadIdx.x, lane = tid & 63, wid = tid >> 6;
+  const int r32 = lane & 31, hk = lane >> 5;
+  const int rr = tid & 31, cl0 = tid >> 5;
+  const int nct = (K + kClasses - 1) / kClasses, ntiles = (B + kRows - 1) / kRows;
+  for (int tile = blockIdx.x; tile < ntiles; tile += gridDim.x) {
+    const int row0 = tile * kRows;
+    stage_rows(Zs, z, z_f16, ld_z, row0, B, C, tid);
+    __syncthreads();
+    float mx = -INFINITY, se = 0.f, st = 0.f;
+    for (int ct = 0; ct < nct; ++ct) {
+      const int k0 = ct * kClasses;
+      int n = k0 + r32;
+      if (n >= K) n = K - 1;
+      float bk[4], vbk[4];
+#pragma unroll
+      for (int j = 0; j < 4; ++j) {            // (asked for before the MFMAs, used after them)
+        const int c = k0 + cl0 + 8 * j;
+        bk[j] = c < K ? bias[c] : 0.f;
+        vbk[j] = (HV && c < K) ? vbias[c] : 0.f;
+      }
+      tile_scores<HV>(Zs, Sp, W + (size_t)n * ld_w + 4 * hk, HV ? V + (size_t)n * ld_w + 4 * hk : nullptr, C, lane, wid);
+      float sc[4], top = mx;
+#pragma unroll
+      for (int j = 0; j < 4; ++j) {
+        const int cl = cl0 + 8 * j;
+        sc[j] = Sp[cl * kRows + rr];
+        if (NSLOT == 2) sc[j] += Sp[kRows * kClasses + cl * kRows + rr];
+        sc[j] += bk[j];
+        if (k0 + cl < K) top = fmaxf(top, sc[j]);
+      }
+      if (top > mx) {                          // the max moved (always in the first tile): rescale what was summed under the old one
+        const float scale = expf(mx - top);   // expf(-inf) = 0 in the first tile, where se = st = 0
+        se *= scale, st *= scale, mx = top;
+      }
+#pragma unroll
+      for (int j = 0; j < 4; ++j) {
+        const int cl = cl0 + 8 * j;
+        if (k0 + cl < K) {
+          const float e = expf(sc[j] - mx);
+          se += e;
+          if (HV) st += e * (Sp[kRows * kClasses + cl * kRows + rr] + vbk[j]);
+        }
+      }
+      __syncthreads();                         // the next class tile's scores (or the merge) overwrite Sp
+    }
+    Sp[cl0 * kRows + rr] = mx, Sp[(8 + cl0) * kRows + rr] = se, Sp[(16 + cl0) * kRows + rr] = st;
+    __syncthreads();
+    if (tid < kRows && row0 + tid < B) {
+      float top = Sp[tid];
+      for (int q = 1; q < 8; ++q) top = fmaxf(top, Sp[q * kRows + tid]);
+      float sum = 0.f, sumt = 0.f;
+      for (int q = 0; q < 8; ++q) {
+        const float scale = expf(Sp[q * kRows + tid] - top);
+        sum += Sp[(8 + q) * kRows + tid] * scale;
+        if (HV) sumt += Sp[(16 + q) * kRows + tid] * scale;
+      }
+      lse[row0 + tid] = top + logf(sum);
+      if (HV) a[row0 + tid] = sumt / sum;
+    }
+    // (the next tile's staging writes Zs only, and a barrier follows it before Sp is written again)
+  }
+}
+
 // sum over walkers 0 .. P-1 of src[p * stride], added in that order; the loads go out eight at a time (a thread that
 // waited for each one before asking for the next spent 0.35 ms on 512 partial sums)
 template <typename T>
@@ -284,13 +451,16 @@ __global__ __launch_bounds__(64) void svm_reduce_kernel(const float *__restrict_
   }
 }
 
-template <bool HV, bool GRID>
+template <bool HV, int OBJ>
 const void *pass_kernel(int C) {
-  if (C <= 128) return reinterpret_cast<const void *>(&svm_pass_kernel<HV, 1, GRID>);
-  if (C <= 256) return reinterpret_cast<const void *>(&svm_pass_kernel<HV, 2, GRID>);
-  if (C <= 512) return reinterpret_cast<const void *>(&svm_pass_kernel<HV, 4, GRID>);
-  return reinterpret_cast<const void *>(&svm_pass_kernel<HV, 8, GRID>);
+  if (C <= 128) return reinterpret_cast<const void *>(&svm_pass_kernel<HV, 1, OBJ>);
+  if (C <= 256) return reinterpret_cast<const void *>(&svm_pass_kernel<HV, 2, OBJ>);
+  if (C <= 512) return reinterpret_cast<const void *>(&svm_pass_kernel<HV, 4, OBJ>);
+  return reinterpret_cast<const void *>(&svm_pass_kernel<HV, 8, OBJ>);
 }
+
+template <int OBJ>
+const void *pass_kernel(bool hv, int C) { return hv ? pass_kernel<true, OBJ>(C) : pass_kernel<false, OBJ>(C); }
 
 bool shape_ok(int C, int K) {
   return C >= 8 && C <= 1024 && (C & 7) == 0 && K >= 1 && class_tiles(K) <= 65535;
@@ -308,10 +478,12 @@ extern "C" size_t lla_svm_pass_workspace_bytes(int C, int K) {
 
 namespace {
 
-// Both entry points: the argument checks, the persistent pass and the ordered reduction.  `cols` == nullptr: lla_svm_pass.
-int svm_pass_launch(const void *z, int z_dtype, int ld_z, const int32_t *y, int B, int C, const float *W, const float *b,
-                    const float *V, const float *vb, int K, int ld_w, const GridCols *cols, float *out_W, float *out_b,
-                    double *out_loss, int accumulate, void *workspace, void *stream) {
+// The three entry points: the argument checks, (softmax over several class tiles: the row statistics,) the persistent pass
+// and the ordered reduction.  obj kHinge: lla_svm_pass; kGrid: `cols`; kSoftmax: `class_weight` (NULL = 1).
+int svm_pass_launch(int obj, const void *z, int z_dtype, int ld_z, const int32_t *y, int B, int C, const float *W,
+                    const float *b, const float *V, const float *vb, int K, int ld_w, const GridCols *cols,
+                    const float *class_weight, float *out_W, float *out_b, double *out_loss, int accumulate,
+                    void *workspace, void *stream) {
   if (!shape_ok(C, K) || B < 0 || ld_z < C || ld_w < C || (ld_z & 3) || (ld_w & 3) ||
       (z_dtype != LLA_Z_F32 && z_dtype != LLA_Z_F16))
     return LLA_EINVAL;
@@ -331,15 +503,29 @@ int svm_pass_launch(const void *z, int z_dtype, int ld_z, const int32_t *y, int 
   float *part_l = part_b + (size_t)nct * walkers_max(K) * kClasses;
   hipStream_t st = as_stream(stream);
   if (P > 0) {
-    const void *kernel = cols ? (V ? pass_kernel<true, true>(C) : pass_kernel<false, true>(C))
-                              : (V ? pass_kernel<true, false>(C) : pass_kernel<false, false>(C));
-    const size_t lds_bytes = (size_t)lds_floats(C) * sizeof(float);
+    const void *kernel = obj == kSoftmax ? pass_kernel<kSoftmax>(V != nullptr, C)
+                                         : obj == kGrid ? pass_kernel<kGrid>(V != nullptr, C) : pass_kernel<kHinge>(V != nullptr, C);
+    const size_t lds_bytes = (size_t)lds_floats(C, obj == kSoftmax) * sizeof(float);
     if (lds_bytes > dynamic_lds_limit(kernel)) return LLA_ECAP;
     const int z_f16 = z_dtype == LLA_Z_F16;
     GridCols gc = cols ? *cols : GridCols{nullptr, nullptr, nullptr, nullptr, nullptr};
+    SoftmaxRows sm = {class_weight, nullptr, nullptr};
+    if (obj == kSoftmax && nct > 1) {          // lse [B], a [B] behind the partial sums
+      float *lse = part_l + (size_t)nct * walkers_max(K) * kClasses, *a = lse + B;
+      const void *rows_kernel = V ? reinterpret_cast<const void *>(&softmax_rows_kernel<true>)
+                                  : reinterpret_cast<const void *>(&softmax_rows_kernel<false>);
+      const size_t rows_lds = (size_t)lds_floats(C) * sizeof(float);
+      if (rows_lds > dynamic_lds_limit(rows_kernel)) return LLA_ECAP;
+      void *rows_args[] = {(void *)&z, (void *)&z_f16, (void *)&ld_z, (void *)&B, (void *)&C, (void *)&W, (void *)&b,
+                           (void *)&V, (void *)&vb, (void *)&K, (void *)&ld_w, (void *)&lse, (void *)&a};
+      hipError_t e = hipLaunchKernel(rows_kernel, dim3(ntiles < kResident ? ntiles : kResident), dim3(256), rows_args,
+                                     rows_lds, st);
+      if (e != hipSuccess) return hip_fail(e);
+      sm.lse = lse, sm.a = a;
+    }
     void *args[] = {(void *)&z, (void *)&z_f16, (void *)&ld_z, (void *)&y, (void *)&B, (void *)&C, (void *)&W, (void *)&b,
                     (void *)&V, (void *)&vb, (void *)&K, (void *)&ld_w, (void *)&part_W, (void *)&part_b, (void *)&part_l,
-                    (void *)&gc};
+                    (void *)&gc, (void *)&sm};
     hipError_t e = hipLaunchKernel(kernel, dim3(P, nct), dim3(256), args, lds_bytes, st);
     if (e != hipSuccess) return hip_fail(e);
   }
@@ -354,8 +540,8 @@ int svm_pass_launch(const void *z, int z_dtype, int ld_z, const int32_t *y, int 
 extern "C" int lla_svm_pass(const void *z, int z_dtype, int ld_z, const int32_t *y, int B, int C, const float *W,
                             const float *b, const float *V, const float *vb, int K, int ld_w, float *out_W, float *out_b,
                             double *out_loss, int accumulate, void *workspace, void *stream) {
-  return svm_pass_launch(z, z_dtype, ld_z, y, B, C, W, b, V, vb, K, ld_w, nullptr, out_W, out_b, out_loss, accumulate,
-                         workspace, stream);
+  return svm_pass_launch(kHinge, z, z_dtype, ld_z, y, B, C, W, b, V, vb, K, ld_w, nullptr, nullptr, out_W, out_b, out_loss,
+                         accumulate, workspace, stream);
 }
 
 // The grid is the one lla_svm_pass launches for K = J: a function of (B, J) alone.
@@ -367,6 +553,19 @@ extern "C" int lla_svm_grid_pass(const void *z, int z_dtype, int ld_z, const int
                                  const float *col_cneg, float *out_W, float *out_b, double *out_loss, int accumulate,
                                  void *workspace, void *stream) {
   const GridCols cols = {fold, col_class, col_held, col_cpos, col_cneg};
-  return svm_pass_launch(z, z_dtype, ld_z, y, B, C, W, b, V, vb, J, ld_w, &cols, out_W, out_b, out_loss, accumulate,
-                         workspace, stream);
+  return svm_pass_launch(kGrid, z, z_dtype, ld_z, y, B, C, W, b, V, vb, J, ld_w, &cols, nullptr, out_W, out_b, out_loss,
+                         accumulate, workspace, stream);
+}
+
+// The partial sums of lla_svm_pass, then lse [B] and a [B] when the classes span more than one tile.
+extern "C" size_t lla_softmax_pass_workspace_bytes(int C, int K, int B) {
+  if (!shape_ok(C, K) || B < 0) return 0;
+  return lla_svm_pass_workspace_bytes(C, K) + (class_tiles(K) > 1 ? 2 * (size_t)B * sizeof(float) : 0);
+}
+
+extern "C" int lla_softmax_pass(const void *z, int z_dtype, int ld_z, const int32_t *y, int B, int C, const float *W,
+                                const float *b, const float *V, const float *vb, int K, int ld_w, const float *class_weight,
+                                float *out_W, float *out_b, double *out_loss, int accumulate, void *workspace, void *stream) {
+  return svm_pass_launch(kSoftmax, z, z_dtype, ld_z, y, B, C, W, b, V, vb, K, ld_w, nullptr, class_weight, out_W, out_b,
+                         out_loss, accumulate, workspace, stream);
 }

@@ -22,6 +22,9 @@ What a pass walks is a set of J *problems* (:class:`_Problems`), not K classes: 
 rest on the rows outside one held-out fold, with liblinear's class weights (``C w[k]`` for the rows of class k, ``C`` for
 the others).  A plain fit is K problems with nothing held out; :class:`LinearProbeCV` lays every (candidate, fold, class)
 of a search over ``C`` and ``class_weight`` side by side and solves them in the same passes (``lla_svm_grid_pass``).
+
+:class:`LogisticProbe` is the softmax-regression sibling: one problem that couples all classes (``lla_softmax_pass``, a
+joint Newton-CG), over the same walk of the rows and the same scoring path.
 """
 import warnings
 
@@ -360,7 +363,75 @@ def _labels_of(data, labels, n):
     return y.to(torch.int64)
 
 
-class LinearProbe:
+class _Scores:
+    """Scoring shared by the probes: ``coef_`` [K, C] and ``intercept_`` [K] against the rows of a fit / predict call."""
+
+    coef_ = intercept_ = classes_ = None
+
+    def _set(self, W, b, classes, n_passes, objective, converged):
+        self.coef_, self.intercept_ = W.to(torch.float32), b.to(torch.float32)
+        self.classes_ = classes.numpy()
+        self.n_passes_, self.objective_, self.converged_ = n_passes, objective, converged
+        self._packed = None
+
+    def _pack(self, dev):
+        """Padded device copies of the weights for ``lla_gemm_f32`` (as ``MLP._pack``): fp32 [Npad8][C], bias [Npad8]."""
+        if self._packed is None or self._packed[0] != str(dev):
+            K, C = self.coef_.shape
+            npad = -(-K // 8) * 8
+            w = torch.zeros((npad, C), dtype=torch.float32, device=dev)
+            w[:K] = self.coef_.to(dev)
+            b = torch.zeros(npad, dtype=torch.float32, device=dev)
+            b[:K] = self.intercept_.to(dev)
+            self._packed = (str(dev), w, b, npad)
+        return self._packed[1:]
+
+    def _scores(self, data, rows_per_pass):
+        """-> [N, K]: fp32 from ``lla_gemm_f32`` on the device, float64 on the CPU."""
+        if self.coef_ is None:
+            raise RuntimeError("fit first")
+        rows = _Rows(data, rows_per_pass, False)
+        rows.first_pass = _is_latents(data)       # (statuses of a decode are checked; tensors are taken as they are)
+        K, C = self.coef_.shape
+        if rows.dim != C:
+            raise ValueError(f"data has {rows.dim} features, the probe was fitted on {C}")
+        try:
+            if rows.device.type == "cuda":
+                if C % 8:
+                    raise ValueError("the device path needs a feature width that is a multiple of 8")
+                w, b, npad = self._pack(rows.device)
+                out = torch.empty((rows.n, npad), dtype=torch.float32, device=rows.device)
+                L = _lib.lib()
+                with torch.cuda.device(rows.device):
+                    for g0, z in rows.groups():
+                        z = z if z.dtype == torch.float32 else z.float()
+                        z = z if z.stride(1) == 1 and z.stride(0) % 4 == 0 else z.contiguous()
+                        g = int(z.shape[0])
+                        o = out[g0:g0 + g]
+                        rc = L.lla_gemm_f32(_lib.ptr(z), int(z.stride(0)) if g > 1 else C, _lib.ptr(w), C, _lib.ptr(b),
+                                            _lib.ptr(o), npad, g, npad, C, 0, _lib.stream_ptr(rows.device))
+                        _lib.check(rc, "lla_gemm_f32")
+                s = out[:, :K]
+            else:
+                W, b = self.coef_.to(torch.float64).cpu(), self.intercept_.to(torch.float64).cpu()
+                s = torch.cat([z.to(torch.float64) @ W.T + b for _, z in rows.groups()]) if rows.n else \
+                    torch.zeros((0, K), dtype=torch.float64)
+        finally:
+            rows.close()
+        return s
+
+    def predict(self, data, rows_per_pass=65536):
+        s = self.decision_function(data, rows_per_pass)
+        which = (s > 0).to(torch.int64) if s.dim() == 1 else s.argmax(1)
+        return torch.from_numpy(self.classes_).to(s.device)[which]
+
+    def score(self, data, labels=None, rows_per_pass=65536):
+        pred = self.predict(data, rows_per_pass)
+        y = _labels_of(data, labels, pred.numel()).to(pred.device)
+        return float((pred == y).double().mean())
+
+
+class LinearProbe(_Scores):
     """``LinearProbe(C=7e-3, tol=1e-4, max_iter=100, class_weight=None)``: scikit-learn's ``LinearSVC(C)`` objective (its
     defaults: squared hinge, L2, one-vs-rest, regularised intercept), solved where the data lives.  ``class_weight`` is
     ``LinearSVC``'s: ``None``, ``"balanced"`` (``n / (K count_k)``) or a ``{label: weight}`` dict (labels left out weigh 1);
@@ -407,67 +478,10 @@ class LinearProbe:
             warnings.warn(f"LinearProbe stopped short of tol = {self.tol} after {self.max_iter} Newton steps", RuntimeWarning)
         return self
 
-    def _set(self, W, b, classes, n_passes, objective, converged):
-        self.coef_, self.intercept_ = W.to(torch.float32), b.to(torch.float32)
-        self.classes_ = classes.numpy()
-        self.n_passes_, self.objective_, self.converged_ = n_passes, objective, converged
-        self._packed = None
-
     # ------------------------------------------------------------------ predict
-    def _pack(self, dev):
-        """Padded device copies of the weights for ``lla_gemm_f32`` (as ``MLP._pack``): fp32 [Npad8][C], bias [Npad8]."""
-        if self._packed is None or self._packed[0] != str(dev):
-            K, C = self.coef_.shape
-            npad = -(-K // 8) * 8
-            w = torch.zeros((npad, C), dtype=torch.float32, device=dev)
-            w[:K] = self.coef_.to(dev)
-            b = torch.zeros(npad, dtype=torch.float32, device=dev)
-            b[:K] = self.intercept_.to(dev)
-            self._packed = (str(dev), w, b, npad)
-        return self._packed[1:]
-
     def decision_function(self, data, rows_per_pass=65536):
-        if self.coef_ is None:
-            raise RuntimeError("fit first")
-        rows = _Rows(data, rows_per_pass, False)
-        rows.first_pass = _is_latents(data)       # (statuses of a decode are checked; tensors are taken as they are)
-        K, C = self.coef_.shape
-        if rows.dim != C:
-            raise ValueError(f"data has {rows.dim} features, the probe was fitted on {C}")
-        try:
-            if rows.device.type == "cuda":
-                if C % 8:
-                    raise ValueError("the device path needs a feature width that is a multiple of 8")
-                w, b, npad = self._pack(rows.device)
-                out = torch.empty((rows.n, npad), dtype=torch.float32, device=rows.device)
-                L = _lib.lib()
-                with torch.cuda.device(rows.device):
-                    for g0, z in rows.groups():
-                        z = z if z.dtype == torch.float32 else z.float()
-                        z = z if z.stride(1) == 1 and z.stride(0) % 4 == 0 else z.contiguous()
-                        g = int(z.shape[0])
-                        o = out[g0:g0 + g]
-                        rc = L.lla_gemm_f32(_lib.ptr(z), int(z.stride(0)) if g > 1 else C, _lib.ptr(w), C, _lib.ptr(b),
-                                            _lib.ptr(o), npad, g, npad, C, 0, _lib.stream_ptr(rows.device))
-                        _lib.check(rc, "lla_gemm_f32")
-                s = out[:, :K]
-            else:
-                W, b = self.coef_.to(torch.float64).cpu(), self.intercept_.to(torch.float64).cpu()
-                s = torch.cat([z.to(torch.float64) @ W.T + b for _, z in rows.groups()]) if rows.n else \
-                    torch.zeros((0, K), dtype=torch.float64)
-        finally:
-            rows.close()
+        s = self._scores(data, rows_per_pass)
         return s[:, 0].contiguous() if len(self.classes_) == 2 else s.contiguous()
-
-    def predict(self, data, rows_per_pass=65536):
-        s = self.decision_function(data, rows_per_pass)
-        which = (s > 0).to(torch.int64) if s.dim() == 1 else s.argmax(1)
-        return torch.from_numpy(self.classes_).to(s.device)[which]
-
-    def score(self, data, labels=None, rows_per_pass=65536):
-        pred = self.predict(data, rows_per_pass)
-        y = self._labels_of(data, labels, pred.numel()).to(pred.device)
-        return float((pred == y).double().mean())
 
 
 class LinearProbeCV:
@@ -646,3 +660,251 @@ class LinearProbeCV:
             for g0, z in rows.groups():
                 count(z.to(torch.float64) @ W64.T + b64, g0)
         return right.cpu()
+
+
+# ---------------------------------------------------------------------- softmax regression
+_HOST_BLOCK = 4096       # rows per evaluation of the float64 twin, whatever rows_per_pass is
+
+
+class _HostSoftmaxSums:
+    """float64 torch evaluation of the two quantities ``lla_softmax_pass`` computes, times C (the CPU path; the GPU tests'
+    oracle).  The rows are evaluated in blocks of ``_HOST_BLOCK`` cut from the walk's groups, so the bits do not depend
+    on ``rows_per_pass``."""
+    dtype = torch.float64
+    slack = 1e-14
+
+    def __init__(self, rows, idx, cw, C):
+        self.rows, self.idx, self.cw, self.C = rows, idx, cw.to(torch.float64), float(C)
+        self.K = int(cw.numel())
+        self.cmax = self.C * float(cw.max())
+        self.n_passes = 0
+
+    def _blocks(self):
+        """-> (first row, float64 rows [<= _HOST_BLOCK, C]) in file order, the same cuts for every grouping of the walk."""
+        held, n_held, at = [], 0, 0
+        for _, z in self.rows.groups():
+            held.append(z.to(torch.float64))
+            n_held += z.shape[0]
+            while n_held >= _HOST_BLOCK:
+                z = torch.cat(held) if len(held) > 1 else held[0]
+                yield at, z[:_HOST_BLOCK]
+                at, n_held = at + _HOST_BLOCK, n_held - _HOST_BLOCK
+                held = [z[_HOST_BLOCK:]] if n_held else []
+        if n_held:
+            yield at, (torch.cat(held) if len(held) > 1 else held[0])
+
+    def _rows_of(self, g0, z, W, b):
+        """-> (scores, lse [g, 1], p, w_i [g, 1], one-hot labels) of the block."""
+        y = self.idx[g0:g0 + z.shape[0]]
+        s = z @ W.T + b
+        lse = torch.logsumexp(s, 1, keepdim=True)
+        hot = torch.zeros_like(s).scatter_(1, y[:, None], 1.0)
+        return s, lse, torch.exp(s - lse), self.cw[y][:, None], hot
+
+    def column_squares(self):
+        sq = torch.zeros(self.rows.dim, dtype=torch.float64)
+        for _, z in self._blocks():
+            sq += (z ** 2).sum(0)
+        self.n_passes += 1
+        return sq
+
+    def gradient(self, W, b):
+        loss, gW, gb = torch.zeros((), dtype=torch.float64), torch.zeros_like(W), torch.zeros_like(b)
+        for g0, z in self._blocks():
+            s, lse, p, w, hot = self._rows_of(g0, z, W, b)
+            r = w * (p - hot)
+            loss += (w * (lse - (s * hot).sum(1, keepdim=True))).sum()
+            gW += r.T @ z
+            gb += r.sum(0)
+        self.n_passes += 1
+        return self.C * loss, self.C * gW, self.C * gb
+
+    def hessian_vector(self, W, b, V, vb):
+        hW, hb = torch.zeros_like(W), torch.zeros_like(b)
+        for g0, z in self._blocks():
+            _, _, p, w, _ = self._rows_of(g0, z, W, b)
+            t = z @ V.T + vb
+            r = w * p * (t - (p * t).sum(1, keepdim=True))
+            hW += r.T @ z
+            hb += r.sum(0)
+        self.n_passes += 1
+        return self.C * hW, self.C * hb
+
+
+class _DeviceSoftmaxSums:
+    """The same two quantities from ``lla_softmax_pass``, one call per decode group, accumulated on the device."""
+    dtype = torch.float32
+    slack = _DeviceSums.slack
+
+    def __init__(self, rows, idx, cw, C):
+        dim, dev = rows.dim, rows.device
+        if dim % 8 or not 8 <= dim <= 1024:
+            raise ValueError(f"the device probe needs a feature width that is a multiple of 8 in [8, 1024], got {dim}")
+        self.rows, self.dim, self.device, self.C = rows, dim, dev, float(C)
+        self.K = int(cw.numel())
+        self.cmax = self.C * float(cw.max())
+        self.y = idx.to(torch.int32).to(dev).contiguous()
+        self.cw = None if bool((cw == 1).all()) else cw.to(torch.float32).to(dev)
+        self.L = _lib.lib()
+        nbytes = int(self.L.lla_softmax_pass_workspace_bytes(dim, self.K, min(rows.group, max(rows.n, 1))))
+        if nbytes == 0:
+            raise ValueError(f"lla_softmax_pass refuses C = {dim}, K = {self.K}")
+        self.ws = torch.empty(nbytes, dtype=torch.uint8, device=dev)
+        self.n_passes = 0
+
+    def _pass(self, W, b, V, vb):
+        K, C = self.K, self.dim
+        oW = torch.zeros((K, C), dtype=torch.float32, device=self.device)
+        ob = torch.zeros(K, dtype=torch.float32, device=self.device)
+        loss = torch.zeros(K, dtype=torch.float64, device=self.device) if V is None else None
+        with torch.cuda.device(self.device):
+            st = _lib.stream_ptr(self.device)
+            for g0, z in self.rows.groups():
+                g = int(z.shape[0])
+                zt = _lib.LLA_Z_F16 if z.dtype == torch.float16 else _lib.LLA_Z_F32
+                rc = self.L.lla_softmax_pass(_lib.ptr(z), zt, int(z.stride(0)) if g > 1 else C, _lib.ptr(self.y[g0:g0 + g]), g, C,
+                                             _lib.ptr(W), _lib.ptr(b), _lib.ptr(V), _lib.ptr(vb), K, C, _lib.ptr(self.cw),
+                                             _lib.ptr(oW), _lib.ptr(ob), _lib.ptr(loss), 1, _lib.ptr(self.ws), st)
+                _lib.check(rc, "lla_softmax_pass")
+        self.n_passes += 1
+        return (None if loss is None else self.C * loss.sum()), self.C * oW, self.C * ob
+
+    def column_squares(self):
+        sq = torch.zeros(self.dim, dtype=torch.float64, device=self.device)
+        for _, z in self.rows.groups():
+            sq += (z.float() ** 2).sum(0, dtype=torch.float64)
+        self.n_passes += 1
+        return sq
+
+    def gradient(self, W, b):
+        return self._pass(W.contiguous(), b.contiguous(), None, None)
+
+    def hessian_vector(self, W, b, V, vb):
+        return self._pass(W.contiguous(), b.contiguous(), V.contiguous(), vb.contiguous())[1:]
+
+
+def _newton_cg_joint(sums, dim, n_rows, device, tol, max_iter):
+    """Truncated Newton-CG on ONE problem over the whole [K, C + 1] array -- the softmax couples the classes, so every
+    inner product, step length and stopping rule is taken over all of them: f = 1/2 (|W|^2 + |b|^2) + C (weighted
+    cross-entropy) -> (W, b, f float64, converged bool).  Stops once the gradient's sup norm is within ``tol`` of the one
+    at 0.  One host synchronisation per CG iteration and per line-search step."""
+    dt, K = sums.dtype, sums.K
+    W, b = torch.zeros((K, dim), dtype=dt, device=device), torch.zeros(K, dtype=dt, device=device)
+
+    def evaluate(W, b):
+        loss, gW, gb = sums.gradient(W, b)
+        return 0.5 * ((W.double() ** 2).sum() + (b.double() ** 2).sum()) + loss, W + gW, b + gb
+
+    def dot(aW, ab, cW, cb):
+        return (aW * cW).sum() + (ab * cb).sum()
+
+    def sup(gW, gb):
+        return float(torch.maximum(gW.abs().max(), gb.abs().max()))
+
+    # Jacobi preconditioner: the Hessian's diagonal is 1 + C sum_i w_i p_ik (1 - p_ik) z_ic^2 and p (1 - p) <= 1/4, so
+    # 1 + C / 4 max(w) sum_i z_ic^2 bounds it for every class and every iterate (the intercept's column is all ones)
+    mW = (1.0 + 0.25 * sums.cmax * sums.column_squares()[None, :]).to(dt)
+    mb = torch.full((K,), 1.0 + 0.25 * sums.cmax * n_rows, dtype=dt, device=device)
+    f, gW, gb = evaluate(W, b)
+    stop_at = tol * sup(gW, gb)
+    for _ in range(int(max_iter)):
+        if sup(gW, gb) <= stop_at:
+            break
+        # preconditioned CG on H d = -g, H v = v + C (Hessian-vector pass)(v), until |H d + g|_2 <= 0.1 |g|_2
+        dW, db = torch.zeros_like(W), torch.zeros_like(b)
+        rW, rb = -gW, -gb
+        yW, yb = rW / mW, rb / mb
+        pW, pb = yW.clone(), yb.clone()
+        rs = dot(rW, rb, yW, yb)
+        stop = _CG_TOL ** 2 * float(dot(rW, rb, rW, rb))
+        for _cg in range(_CG_MAX):
+            hW, hb = sums.hessian_vector(W, b, pW, pb)
+            hW, hb = pW + hW, pb + hb
+            alpha = rs / dot(pW, pb, hW, hb).clamp_min(torch.finfo(dt).tiny)
+            dW += alpha * pW
+            db += alpha * pb
+            rW -= alpha * hW
+            rb -= alpha * hb
+            if float(dot(rW, rb, rW, rb)) <= stop:
+                break
+            yW, yb = rW / mW, rb / mb
+            rs2 = dot(rW, rb, yW, yb)
+            beta = rs2 / rs.clamp_min(torch.finfo(dt).tiny)
+            pW, pb = yW + beta * pW, yb + beta * pb
+            rs = rs2
+        # backtracking until the Armijo condition holds (fp32 sums: with the slack of the per-class solver)
+        gd = float(dot(gW, gb, dW, db))
+        t = 1.0
+        for _ls in range(_BACKTRACKS):
+            W2, b2 = W + t * dW, b + t * db
+            f2, gW2, gb2 = evaluate(W2, b2)
+            if float(f2) <= float(f) + _ARMIJO * t * gd + sums.slack * abs(float(f)):
+                break
+            t *= 0.5
+        else:                            # no step passed: rounding has the last word
+            break
+        W, b, f, gW, gb = W2, b2, f2, gW2, gb2
+    return W, b, f, sup(gW, gb) <= stop_at
+
+
+class LogisticProbe(_Scores):
+    """``LogisticProbe(C=1.0, tol=1e-4, max_iter=100, class_weight=None)``: L2-regularised multinomial logistic regression
+    (softmax regression, CLIP's own linear-probe protocol; the cross-entropy the reference's predictors minimise), solved
+    where the data lives, from what ``LinearProbe.fit`` takes:
+
+        f(W, b) = 1/2 (|W|^2 + |b|^2) + C sum_i w_i (lse_i - s_{i, y_i}),   s_ik = z_i . W_k + b_k,  lse_i = log sum_k exp(s_ik)
+
+    The intercept is regularised as one more feature, as ``LinearProbe`` does: this is scikit-learn's
+    ``LogisticRegression(C, fit_intercept=False)`` on ``[Z, 1]``, and f is 1-strongly convex.  ``class_weight`` is
+    ``None``, ``"balanced"`` (``n / (K count_k)``) or a ``{label: weight}`` dict, and weighs the ROW: ``w_i = cw[y_i]``
+    (scikit-learn's semantics for this estimator).  Two classes are scikit-learn's one binomial problem
+    ``1/2 |w|^2 + C sum_i w_i log(1 + exp(-y_i s_i))``: the K = 2 softmax is solved with C / 2 and ``coef_ = W_1 - W_0``.
+
+    ``fit(data, labels=None, rows_per_pass=65536, keep_rows=False)`` as ``LinearProbe.fit``; a pass hands each decode group
+    to ``lla_softmax_pass`` (csrc/probe.hip).  The solver is one truncated Newton-CG over all classes (Jacobi
+    preconditioner, Armijo backtracking), deterministic; it stops when ``|grad f|_inf <= tol |grad f(0)|_inf``, and warns
+    and sets ``converged_ = False`` at ``max_iter`` Newton steps.  CPU data run a float64 torch evaluation of the same sums.
+
+    After ``fit``: ``coef_`` fp32 ``[K, C]`` (``[1, C]`` for two classes, positive class ``classes_[1]``), ``intercept_``,
+    ``classes_``, ``n_passes_``, ``objective_`` (f at the solution; the binomial objective for two classes),
+    ``converged_``.  ``decision_function`` returns ``[N, K]`` (``[N]`` for two classes) through ``lla_gemm_f32`` on the
+    device; ``predict_proba`` its softmax (the sigmoid for two classes: columns ``classes_[0]``, ``classes_[1]``);
+    ``predict`` labels, ``score`` the mean accuracy."""
+
+    def __init__(self, C=1.0, tol=1e-4, max_iter=100, class_weight=None):
+        if not C > 0 or not tol > 0 or int(max_iter) < 1:
+            raise ValueError("C and tol must be positive, max_iter at least 1")
+        if not (class_weight is None or class_weight == "balanced" or isinstance(class_weight, dict)):
+            raise ValueError(f"class_weight must be None, 'balanced' or a dict, got {class_weight!r}")
+        self.C, self.tol, self.max_iter, self.class_weight = float(C), float(tol), int(max_iter), class_weight
+
+    def fit(self, data, labels=None, rows_per_pass=65536, keep_rows=False):
+        rows = _Rows(data, rows_per_pass, keep_rows)
+        y = _labels_of(data, labels, rows.n)
+        classes, _, _ = _class_indexes(y)
+        idx = torch.searchsorted(classes, y)                  # class k is classes_[k], for two classes too
+        K = int(classes.numel())
+        cw = _class_weights(self.class_weight, classes.numpy(), torch.bincount(idx, minlength=K))
+        try:
+            Sums = _DeviceSoftmaxSums if rows.device.type == "cuda" else _HostSoftmaxSums
+            sums = Sums(rows, idx, cw, self.C / 2 if K == 2 else self.C)
+            W, b, f, converged = _newton_cg_joint(sums, rows.dim, rows.n, rows.device, self.tol, self.max_iter)
+        finally:
+            rows.close()
+        if K == 2:                       # from zero the solution is symmetric (W_0 = -W_1): w = W_1 - W_0 minimises the binomial f
+            W, b, f = W[1:] - W[:1], b[1:] - b[:1], 2.0 * f
+        self._set(W, b, classes, sums.n_passes, float(f), bool(converged))
+        if not self.converged_:
+            warnings.warn(f"LogisticProbe stopped short of tol = {self.tol} after {self.max_iter} Newton steps", RuntimeWarning)
+        return self
+
+    def decision_function(self, data, rows_per_pass=65536):
+        s = self._scores(data, rows_per_pass)
+        return s[:, 0].contiguous() if len(self.classes_) == 2 else s.contiguous()
+
+    def predict_proba(self, data, rows_per_pass=65536):
+        s = self.decision_function(data, rows_per_pass)
+        if s.dim() == 1:
+            p = torch.sigmoid(s)
+            return torch.stack([1.0 - p, p], 1)
+        return torch.softmax(s, 1)

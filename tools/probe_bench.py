@@ -25,8 +25,17 @@ both with the rows resident and streamed (``take`` of the rows a call needs, the
 than the spread of (s)'s own runs, resident and streamed.  Reported, not gated: wall time of ``LinearProbeCV.fit`` at the
 STL10 shape against the same search as a loop of ``LinearProbe.fit``.
 
+``--softmax`` measures the softmax-regression pass instead, at K = 10 (the row statistics inside the
+pass) and K = 1000 (the row-statistics kernel first), in gradient and in Hessian-vector mode:
+
+(a)  one ``lla_softmax_pass`` over the N resident rows,
+(c)  ``lla_gemm_f32`` for the scores (and for t), torch ``log_softmax`` and elementwise ops, ``R.T @ Z`` and ``R.sum(0)``,
+(a') streamed: ``take`` of a decode group, then ``lla_softmax_pass(accumulate=1)``, against the ``take`` calls alone.
+Bar, as above: the median of (a) may not exceed the median of (c) by more than the spread of (c)'s own runs.
+
 usage (GPU box): python tools/probe_bench.py [--records 131072] [--reps 3] [--out profiles/linear_probe.txt]
                  python tools/probe_bench.py --grid --out profiles/linear_probe_cv.txt
+                 python tools/probe_bench.py --softmax --out profiles/logistic_probe.txt
 """
 import argparse
 import os
@@ -41,7 +50,7 @@ import torch  # noqa: E402
 
 import hubconf  # noqa: E402
 from latents_bench import interleaved, med  # noqa: E402
-from lossyless_amd import LinearProbe, LinearProbeCV, _lib  # noqa: E402
+from lossyless_amd import LinearProbe, LinearProbeCV, LogisticProbe, _lib  # noqa: E402
 
 
 def grid_arms(args, say, dev, ds, Z, g):
@@ -181,12 +190,127 @@ def grid_arms(args, say, dev, ds, Z, g):
         f"{float((scores - cv.cv_scores_).abs().max()):.4f}   (reported, not gated)")
 
 
+def softmax_arms(args, say, dev, ds, Z, g):
+    """The --softmax table (module docstring)."""
+    L, st = _lib.lib(), _lib.stream_ptr(dev)
+    N, C = Z.shape
+    group = 65536
+    buf = torch.empty((min(group, N), C), dtype=torch.float32, device=dev)
+    idxs = [(g0, torch.arange(g0, min(g0 + group, N), device=dev)) for g0 in range(0, N, group)]
+    for K in (10, 1000):
+        inner = args.inner or (40 if K <= 32 else 8)
+        y = torch.randint(0, K, (N,), generator=g).to(torch.int32).to(dev)
+        y64 = y.to(torch.int64)
+        W = (torch.randn(K, C, generator=g) * 0.03).to(dev)
+        b = (torch.randn(K, generator=g) * 0.1).to(dev)
+        V = (torch.randn(K, C, generator=g) * 0.03).to(dev)
+        vb = (torch.randn(K, generator=g) * 0.1).to(dev)
+        cw = (0.5 + torch.rand(K, generator=g)).to(dev)
+        ws = torch.empty(int(L.lla_softmax_pass_workspace_bytes(C, K, N)), dtype=torch.uint8, device=dev)
+        oW, ob = torch.empty((K, C), device=dev), torch.empty(K, device=dev)
+        ol = torch.empty(K, dtype=torch.float64, device=dev)
+        npad = -(-K // 8) * 8
+        Wp, bp = torch.zeros((npad, C), device=dev), torch.zeros(npad, device=dev)
+        Vp, vbp = torch.zeros((npad, C), device=dev), torch.zeros(npad, device=dev)
+        Wp[:K], bp[:K], Vp[:K], vbp[:K] = W, b, V, vb
+        S, T = torch.empty((N, npad), device=dev), torch.empty((N, npad), device=dev)
+        wi = cw[y64][:, None]
+        for hv in (False, True):
+            Vm, vbm = (V, vb) if hv else (None, None)
+            parts = {}
+
+            def fused(rows=Z, labels=y, acc=0):
+                rc = L.lla_softmax_pass(_lib.ptr(rows), _lib.LLA_Z_F32, C, _lib.ptr(labels), rows.shape[0], C, _lib.ptr(W),
+                                        _lib.ptr(b), _lib.ptr(Vm), _lib.ptr(vbm), K, C, _lib.ptr(cw), _lib.ptr(oW), _lib.ptr(ob),
+                                        _lib.ptr(ol), acc, _lib.ptr(ws), st)
+                _lib.check(rc, "lla_softmax_pass")
+
+            def from_parts():
+                rc = L.lla_gemm_f32(_lib.ptr(Z), C, _lib.ptr(Wp), C, _lib.ptr(bp), _lib.ptr(S), npad, N, npad, C, 0, st)
+                _lib.check(rc, "lla_gemm_f32")
+                logp = torch.log_softmax(S[:, :K], 1)
+                if hv:
+                    rc = L.lla_gemm_f32(_lib.ptr(Z), C, _lib.ptr(Vp), C, _lib.ptr(vbp), _lib.ptr(T), npad, N, npad, C, 0, st)
+                    _lib.check(rc, "lla_gemm_f32")
+                    pk, t = logp.exp(), T[:, :K]
+                    R = wi * pk * (t - (pk * t).sum(1, keepdim=True))
+                else:
+                    R = logp.exp()
+                    R[torch.arange(N, device=dev), y64] -= 1.0
+                    R *= wi
+                    parts["loss"] = -(wi[:, 0] * logp[torch.arange(N, device=dev), y64]).sum(dtype=torch.float64)
+                parts["W"], parts["b"] = R.T @ Z, R.sum(0)
+
+            def take_only():
+                for _, idx in idxs:
+                    ds.take(idx, out=buf[:idx.numel()], check=False)
+
+            def streamed():
+                oW.zero_(), ob.zero_(), ol.zero_()
+                for g0, idx in idxs:
+                    rows = ds.take(idx, out=buf[:idx.numel()], check=False)
+                    fused(rows, y[g0:g0 + idx.numel()], 1)
+
+            # same sums from both paths, before anything is timed (fp32 in different orders: relative to the absolute sums)
+            fused(), from_parts()
+            torch.cuda.synchronize(dev)
+            scale = float(parts["W"].abs().max())
+            err = float((oW - parts["W"]).abs().max()) / scale
+            lerr = 0.0 if hv else abs(float(ol.sum()) - float(parts["loss"])) / float(parts["loss"])
+            assert err < 1e-4 and lerr < 1e-5, f"arms disagree: {err:.2e} {lerr:.2e}"
+            first = oW.clone()
+            streamed()
+            torch.cuda.synchronize(dev)
+            assert float((oW - first).abs().max()) / scale < 1e-4, "the streamed pass disagrees"
+
+            mode = "Hessian-vector" if hv else "gradient"
+            names = ["(a) lla_softmax_pass, rows resident", "(c) gemm_f32 + log_softmax + R.T @ Z",
+                     "(a') streamed: take + lla_softmax_pass", "     take alone"]
+            times = interleaved(dict(zip(names, (fused, from_parts, streamed, take_only))), inner, args.reps, dev)
+            say()
+            say(f"K = {K}, {mode} mode ({'one kernel' if K <= 32 else 'row statistics + pass'}): ms per pass over {N} rows, device "
+                f"events over {inner} back-to-back calls, {args.reps} interleaved runs   (max |(a) - (c)| / max |(c)| = {err:.1e})")
+            for k, ts in times.items():
+                runs = "  ".join(f"{x:9.4f}" for x in ts)
+                say(f"    {k:40s} {runs}   median {med(ts):9.4f} ms")
+            a, c = times[names[0]], times[names[1]]
+            ok = med(a) <= med(c) + (max(c) - min(c))
+            say(f"    (a) / (c) medians = {med(a) / med(c):.3f};  spread of (c) = {max(c) - min(c):.4f} ms;  "
+                f"(a) - (c) = {med(a) - med(c):+.4f} ms   -> bar {'MET' if ok else 'MISSED'}")
+
+    # reference point: an STL10-shaped fit
+    n, k = 5000, 10
+    labels = torch.arange(n) % k
+    mu = torch.randn(k, C, generator=g) * 0.1
+    X = mu[labels] + torch.randn(n, C, generator=g) * 0.5
+    Xd = X.to(dev)
+    LogisticProbe().fit(Xd[:512], labels[:512])          # (code objects loaded)
+    torch.cuda.synchronize(dev)
+    t0 = time.perf_counter()
+    p = LogisticProbe().fit(Xd, labels)
+    torch.cuda.synchronize(dev)
+    fit_s = time.perf_counter() - t0
+    say()
+    say(f"STL10-shaped fit ({n} x {C}, K = {k}): LogisticProbe.fit {fit_s:.3f} s wall, {p.n_passes_} passes, converged "
+        f"{p.converged_}, train accuracy {p.score(Xd, labels):.4f}")
+    try:
+        from sklearn.linear_model import LogisticRegression
+        X1 = torch.cat([X, torch.ones(n, 1)], 1).numpy()
+        t0 = time.perf_counter()
+        clf = LogisticRegression(C=1.0, fit_intercept=False, max_iter=1000).fit(X1, labels.numpy())
+        say(f"    scikit-learn LogisticRegression(C=1, fit_intercept=False) on [Z, 1] on this host: {time.perf_counter() - t0:.3f} s "
+            f"wall, train accuracy {clf.score(X1, labels.numpy()):.4f}   (reported, not gated)")
+    except ImportError:
+        say("    scikit-learn is not installed here: no host reference")
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--records", type=int, default=131072)
     ap.add_argument("--reps", type=int, default=3)
     ap.add_argument("--inner", type=int, default=0, help="calls per timed window (0: 40 at K = 10, 8 at K = 1000)")
     ap.add_argument("--grid", action="store_true", help="measure the cross-validated search (lla_svm_grid_pass) instead")
+    ap.add_argument("--softmax", action="store_true", help="measure the softmax-regression pass (lla_softmax_pass) instead")
     ap.add_argument("--out", default=None)
     args = ap.parse_args()
     if not torch.cuda.is_available():
@@ -221,8 +345,8 @@ def main():
     buf = torch.empty((min(group, N), C), dtype=torch.float32, device=dev)
     idxs = [(g0, torch.arange(g0, min(g0 + group, N), device=dev)) for g0 in range(0, N, group)]
 
-    if args.grid:
-        grid_arms(args, say, dev, ds, Z, g)
+    if args.grid or args.softmax:
+        (grid_arms if args.grid else softmax_arms)(args, say, dev, ds, Z, g)
         if args.out:
             with open(args.out, "w") as fh:
                 fh.write("\n".join(lines) + "\n")
