@@ -602,6 +602,23 @@ int lla_softmax_pass(const void *z, int z_dtype, int ld_z, const int32_t *y, int
                      const float *V, const float *vb, int K, int ld_w, const float *class_weight, float *out_W,
                      float *out_b, double *out_loss, int accumulate, void *workspace, void *stream);
 
+/* The same pass over G classifiers ("groups") of K <= 32 classes each that see the same rows: every (candidate, fold) of a
+ * cross-validated softmax regression in the passes of one fit.  W, V, out_W are [G K][C] with pitch ld_w, class k of group
+ * g in row g K + k; b, vb, out_b, out_loss are [G K]; group_held is [G]; group_class_weight is [G][K] (NULL = 1); fold is
+ * [B] (NULL: no row is held out); all on the device.  The quantities are lla_softmax_pass's per group, with the row weight
+ *   w_ig = 0 if (fold != NULL and fold[i] == group_held[g]) or y[i] lies outside [0, K), else group_class_weight[g][y[i]]
+ * -- selected, not multiplied by a mask: no rounding is added.  A 32-column tile holds 32 / K whole groups (the columns
+ * left over are dead), so the pass walks ceil(G / (32 / K)) tiles and its grid is a function of (B, K, G) alone; within a
+ * group the maximum and the sums run over its classes in class order, as lla_softmax_pass does, so where the grids agree
+ * (one tile) a group's slice of the outputs is bitwise what lla_softmax_pass returns for (W_g, b_g, y with the held-out
+ * rows relabelled -1, group_class_weight[g]).  K < 1, K > 32, G < 1 and group_held == NULL with fold != NULL are
+ * LLA_EINVAL (the workspace size of a refused shape is 0); everything else as lla_softmax_pass. */
+size_t lla_softmax_grid_pass_workspace_bytes(int C, int K, int G);
+int lla_softmax_grid_pass(const void *z, int z_dtype, int ld_z, const int32_t *y, const int32_t *fold, int B, int C,
+                          const float *W, const float *b, const float *V, const float *vb, int K, int G, int ld_w,
+                          const int32_t *group_held, const float *group_class_weight, float *out_W, float *out_b,
+                          double *out_loss, int accumulate, void *workspace, void *stream);
+
 /* out[n][H][W][ldc] (first cout channels) = relu(conv3x3(in, stride 1, pad 1) + bias) as an IMPLICIT GEMM:
  * `in` is NHWC fp16 [n][H][W][pitch] (first cin channels used; cin % 64 == 0, or cin == 32), weights fp16
  * [cout][K] with K = 9 cin rounded up to a multiple of 64 (zero padded) in the order (kh, kw, c), bias fp32

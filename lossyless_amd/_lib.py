@@ -97,6 +97,9 @@ _SIGNATURES = {
                                _i, _vp, _vp]),
     "lla_softmax_pass_workspace_bytes": (_sz, [_i, _i, _i]),
     "lla_softmax_pass": (_i, [_vp, _i, _i, _vp, _i, _i, _vp, _vp, _vp, _vp, _i, _i, _vp, _vp, _vp, _vp, _i, _vp, _vp]),
+    "lla_softmax_grid_pass_workspace_bytes": (_sz, [_i, _i, _i]),
+    "lla_softmax_grid_pass": (_i, [_vp, _i, _i, _vp, _vp, _i, _i, _vp, _vp, _vp, _vp, _i, _i, _i, _vp, _vp, _vp, _vp, _vp,
+                                   _i, _vp, _vp]),
     "lla_conv3x3_relu_f16": (_i, [_vp, _i, _i, _i, _i, _i, _vp, _vp, _vp, _i, _i, _vp]),
     "lla_conv3x3_direct_relu_f16": (_i, [_vp, _i, _i, _i, _i, _i, _vp, _i, _vp, _vp, _i, _i, _i, _vp]),
     "lla_conv3x3_rgb_s2_relu_f16": (_i, [_vp, _i, _i, _i, _vp, _i, _vp, _vp, _i, _vp]),

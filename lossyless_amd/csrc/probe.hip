@@ -41,6 +41,15 @@
 // per thread, no barrier, no second kernel.  K > 32: softmax_rows_kernel runs first -- the same staging and the same score
 // MFMA over ALL class tiles of a row tile, a running (max, sum exp(s - max), sum exp(s - max) t) per thread over its classes,
 // merged per row at the end of the row tile -- and leaves lse[B], a[B] in the workspace for step 3 to read.
+//
+// The softmax grid pass (lla_softmax_grid_pass; kSoftGrid below) is that walk over G classifiers ("groups") of K <= 32
+// classes each -- every (candidate, fold) of a cross-validated search -- which see the same rows: group g leaves the rows of
+// fold group_held[g] out and weighs the others by group_class_weight[g][y_i] (selected, not multiplied: no rounding is added).
+// A 32-column tile holds gpt = 32 / K whole groups: tile ct starts at column ct gpt K of the dense [G K] layout, column cl of
+// it is class cl % K of group ct gpt + cl / K, and the columns from gpt K on (and those of groups >= G) are dead: clamped
+// for the loads, residual 0.  Only step 3 differs: a thread's four columns lie in up to four groups, and it takes
+// (max, sum exp, sum exp t) of each of them itself from that group's K scores in LDS, in class order -- the loop of the
+// softmax pass over another range, so a group's outputs are the bits lla_softmax_pass gives when the grids agree.
 #include "common.h"
 
 #include <hip/hip_fp16.h>
@@ -57,14 +66,19 @@ constexpr int kZPad = 4;           // floats: 16-byte reads of one column group 
 constexpr int kRPitch = kClasses + 1;
 constexpr int kResident = 512;     // workgroups the chip holds at two per CU: the grid is cut to it
 
-enum { kHinge = 0, kGrid = 1, kSoftmax = 2 };      // what step 3 computes: lla_svm_pass, lla_svm_grid_pass, lla_softmax_pass
+// what step 3 computes: lla_svm_pass, lla_svm_grid_pass, lla_softmax_pass, lla_softmax_grid_pass
+enum { kHinge = 0, kGrid = 1, kSoftmax = 2, kSoftGrid = 3 };
 
 // (the softmax pass keeps the tile's 32 b and 32 vb behind Rs)
 __host__ __device__ inline int lds_floats(int C, bool softmax = false) {
   return kRows * (C + kZPad) + 2 * kRows * kClasses + kRows * kRPitch + (softmax ? 2 * kClasses : 0);
 }
 inline int class_tiles(int K) { return (K + kClasses - 1) / kClasses; }
-inline int walkers_max(int K) { const int w = kResident / class_tiles(K); return w < 1 ? 1 : w; }
+inline int tile_walkers(int nct) { const int w = kResident / nct; return w < 1 ? 1 : w; }
+inline int walkers_max(int K) { return tile_walkers(class_tiles(K)); }
+// softmax grid pass: the columns of a tile that hold whole groups of K classes, and the tiles G groups take
+inline int group_tile_cols(int K) { return (kClasses / K) * K; }
+inline long long group_tiles(int K, int G) { const int gpt = kClasses / K; return ((long long)G + gpt - 1) / gpt; }
 
 // The columns of a grid pass: what makes problem j of lla_svm_grid_pass differ from class j of lla_svm_pass.
 struct GridCols {
@@ -80,6 +94,9 @@ struct SoftmaxRows {
   const float *class_weight;  // [K] or NULL: every row weighs 1
   const float *lse;           // [B]; NULL when one class tile holds all K classes: step 3 takes the statistics itself
   const float *a;             // [B] (Hessian-vector mode)
+  // kSoftGrid: class_weight is [G][classes]; the row's fold id and the groups' held-out folds come in GridCols
+  // (fold, col_held [G]), and K is the number of real columns, G classes
+  int classes;                // classes per group
 };
 
 // 1. rows row0 .. row0 + 31 -> Zs [32][C + kZPad] as fp32 (rows beyond B are zeros: they contribute exactly nothing)
@@ -149,7 +166,9 @@ __device__ __forceinline__ void tile_scores(const float *Zs, float *Sp, const fl
 
 // HV: Hessian-vector mode.  NT: 32-column tiles of the gradient slice per wave (C <= 128 NT).  OBJ: kHinge -- column k is
 // class k, nothing is held out and every weight is 1; kGrid -- the columns are the problems of `cols` (K is their number J);
-// kSoftmax -- column k is class k and step 3 is the softmax residual of `sm`.
+// kSoftmax -- column k is class k and step 3 is the softmax residual of `sm`; kSoftGrid -- a tile's first
+// (32 / sm.classes) sm.classes columns are whole groups of sm.classes classes (K is the number of real columns, G classes),
+// the row's fold id and the groups' held-out folds are in `cols`, and step 3 is the softmax residual per group.
 // Workspace: part_W [class tile][walker][32][C], part_b / part_l [class tile][walker][32].
 template <bool HV, int NT, int OBJ>
 __global__ __launch_bounds__(256) void svm_pass_kernel(const void *__restrict__ z, int z_f16, int ld_z,
@@ -161,17 +180,18 @@ __global__ __launch_bounds__(256) void svm_pass_kernel(const void *__restrict__ 
                                                        GridCols cols, SoftmaxRows sm) {
   extern __shared__ __align__(16) float lds[];
   constexpr int NSLOT = HV ? 1 : 2;            // score partials kept apart in LDS (HV holds two products: same bytes)
-  constexpr bool GRID = OBJ == kGrid, SOFTMAX = OBJ == kSoftmax;
+  constexpr bool GRID = OBJ == kGrid, SOFTMAX = OBJ == kSoftmax, SOFTGRID = OBJ == kSoftGrid;
   const int pitch = C + kZPad;
   float *Zs = lds;                             // [32 rows][pitch]
   float *Sp = Zs + kRows * pitch;              // [product][slot][32 classes][32 rows]
   float *Rs = Sp + 2 * kRows * kClasses;       // [32 rows][33]
-  float *Bs = Rs + kRows * kRPitch;            // SOFTMAX: b and vb of the tile's classes, [2][32]
+  float *Bs = Rs + kRows * kRPitch;            // SOFTMAX, SOFTGRID: b and vb of the tile's classes, [2][32]
 
   const int tid = threadIdx.x, lane = tid & 63, wid = tid >> 6;
   const int r32 = lane & 31, hk = lane >> 5;
   const int ct = blockIdx.y, P = gridDim.x, p = blockIdx.x;
-  const int k0 = ct * kClasses;
+  const int ncols = SOFTGRID ? (kClasses / sm.classes) * sm.classes : kClasses;      // live columns of a full tile
+  const int k0 = ct * ncols;
 
   // scores: "A" lane l = W[k0 + (l & 31)][c + (l >> 5)], "B" lane l = Z[row (l & 31)][c + (l >> 5)]  (gemm_f32.hip)
   int n = k0 + r32;
@@ -188,7 +208,7 @@ __global__ __launch_bounds__(256) void svm_pass_kernel(const void *__restrict__ 
 #pragma unroll
   for (int j = 0; j < 4; ++j) {
     const int c = k0 + cl0 + 8 * j;
-    c_ok[j] = c < K;
+    c_ok[j] = c < K && (!SOFTGRID || cl0 + 8 * j < ncols);
     bk[j] = c_ok[j] ? bias[c] : 0.f;
     vbk[j] = (HV && c_ok[j]) ? vbias[c] : 0.f;
     ccls[j] = (GRID && c_ok[j]) ? cols.col_class[c] : c;
@@ -197,9 +217,23 @@ __global__ __launch_bounds__(256) void svm_pass_kernel(const void *__restrict__ 
     cneg[j] = (GRID && c_ok[j]) ? cols.col_cneg[c] : 0.f;
   }
   const bool folds = GRID && cols.fold != nullptr;
-  if (SOFTMAX && tid < kClasses) {             // (visible after the barrier that follows the first staging)
-    Bs[tid] = k0 + tid < K ? bias[k0 + tid] : 0.f;
-    Bs[kClasses + tid] = (HV && k0 + tid < K) ? vbias[k0 + tid] : 0.f;
+  if ((SOFTMAX || SOFTGRID) && tid < kClasses) {         // (visible after the barrier that follows the first staging)
+    const bool real = k0 + tid < K && tid < ncols;
+    Bs[tid] = real ? bias[k0 + tid] : 0.f;
+    Bs[kClasses + tid] = (HV && real) ? vbias[k0 + tid] : 0.f;
+  }
+  // SOFTGRID: per column its group's first column in the tile, its held-out fold and its K class weights
+  int gcol[4], gheld[4];
+  const float *gcw[4];
+#pragma unroll
+  for (int j = 0; j < 4; ++j) {
+    gcol[j] = 0, gheld[j] = 0, gcw[j] = nullptr;
+    if (SOFTGRID && c_ok[j]) {
+      const int gi = (cl0 + 8 * j) / sm.classes, g = (k0 + cl0 + 8 * j) / sm.classes;
+      gcol[j] = gi * sm.classes;
+      gheld[j] = cols.fold ? cols.col_held[g] : 0;
+      gcw[j] = sm.class_weight ? sm.class_weight + (size_t)g * sm.classes : nullptr;
+    }
   }
 
   f32x16 acc[NT];
@@ -217,7 +251,50 @@ __global__ __launch_bounds__(256) void svm_pass_kernel(const void *__restrict__ 
     tile_scores<HV>(Zs, Sp, wp, vp, C, lane, wid);                   // 2.
 
     // 3. residuals
-    if constexpr (SOFTMAX) {
+    if constexpr (SOFTGRID) {
+      const bool row_ok = row0 + rr < B;
+      const int yy = row_ok ? y[row0 + rr] : -1;
+      const bool live = yy >= 0 && yy < sm.classes;      // any other row weighs 0 in every group
+      const int ff = (cols.fold && row_ok) ? cols.fold[row0 + rr] : 0;
+      const auto score = [&](int cl) {         // (as the softmax pass)
+        float sc = Sp[cl * kRows + rr];
+        if (NSLOT == 2) sc += Sp[kRows * kClasses + cl * kRows + rr];
+        return sc + Bs[cl];
+      };
+      const auto tangent = [&](int cl) { return Sp[kRows * kClasses + cl * kRows + rr] + Bs[kClasses + cl]; };
+      int have = -1;                           // the group whose statistics lse / ai hold: the columns' groups ascend with j
+      float lse = 0.f, ai = 0.f;
+#pragma unroll
+      for (int j = 0; j < 4; ++j) {
+        const int cl = cl0 + 8 * j;
+        // the row trains group j: its label is a class and its fold is not the one the group holds out
+        const bool on = live && c_ok[j] && !(cols.fold && ff == gheld[j]);
+        float r = 0.f;
+        if (on) {
+          if (gcol[j] != have) {               // the statistics over the group's classes in class order, as the softmax pass
+            have = gcol[j];
+            float mx = score(have);
+            for (int k = 1; k < sm.classes; ++k) mx = fmaxf(mx, score(have + k));
+            float se = 0.f, st = 0.f;
+            for (int k = 0; k < sm.classes; ++k) {
+              const float e = expf(score(have + k) - mx);
+              se += e;
+              if (HV) st += e * tangent(have + k);
+            }
+            lse = mx + logf(se);
+            if (HV) ai = st / se;
+          }
+          const float wi = gcw[j] ? gcw[j][yy] : 1.f;
+          const float sc = score(cl);
+          const bool own = yy == cl - gcol[j];
+          const float pk = expf(sc - lse);
+          r = HV ? wi * pk * (tangent(cl) - ai) : wi * (pk - (own ? 1.f : 0.f));
+          if (!HV && own) lacc[j] += wi * (lse - sc);
+        }
+        bacc[j] += r;
+        Rs[rr * kRPitch + cl] = r;
+      }
+    } else if constexpr (SOFTMAX) {
       const bool row_ok = row0 + rr < B;
       const int yy = row_ok ? y[row0 + rr] : -1;
       const bool live = yy >= 0 && yy < K;     // any other row weighs 0: it contributes exactly nothing
@@ -307,7 +384,8 @@ __global__ __launch_bounds__(256) void svm_pass_kernel(const void *__restrict__ 
     __syncthreads();                           // the next tile's staging overwrites Zs, Sp and Rs
   }
 
-  // this workgroup's partial sums -> workspace (classes beyond K hold exact zeros and are never read)
+  // this workgroup's partial sums -> workspace (classes beyond K, and the dead columns from `ncols` on of a kSoftGrid tile,
+  // hold exact zeros and are never read: svm_reduce_kernel maps output k to slot k % ncols of tile k / ncols)
   float *pw = part_W + (size_t)(ct * P + p) * kClasses * C;
 #pragma unroll
   for (int t = 0; t < NT; ++t) {
@@ -429,15 +507,16 @@ __device__ __forceinline__ T ordered_sum(const float *__restrict__ src, size_t s
 }
 
 // out (+)= the partial sums of walkers 0 .. P-1, in that order.  One thread per (class, column); columns C and C + 1
-// of a class are its out_b and out_loss.
+// of a class are its out_b and out_loss.  ncols: the live columns of a tile (32; a softmax grid pass: 32 / K whole groups),
+// so that output k is slot k % ncols of tile k / ncols.
 __global__ __launch_bounds__(64) void svm_reduce_kernel(const float *__restrict__ part_W, const float *__restrict__ part_b,
                                                         const float *__restrict__ part_l, int P, int C, int K, int ld_w,
                                                         float *__restrict__ out_W, float *__restrict__ out_b,
-                                                        double *__restrict__ out_loss, int accumulate) {
+                                                        double *__restrict__ out_loss, int accumulate, int ncols) {
   const long long idx = (long long)blockIdx.x * 64 + threadIdx.x;
   if (idx >= (long long)K * (C + 2)) return;
   const int k = (int)(idx / (C + 2)), c = (int)(idx - (long long)k * (C + 2));
-  const int ct = k / kClasses, i = k - ct * kClasses;
+  const int ct = k / ncols, i = k - ct * ncols;
   if (c < C) {
     const float sum = ordered_sum<float>(part_W + ((size_t)ct * P * kClasses + i) * C + c, (size_t)kClasses * C, P);
     float *o = out_W + (size_t)k * ld_w + c;
@@ -478,40 +557,45 @@ extern "C" size_t lla_svm_pass_workspace_bytes(int C, int K) {
 
 namespace {
 
-// The three entry points: the argument checks, (softmax over several class tiles: the row statistics,) the persistent pass
-// and the ordered reduction.  obj kHinge: lla_svm_pass; kGrid: `cols`; kSoftmax: `class_weight` (NULL = 1).
+// The four entry points: the argument checks, (softmax over several class tiles: the row statistics,) the persistent pass
+// and the ordered reduction.  obj kHinge: lla_svm_pass; kGrid: `cols`; kSoftmax: `class_weight` (NULL = 1); kSoftGrid: G
+// groups of `classes` classes (K = G classes columns), `class_weight` [G][classes], the fold ids and held-out folds in `cols`.
 int svm_pass_launch(int obj, const void *z, int z_dtype, int ld_z, const int32_t *y, int B, int C, const float *W,
                     const float *b, const float *V, const float *vb, int K, int ld_w, const GridCols *cols,
                     const float *class_weight, float *out_W, float *out_b, double *out_loss, int accumulate,
-                    void *workspace, void *stream) {
+                    void *workspace, void *stream, int classes) {
   if (!shape_ok(C, K) || B < 0 || ld_z < C || ld_w < C || (ld_z & 3) || (ld_w & 3) ||
       (z_dtype != LLA_Z_F32 && z_dtype != LLA_Z_F16))
     return LLA_EINVAL;
   if (!W || !b || !out_W || !out_b || !workspace || (V && !vb) || (!V && !out_loss) || (B > 0 && (!z || !y)))
     return LLA_EINVAL;
-  if (cols && (!cols->col_class || !cols->col_held || !cols->col_cpos || !cols->col_cneg)) return LLA_EINVAL;
+  if (obj == kGrid && (!cols->col_class || !cols->col_held || !cols->col_cpos || !cols->col_cneg)) return LLA_EINVAL;
+  if (obj == kSoftGrid && (classes < 1 || classes > kClasses || (cols->fold && !cols->col_held))) return LLA_EINVAL;
   const uintptr_t z_align = z_dtype == LLA_Z_F32 ? 15 : 7;
   if (((uintptr_t)z & z_align) || ((uintptr_t)W & 15) || ((uintptr_t)V & 15) || ((uintptr_t)workspace & 3))
     return LLA_EINVAL;
   if (B == 0 && accumulate) return LLA_OK;
 
-  const int nct = class_tiles(K);
+  const int ncols = obj == kSoftGrid ? group_tile_cols(classes) : kClasses;      // live columns of a full tile
+  const int nct = (K + ncols - 1) / ncols;
   const int ntiles = (B + kRows - 1) / kRows;
-  const int P = ntiles < walkers_max(K) ? ntiles : walkers_max(K);
+  const int pmax = tile_walkers(nct);
+  const int P = ntiles < pmax ? ntiles : pmax;
   float *part_W = static_cast<float *>(workspace);
-  float *part_b = part_W + (size_t)nct * walkers_max(K) * kClasses * C;
-  float *part_l = part_b + (size_t)nct * walkers_max(K) * kClasses;
+  float *part_b = part_W + (size_t)nct * pmax * kClasses * C;
+  float *part_l = part_b + (size_t)nct * pmax * kClasses;
   hipStream_t st = as_stream(stream);
   if (P > 0) {
-    const void *kernel = obj == kSoftmax ? pass_kernel<kSoftmax>(V != nullptr, C)
-                                         : obj == kGrid ? pass_kernel<kGrid>(V != nullptr, C) : pass_kernel<kHinge>(V != nullptr, C);
-    const size_t lds_bytes = (size_t)lds_floats(C, obj == kSoftmax) * sizeof(float);
+    const void *kernel = obj == kSoftGrid ? pass_kernel<kSoftGrid>(V != nullptr, C)
+                         : obj == kSoftmax ? pass_kernel<kSoftmax>(V != nullptr, C)
+                         : obj == kGrid    ? pass_kernel<kGrid>(V != nullptr, C) : pass_kernel<kHinge>(V != nullptr, C);
+    const size_t lds_bytes = (size_t)lds_floats(C, obj == kSoftmax || obj == kSoftGrid) * sizeof(float);
     if (lds_bytes > dynamic_lds_limit(kernel)) return LLA_ECAP;
     const int z_f16 = z_dtype == LLA_Z_F16;
     GridCols gc = cols ? *cols : GridCols{nullptr, nullptr, nullptr, nullptr, nullptr};
-    SoftmaxRows sm = {class_weight, nullptr, nullptr};
+    SoftmaxRows sm = {class_weight, nullptr, nullptr, classes};
     if (obj == kSoftmax && nct > 1) {          // lse [B], a [B] behind the partial sums
-      float *lse = part_l + (size_t)nct * walkers_max(K) * kClasses, *a = lse + B;
+      float *lse = part_l + (size_t)nct * pmax * kClasses, *a = lse + B;
       const void *rows_kernel = V ? reinterpret_cast<const void *>(&softmax_rows_kernel<true>)
                                   : reinterpret_cast<const void *>(&softmax_rows_kernel<false>);
       const size_t rows_lds = (size_t)lds_floats(C) * sizeof(float);
@@ -531,7 +615,7 @@ int svm_pass_launch(int obj, const void *z, int z_dtype, int ld_z, const int32_t
   }
   const long long n_out = (long long)K * (C + 2);
   svm_reduce_kernel<<<(unsigned)((n_out + 63) / 64), 64, 0, st>>>(part_W, part_b, part_l, P, C, K, ld_w, out_W, out_b,
-                                                                     V ? nullptr : out_loss, accumulate);
+                                                                     V ? nullptr : out_loss, accumulate, ncols);
   return check_launch();
 }
 
@@ -541,7 +625,7 @@ extern "C" int lla_svm_pass(const void *z, int z_dtype, int ld_z, const int32_t 
                             const float *b, const float *V, const float *vb, int K, int ld_w, float *out_W, float *out_b,
                             double *out_loss, int accumulate, void *workspace, void *stream) {
   return svm_pass_launch(kHinge, z, z_dtype, ld_z, y, B, C, W, b, V, vb, K, ld_w, nullptr, nullptr, out_W, out_b, out_loss,
-                         accumulate, workspace, stream);
+                         accumulate, workspace, stream, 0);
 }
 
 // The grid is the one lla_svm_pass launches for K = J: a function of (B, J) alone.
@@ -554,7 +638,7 @@ extern "C" int lla_svm_grid_pass(const void *z, int z_dtype, int ld_z, const int
                                  void *workspace, void *stream) {
   const GridCols cols = {fold, col_class, col_held, col_cpos, col_cneg};
   return svm_pass_launch(kGrid, z, z_dtype, ld_z, y, B, C, W, b, V, vb, J, ld_w, &cols, nullptr, out_W, out_b, out_loss,
-                         accumulate, workspace, stream);
+                         accumulate, workspace, stream, 0);
 }
 
 // The partial sums of lla_svm_pass, then lse [B] and a [B] when the classes span more than one tile.
@@ -567,5 +651,22 @@ extern "C" int lla_softmax_pass(const void *z, int z_dtype, int ld_z, const int3
                                 const float *b, const float *V, const float *vb, int K, int ld_w, const float *class_weight,
                                 float *out_W, float *out_b, double *out_loss, int accumulate, void *workspace, void *stream) {
   return svm_pass_launch(kSoftmax, z, z_dtype, ld_z, y, B, C, W, b, V, vb, K, ld_w, nullptr, class_weight, out_W, out_b,
-                         out_loss, accumulate, workspace, stream);
+                         out_loss, accumulate, workspace, stream, 0);
+}
+
+// The partial sums of ceil(G / (32 / K)) tiles: the grid is a function of (B, K, G) alone.
+extern "C" size_t lla_softmax_grid_pass_workspace_bytes(int C, int K, int G) {
+  if (K < 1 || K > kClasses || G < 1 || !shape_ok(C, K) || group_tiles(K, G) > 65535) return 0;
+  const int nct = (int)group_tiles(K, G);
+  return (size_t)nct * tile_walkers(nct) * kClasses * (C + 2) * sizeof(float);
+}
+
+extern "C" int lla_softmax_grid_pass(const void *z, int z_dtype, int ld_z, const int32_t *y, const int32_t *fold, int B, int C,
+                                     const float *W, const float *b, const float *V, const float *vb, int K, int G, int ld_w,
+                                     const int32_t *group_held, const float *group_class_weight, float *out_W, float *out_b,
+                                     double *out_loss, int accumulate, void *workspace, void *stream) {
+  if (K < 1 || K > kClasses || G < 1 || group_tiles(K, G) > 65535) return LLA_EINVAL;
+  const GridCols cols = {fold, nullptr, group_held, nullptr, nullptr};
+  return svm_pass_launch(kSoftGrid, z, z_dtype, ld_z, y, B, C, W, b, V, vb, G * K, ld_w, &cols, group_class_weight, out_W,
+                         out_b, out_loss, accumulate, workspace, stream, K);
 }

@@ -484,6 +484,40 @@ class LinearProbe(_Scores):
         return s[:, 0].contiguous() if len(self.classes_) == 2 else s.contiguous()
 
 
+def _folds_of(cv_arg, cls_idx, n_classes):
+    """-> (fold id per row int64 [N], sorted fold ids, class counts of each fold's training part); raises if a training part lacks a class or a fold is empty."""
+    N = int(cls_idx.numel())
+    if isinstance(cv_arg, (int, np.integer)):
+        cv = int(cv_arg)
+        if cv < 2:
+            raise ValueError("cv must be at least 2")
+        order = torch.argsort(cls_idx, stable=True)                         # file order within each class
+        counts = torch.bincount(cls_idx, minlength=n_classes)
+        rank = torch.arange(N) - (torch.cumsum(counts, 0) - counts)[cls_idx[order]]
+        fold = torch.empty(N, dtype=torch.int64)
+        fold[order] = rank % cv
+        ids = list(range(cv))
+    else:
+        fold = torch.as_tensor(np.asarray(cv_arg.cpu() if isinstance(cv_arg, torch.Tensor) else cv_arg))
+        if fold.is_floating_point() or fold.dtype == torch.bool or fold.dim() != 1 or fold.numel() != N:
+            raise ValueError(f"cv must be an int or an int array of {N} fold ids")
+        fold = fold.to(torch.int64)
+        if int(fold.min()) < -1 or int(fold.max()) >= 2 ** 31 - 1:
+            raise ValueError("fold ids must be >= -1 (-1: always train)")
+        ids = [int(v) for v in torch.unique(fold) if int(v) >= 0]
+        if not ids:
+            raise ValueError("no row is ever held out")
+    train_counts = []
+    for f in ids:
+        if not bool((fold == f).any()):
+            raise ValueError(f"fold {f} holds no row")
+        c = torch.bincount(cls_idx[fold != f], minlength=n_classes)
+        if bool((c == 0).any()):
+            raise ValueError(f"the training part of fold {f} lacks a class")
+        train_counts.append(c)
+    return fold, ids, train_counts
+
+
 class LinearProbeCV:
     """``LinearProbeCV(candidates, cv=5, tol=1e-4, max_iter=100, refit=True, max_problems=4096)``: the search the reference
     evaluates a compressor with (its utils/Z_linear_eval.py:62-93: ``RandomizedSearchCV`` over ``C`` and ``class_weight``,
@@ -527,37 +561,7 @@ class LinearProbeCV:
 
     # ------------------------------------------------------------------ folds
     def _folds_of(self, cls_idx, n_classes):
-        """-> (fold id per row int64 [N], sorted fold ids); raises if a training part lacks a class or a fold is empty."""
-        N = int(cls_idx.numel())
-        if isinstance(self.cv, (int, np.integer)):
-            cv = int(self.cv)
-            if cv < 2:
-                raise ValueError("cv must be at least 2")
-            order = torch.argsort(cls_idx, stable=True)                         # file order within each class
-            counts = torch.bincount(cls_idx, minlength=n_classes)
-            rank = torch.arange(N) - (torch.cumsum(counts, 0) - counts)[cls_idx[order]]
-            fold = torch.empty(N, dtype=torch.int64)
-            fold[order] = rank % cv
-            ids = list(range(cv))
-        else:
-            fold = torch.as_tensor(np.asarray(self.cv.cpu() if isinstance(self.cv, torch.Tensor) else self.cv))
-            if fold.is_floating_point() or fold.dtype == torch.bool or fold.dim() != 1 or fold.numel() != N:
-                raise ValueError(f"cv must be an int or an int array of {N} fold ids")
-            fold = fold.to(torch.int64)
-            if int(fold.min()) < -1 or int(fold.max()) >= 2 ** 31 - 1:
-                raise ValueError("fold ids must be >= -1 (-1: always train)")
-            ids = [int(v) for v in torch.unique(fold) if int(v) >= 0]
-            if not ids:
-                raise ValueError("no row is ever held out")
-        train_counts = []
-        for f in ids:
-            if not bool((fold == f).any()):
-                raise ValueError(f"fold {f} holds no row")
-            c = torch.bincount(cls_idx[fold != f], minlength=n_classes)
-            if bool((c == 0).any()):
-                raise ValueError(f"the training part of fold {f} lacks a class")
-            train_counts.append(c)
-        return fold, ids, train_counts
+        return _folds_of(self.cv, cls_idx, n_classes)
 
     # ------------------------------------------------------------------ fit
     def fit(self, data, labels=None, rows_per_pass=65536, keep_rows=False):
@@ -908,3 +912,302 @@ class LogisticProbe(_Scores):
             p = torch.sigmoid(s)
             return torch.stack([1.0 - p, p], 1)
         return torch.softmax(s, 1)
+
+
+# ---------------------------------------------------------------------- cross-validated softmax regression
+class _HostSoftmaxGridSums(_HostSoftmaxSums):
+    """float64 torch evaluation of the two quantities ``lla_softmax_grid_pass`` computes for G groups of K classes, times
+    each group's C (the CPU path; the GPU tests' oracle): ``held`` [G] fold ids, ``cw`` [G, K] class weights, ``scale`` [G].
+    The fixed blocks of ``_HostSoftmaxSums``, one group at a time."""
+
+    def __init__(self, rows, idx, fold, held, cw, scale):
+        self.rows, self.idx, self.fold = rows, idx, fold
+        self.held, self.cw, self.scale = held.to(torch.int64), cw.to(torch.float64), scale.to(torch.float64)
+        self.G, self.K = int(cw.shape[0]), int(cw.shape[1])
+        self.cmax = self.scale * self.cw.amax(1)
+        self.n_passes = 0
+
+    def _rows_of(self, g, g0, z, W, b):
+        """-> (scores [n, K], lse [n, 1], p, w_ig [n, 1], one-hot labels [n, K]) of the block for group g."""
+        n = z.shape[0]
+        y = self.idx[g0:g0 + n]
+        s = z @ W[g].T + b[g]
+        lse = torch.logsumexp(s, 1, keepdim=True)
+        hot = torch.zeros_like(s).scatter_(1, y[:, None], 1.0)
+        w = torch.where(self.fold[g0:g0 + n] == self.held[g], torch.zeros((), dtype=torch.float64), self.cw[g][y])
+        return s, lse, torch.exp(s - lse), w[:, None], hot
+
+    # Every product and every sum below has the shape of ONE group: a group's numbers do not depend on how many groups
+    # share the batch, so solving in several batches returns the bits of one batch.
+    def gradient(self, W, b):
+        loss, gW, gb = torch.zeros(self.G, dtype=torch.float64), torch.zeros_like(W), torch.zeros_like(b)
+        for g0, z in self._blocks():
+            for g in range(self.G):
+                s, lse, p, w, hot = self._rows_of(g, g0, z, W, b)
+                r = w * (p - hot)
+                loss[g] += (w * (lse - (s * hot).sum(1, keepdim=True))).sum()
+                gW[g] += r.T @ z
+                gb[g] += r.sum(0)
+        self.n_passes += 1
+        return self.scale * loss, self.scale[:, None, None] * gW, self.scale[:, None] * gb
+
+    def hessian_vector(self, W, b, V, vb):
+        hW, hb = torch.zeros_like(W), torch.zeros_like(b)
+        for g0, z in self._blocks():
+            for g in range(self.G):
+                _, _, p, w, _ = self._rows_of(g, g0, z, W, b)
+                t = z @ V[g].T + vb[g]
+                r = w * p * (t - (p * t).sum(1, keepdim=True))
+                hW[g] += r.T @ z
+                hb[g] += r.sum(0)
+        self.n_passes += 1
+        return self.scale[:, None, None] * hW, self.scale[:, None] * hb
+
+
+class _DeviceSoftmaxGridSums:
+    """The same two quantities on the device, one decode per group of rows for all G classifiers.  K <= 32: one
+    ``lla_softmax_grid_pass(accumulate=1)`` per decode group.  K > 32: ``lla_softmax_pass`` once per classifier on the same
+    taken buffer, with that classifier's held-out rows relabelled -1 (an out-of-range label contributes exactly nothing)."""
+    dtype = torch.float32
+    slack = _DeviceSums.slack
+
+    def __init__(self, rows, idx, fold, held, cw, scale):
+        dim, dev = rows.dim, rows.device
+        if dim % 8 or not 8 <= dim <= 1024:
+            raise ValueError(f"the device probe needs a feature width that is a multiple of 8 in [8, 1024], got {dim}")
+        self.rows, self.dim, self.device = rows, dim, dev
+        self.G, self.K = int(cw.shape[0]), int(cw.shape[1])
+        self.scale = scale.to(torch.float64).to(dev)
+        self.scale32 = self.scale.to(torch.float32)
+        self.cmax = self.scale * cw.to(torch.float64).amax(1).to(dev)
+        self.cw = None if bool((cw == 1).all()) else cw.to(torch.float32).to(dev).contiguous()
+        self.fused = self.K <= 32
+        self.L = _lib.lib()
+        y, fold, held = idx.to(torch.int32).to(dev), fold.to(torch.int32).to(dev), held.to(torch.int32).to(dev)
+        if self.fused:
+            self.y, self.fold, self.held = y.contiguous(), fold.contiguous(), held.contiguous()
+            nbytes = int(self.L.lla_softmax_grid_pass_workspace_bytes(dim, self.K, self.G))
+        else:
+            self.y, self.fold, self.held = y.contiguous(), fold.contiguous(), held.tolist()
+            nbytes = int(self.L.lla_softmax_pass_workspace_bytes(dim, self.K, min(rows.group, max(rows.n, 1))))
+        if nbytes == 0:
+            raise ValueError(f"the softmax passes refuse C = {dim}, K = {self.K}, G = {self.G}")
+        self.ws = torch.empty(nbytes, dtype=torch.uint8, device=dev)
+        self.n_passes = 0
+
+    def _pass(self, W, b, V, vb):
+        G, K, C = self.G, self.K, self.dim
+        oW = torch.zeros((G, K, C), dtype=torch.float32, device=self.device)
+        ob = torch.zeros((G, K), dtype=torch.float32, device=self.device)
+        loss = torch.zeros((G, K), dtype=torch.float64, device=self.device) if V is None else None
+        at = (lambda t, g: None if t is None else t[g])
+        with torch.cuda.device(self.device):
+            st = _lib.stream_ptr(self.device)
+            for g0, z in self.rows.groups():
+                n = int(z.shape[0])
+                zt = _lib.LLA_Z_F16 if z.dtype == torch.float16 else _lib.LLA_Z_F32
+                ld = int(z.stride(0)) if n > 1 else C
+                if self.fused:
+                    rc = self.L.lla_softmax_grid_pass(_lib.ptr(z), zt, ld, _lib.ptr(self.y[g0:g0 + n]), _lib.ptr(self.fold[g0:g0 + n]),
+                                                      n, C, _lib.ptr(W), _lib.ptr(b), _lib.ptr(V), _lib.ptr(vb), K, G, C,
+                                                      _lib.ptr(self.held), _lib.ptr(self.cw), _lib.ptr(oW), _lib.ptr(ob),
+                                                      _lib.ptr(loss), 1, _lib.ptr(self.ws), st)
+                    _lib.check(rc, "lla_softmax_grid_pass")
+                    continue
+                yn, fn = self.y[g0:g0 + n], self.fold[g0:g0 + n]
+                for g in range(G):       # this classifier's labels of the decode group: -1 on the rows it holds out
+                    yg = torch.where(fn == self.held[g], -1, yn).to(torch.int32)
+                    rc = self.L.lla_softmax_pass(_lib.ptr(z), zt, ld, _lib.ptr(yg), n, C, _lib.ptr(W[g]),
+                                                 _lib.ptr(b[g]), _lib.ptr(at(V, g)), _lib.ptr(at(vb, g)), K, C,
+                                                 _lib.ptr(at(self.cw, g)), _lib.ptr(oW[g]), _lib.ptr(ob[g]), _lib.ptr(at(loss, g)),
+                                                 1, _lib.ptr(self.ws), st)
+                    _lib.check(rc, "lla_softmax_pass")
+        self.n_passes += 1
+        return (None if loss is None else self.scale * loss.sum(1)), self.scale32[:, None, None] * oW, self.scale32[:, None] * ob
+
+    column_squares = _DeviceSoftmaxSums.column_squares
+
+    def gradient(self, W, b):
+        return self._pass(W.contiguous(), b.contiguous(), None, None)
+
+    def hessian_vector(self, W, b, V, vb):
+        return self._pass(W.contiguous(), b.contiguous(), V.contiguous(), vb.contiguous())[1:]
+
+
+def _newton_cg_joint_groups(sums, dim, n_rows, device, tol, max_iter):
+    """``_newton_cg_joint`` for G classifiers side by side: W [G, K, C], b [G, K]; every group is its own joint problem with
+    its own inner products, CG residual test, step length and stopping rule, and a group that has converged stands still
+    while the others go on (as the problems of ``_newton_cg``) -> (W, b, f [G] float64, converged [G] bool on the CPU)."""
+    dt, G, K = sums.dtype, sums.G, sums.K
+    W, b = torch.zeros((G, K, dim), dtype=dt, device=device), torch.zeros((G, K), dtype=dt, device=device)
+    tiny = torch.finfo(dt).tiny
+
+    def evaluate(W, b):
+        loss, gW, gb = sums.gradient(W, b)
+        return 0.5 * ((W.double() ** 2).sum((1, 2)) + (b.double() ** 2).sum(1)) + loss, W + gW, b + gb
+
+    def dot(aW, ab, cW, cb):         # per-group inner product over [K, C + 1]
+        return (aW * cW).sum((1, 2)) + (ab * cb).sum(1)
+
+    def sup(gW, gb):
+        return torch.maximum(gW.abs().amax((1, 2)), gb.abs().amax(1))
+
+    # Jacobi preconditioner per group: 1 + C_g / 4 max(cw_g) sum_i z_ic^2 with the column sums over ALL rows, held-out ones
+    # included -- an upper bound of the Hessian's diagonal for every fold (any positive diagonal is valid)
+    cmax = sums.cmax.to(device)
+    mW = (1.0 + 0.25 * cmax[:, None, None] * sums.column_squares()[None, None, :]).to(dt)
+    mb = (1.0 + 0.25 * cmax * n_rows).to(dt)[:, None]
+    f, gW, gb = evaluate(W, b)
+    stop_at = tol * sup(gW, gb)
+    for _ in range(int(max_iter)):
+        live = sup(gW, gb) > stop_at     # groups still short of the stopping rule; the others stay where they are
+        if not bool(live.any()):
+            break
+        lv = live.to(dt)
+        dW, db = torch.zeros_like(W), torch.zeros_like(b)
+        rW, rb = -gW * lv[:, None, None], -gb * lv[:, None]
+        yW, yb = rW / mW, rb / mb
+        pW, pb = yW.clone(), yb.clone()
+        rs = dot(rW, rb, yW, yb)
+        stop = _CG_TOL ** 2 * dot(rW, rb, rW, rb)
+        busy = live.clone()
+        for _cg in range(_CG_MAX):
+            hW, hb = sums.hessian_vector(W, b, pW, pb)
+            hW, hb = pW + hW, pb + hb
+            alpha = busy.to(dt) * rs / dot(pW, pb, hW, hb).clamp_min(tiny)
+            dW += alpha[:, None, None] * pW
+            db += alpha[:, None] * pb
+            rW -= alpha[:, None, None] * hW
+            rb -= alpha[:, None] * hb
+            busy = busy & (dot(rW, rb, rW, rb) > stop)       # |H d + g|_2 <= 0.1 |g|_2: the group's step is ready
+            if not bool(busy.any()):
+                break
+            yW, yb = rW / mW, rb / mb
+            rs2 = dot(rW, rb, yW, yb)
+            beta = busy.to(dt) * rs2 / rs.clamp_min(tiny)
+            pW, pb = yW + beta[:, None, None] * pW, yb + beta[:, None] * pb
+            rs = torch.where(busy, rs2, rs)
+        # per-group backtracking: a group keeps its step length once the Armijo condition holds for it
+        gd = dot(gW, gb, dW, db).double()
+        t = torch.ones(G, dtype=dt, device=device)
+        for _ls in range(_BACKTRACKS):
+            W2, b2 = W + t[:, None, None] * dW, b + t[:, None] * db
+            f2, gW2, gb2 = evaluate(W2, b2)
+            ok = f2 <= f + _ARMIJO * t.double() * gd + sums.slack * f.abs()
+            if bool(ok.all()):
+                break
+            t = torch.where(ok, t, t * 0.5)
+        else:                            # groups whose step never passed stay where they were
+            t = torch.where(ok, t, torch.zeros_like(t))
+            W2, b2 = W + t[:, None, None] * dW, b + t[:, None] * db
+            f2, gW2, gb2 = evaluate(W2, b2)
+        W, b, f, gW, gb = W2, b2, f2, gW2, gb2
+        if not bool(((t > 0) & live).any()):      # nothing moved: rounding has the last word
+            break
+    return W, b, f, (sup(gW, gb) <= stop_at).cpu()
+
+
+class LogisticProbeCV:
+    """``LogisticProbeCV(candidates, cv=5, tol=1e-4, max_iter=100, refit=True, max_problems=4096)``: CLIP's linear-probe
+    protocol -- softmax regression with the L2 strength chosen on held-out data -- as ``LinearProbeCV`` runs the hinge's
+    search: every (candidate, fold) classifier of ``LogisticProbe``'s objective solved in the same passes over the data.
+
+    candidates  a sequence of ``(C, class_weight)``: ``LogisticProbeCV.logspace(n, low, high)`` for the usual sweep;
+                what ``LinearProbeCV.sample`` returns is accepted.
+    cv          as ``LinearProbeCV``: an int (stratified, unshuffled) or an int array of fold ids with -1 for rows that
+                always train; ``"balanced"`` weights are counted on each fold's training part.
+    refit       also fit every candidate on all rows, in the same passes: ``best_estimator_`` costs no second solve.
+    max_problems  at most ``max_problems // K`` classifiers are solved side by side; more are solved in batches.
+
+    ``fit(data, labels=None, rows_per_pass=65536, keep_rows=False)`` takes what ``LogisticProbe.fit`` takes; a pass hands
+    each decode group to ``lla_softmax_grid_pass`` (K <= 32; above, to ``lla_softmax_pass`` once per classifier on the same
+    decoded rows).  Every classifier is its own joint Newton-CG problem; a converged one stands still while the others go
+    on.  Two classes follow ``LogisticProbe`` (the K = 2 softmax with C / 2, ``coef = W_1 - W_0``).  Afterwards:
+    ``cv_scores_`` float64 ``[candidates, folds]`` (accuracy on the held-out rows), ``mean_scores_``, ``best_index_`` (the
+    first maximum), ``best_params_``, ``fold_coef_`` / ``fold_intercept_`` fp32 ``[candidates, folds, K or 1, C]``,
+    ``best_estimator_`` (a fitted ``LogisticProbe``; ``None`` without ``refit``), ``classes_``, ``folds_``, ``n_passes_``,
+    ``converged_`` bool ``[candidates, folds (+ 1 with refit)]``; warns when a classifier stops short of ``tol``."""
+
+    def __init__(self, candidates, cv=5, tol=1e-4, max_iter=100, refit=True, max_problems=4096):
+        self.candidates = [(float(C), cw) for C, cw in candidates]
+        if not self.candidates:
+            raise ValueError("no candidates")
+        for C, cw in self.candidates:
+            LogisticProbe(C=C, tol=tol, max_iter=max_iter, class_weight=cw)       # (its checks)
+        if int(max_problems) < 1:
+            raise ValueError("max_problems must be at least 1")
+        self.cv, self.tol, self.max_iter = cv, float(tol), int(max_iter)
+        self.refit, self.max_problems = bool(refit), int(max_problems)
+        self.cv_scores_ = self.best_estimator_ = None
+
+    @staticmethod
+    def logspace(n, low, high, class_weight=None):
+        """n candidates with C spaced evenly in the logarithm from low to high (both included), one ``class_weight``."""
+        if int(n) < 1 or not 0 < low <= high:
+            raise ValueError("need n >= 1 and 0 < low <= high")
+        Cs = np.exp(np.linspace(np.log(low), np.log(high), int(n))).clip(low, high)
+        Cs[0], Cs[-1] = low, high        # (exp(log(x)) may miss x by an ulp; n = 1: high)
+        return [(float(C), class_weight) for C in Cs]
+
+    def fit(self, data, labels=None, rows_per_pass=65536, keep_rows=False):
+        rows = _Rows(data, rows_per_pass, keep_rows)
+        y = _labels_of(data, labels, rows.n)
+        classes, _, _ = _class_indexes(y)
+        idx = torch.searchsorted(classes, y)                  # class k is classes_[k], for two classes too
+        K = int(classes.numel())
+        Kp = 1 if K == 2 else K                               # rows of a reported classifier
+        fold, ids, train_counts = _folds_of(self.cv, idx, K)
+        all_counts = torch.bincount(idx, minlength=K)
+        nc, nf = len(self.candidates), len(ids)
+        per = nf + int(self.refit)
+        # one classifier (group) per (candidate, fold), then per candidate one with nothing held out
+        layout = [(c, f) for c in range(nc) for f in range(per)]
+        step = max(self.max_problems // K, 1)
+        device = rows.device
+        Sums = _DeviceSoftmaxGridSums if device.type == "cuda" else _HostSoftmaxGridSums
+        coef = torch.empty((nc, per, Kp, rows.dim), dtype=torch.float32, device=device)
+        icpt = torch.empty((nc, per, Kp), dtype=torch.float32, device=device)
+        objective = torch.empty((nc, per), dtype=torch.float64)
+        converged = torch.empty((nc, per), dtype=torch.bool)
+        self.n_passes_ = 0
+        try:
+            for at in range(0, len(layout), step):
+                batch = layout[at:at + step]
+                held = torch.tensor([ids[f] if f < nf else _NO_FOLD for _, f in batch], dtype=torch.int64)
+                cw = torch.stack([_class_weights(self.candidates[c][1], classes.numpy(), train_counts[f] if f < nf else all_counts)
+                                  for c, f in batch])
+                scale = torch.tensor([self.candidates[c][0] / 2 if K == 2 else self.candidates[c][0] for c, _ in batch],
+                                     dtype=torch.float64)
+                sums = Sums(rows, idx, fold, held, cw, scale)
+                W, b, fv, conv = _newton_cg_joint_groups(sums, rows.dim, rows.n, device, self.tol, self.max_iter)
+                self.n_passes_ += sums.n_passes
+                if K == 2:               # as LogisticProbe: w = W_1 - W_0 minimises the binomial objective, which is 2 f
+                    W, b, fv = W[:, 1:] - W[:, :1], b[:, 1:] - b[:, :1], 2.0 * fv
+                for g, (c, f) in enumerate(batch):
+                    coef[c, f], icpt[c, f] = W[g], b[g]
+                    objective[c, f], converged[c, f] = float(fv[g]), bool(conv[g])
+            # one scoring walk, shared with LinearProbeCV (two classes: its one-column rule, whose class 0 is classes_[1])
+            score_held = torch.tensor(ids, dtype=torch.int64).repeat(nc)
+            right = LinearProbeCV._score(rows, coef[:, :nf].reshape(nc * nf * Kp, rows.dim), icpt[:, :nf].reshape(-1),
+                                         1 - idx if K == 2 else idx, fold, score_held, Kp)
+            self.n_passes_ += 1
+        finally:
+            rows.close()
+        n_held = torch.stack([(fold == f).sum() for f in ids]).double()
+        self.cv_scores_ = right.reshape(nc, nf).double() / n_held[None, :]
+        self.mean_scores_ = self.cv_scores_.mean(1)
+        self.best_index_ = int(self.mean_scores_.argmax())                       # the first maximum
+        self.best_params_ = dict(zip(("C", "class_weight"), self.candidates[self.best_index_]))
+        self.fold_coef_, self.fold_intercept_ = coef[:, :nf].contiguous(), icpt[:, :nf].contiguous()
+        self.classes_, self.folds_, self.converged_ = classes.numpy(), list(ids), converged
+        self.best_estimator_ = None
+        if self.refit:
+            best = LogisticProbe(C=self.best_params_["C"], tol=self.tol, max_iter=self.max_iter,
+                                 class_weight=self.best_params_["class_weight"])
+            best._set(coef[self.best_index_, nf].clone(), icpt[self.best_index_, nf].clone(), classes, self.n_passes_,
+                      float(objective[self.best_index_, nf]), bool(converged[self.best_index_, nf]))
+            self.best_estimator_ = best
+        if not bool(converged.all()):
+            warnings.warn(f"LogisticProbeCV: {int((~converged).sum())} of {converged.numel()} classifiers stopped short of "
+                          f"tol = {self.tol} after {self.max_iter} Newton steps", RuntimeWarning)
+        return self

@@ -33,9 +33,20 @@ pass) and K = 1000 (the row-statistics kernel first), in gradient and in Hessian
 (a') streamed: ``take`` of a decode group, then ``lla_softmax_pass(accumulate=1)``, against the ``take`` calls alone.
 Bar, as above: the median of (a) may not exceed the median of (c) by more than the spread of (c)'s own runs.
 
+``--softmax-grid`` measures the cross-validated softmax regression instead: K = 10, 8 candidates x 5 folds =
+40 classifiers (14 tiles), in gradient and in Hessian-vector mode,
+
+(g)  one ``lla_softmax_grid_pass`` over all N rows, every classifier leaving its own fold out,
+(s)  what the library offered before: 40 ``lla_softmax_pass(K = 10)`` calls, each over a contiguous copy of that fold's
+     training rows (the copies are made outside the timed region),
+both resident and streamed; (g) is checked against (s) first.  Bar: the median of (g) lies below the median of (s) by more
+than (s)'s spread, resident and streamed.  Reported, not gated: ``LogisticProbeCV.fit`` at the STL10 shape against the same
+search as a loop of ``LogisticProbe.fit``, and the pass time of the K = 1000 fallback (``lla_softmax_pass`` per classifier).
+
 usage (GPU box): python tools/probe_bench.py [--records 131072] [--reps 3] [--out profiles/linear_probe.txt]
                  python tools/probe_bench.py --grid --out profiles/linear_probe_cv.txt
                  python tools/probe_bench.py --softmax --out profiles/logistic_probe.txt
+                 python tools/probe_bench.py --softmax-grid --out profiles/logistic_probe_cv.txt
 """
 import argparse
 import os
@@ -50,7 +61,7 @@ import torch  # noqa: E402
 
 import hubconf  # noqa: E402
 from latents_bench import interleaved, med  # noqa: E402
-from lossyless_amd import LinearProbe, LinearProbeCV, LogisticProbe, _lib  # noqa: E402
+from lossyless_amd import LinearProbe, LinearProbeCV, LogisticProbe, LogisticProbeCV, _lib  # noqa: E402
 
 
 def grid_arms(args, say, dev, ds, Z, g):
@@ -304,6 +315,157 @@ def softmax_arms(args, say, dev, ds, Z, g):
         say("    scikit-learn is not installed here: no host reference")
 
 
+def softmax_grid_arms(args, say, dev, ds, Z, g):
+    """The --softmax-grid table (module docstring)."""
+    L, st = _lib.lib(), _lib.stream_ptr(dev)
+    N, C = Z.shape
+    group = 65536
+    buf = torch.empty((min(group, N), C), dtype=torch.float32, device=dev)
+    pieces = lambda idx: [idx[i:i + group] for i in range(0, idx.numel(), group)]       # noqa: E731
+    K, n_cand, n_fold = 10, 8, 5
+    G = n_cand * n_fold
+    J = G * K
+    inner = args.inner or 10
+    y = torch.randint(0, K, (N,), generator=g).to(torch.int32).to(dev)
+    fold = (torch.arange(N) % n_fold).to(torch.int32).to(dev)
+    W = (torch.randn(J, C, generator=g) * 0.03).to(dev)
+    b = (torch.randn(J, generator=g) * 0.1).to(dev)
+    V = torch.randn(J, C, generator=g).to(dev)
+    vb = torch.randn(J, generator=g).to(dev)
+    # classifier (candidate c, fold f) is group c n_fold + f; candidate c weighs class k by 1 + (c + k) / 16
+    held = torch.arange(n_fold, dtype=torch.int32).repeat(n_cand).to(dev)
+    cw = (1.0 + (torch.arange(n_cand)[:, None, None] + torch.arange(K)[None, None, :]) / 16.0).expand(n_cand, n_fold, K) \
+        .reshape(G, K).contiguous().to(dev)
+    ws = torch.empty(int(L.lla_softmax_grid_pass_workspace_bytes(C, K, G)), dtype=torch.uint8, device=dev)
+    ws1 = torch.empty(int(L.lla_softmax_pass_workspace_bytes(C, K, N)), dtype=torch.uint8, device=dev)
+    oW, ob, ol = torch.empty((J, C), device=dev), torch.empty(J, device=dev), torch.empty(J, dtype=torch.float64, device=dev)
+    sW, sb, sl = torch.empty((J, C), device=dev), torch.empty(J, device=dev), torch.empty(J, dtype=torch.float64, device=dev)
+    train_idx = [torch.nonzero(fold != f)[:, 0] for f in range(n_fold)]
+    train_rows = [Z[idx] for idx in train_idx]
+    train_y = [y[idx].contiguous() for idx in train_idx]
+    idxs = [(g0, torch.arange(g0, min(g0 + group, N), device=dev)) for g0 in range(0, N, group)]
+    train_pieces = [[(p, y[p].contiguous()) for p in pieces(idx)] for idx in train_idx]
+    tiles = -(-G // (32 // K))
+    for hv in (False, True):
+        Vm, vbm = (V, vb) if hv else (None, None)
+
+        def grid(rows=Z, labels=y, folds=fold, acc=0):
+            rc = L.lla_softmax_grid_pass(_lib.ptr(rows), _lib.LLA_Z_F32, C, _lib.ptr(labels), _lib.ptr(folds), rows.shape[0], C,
+                                         _lib.ptr(W), _lib.ptr(b), _lib.ptr(Vm), _lib.ptr(vbm), K, G, C, _lib.ptr(held),
+                                         _lib.ptr(cw), _lib.ptr(oW), _lib.ptr(ob), _lib.ptr(ol), acc, _lib.ptr(ws), st)
+            _lib.check(rc, "lla_softmax_grid_pass")
+
+        def one(rows, labels, gi, acc):
+            at = gi * K
+            rc = L.lla_softmax_pass(_lib.ptr(rows), _lib.LLA_Z_F32, C, _lib.ptr(labels), rows.shape[0], C, _lib.ptr(W[at:at + K]),
+                                    _lib.ptr(b[at:at + K]), _lib.ptr(None if Vm is None else Vm[at:at + K]),
+                                    _lib.ptr(None if vbm is None else vbm[at:at + K]), K, C, _lib.ptr(cw[gi]),
+                                    _lib.ptr(sW[at:at + K]), _lib.ptr(sb[at:at + K]), _lib.ptr(sl[at:at + K]), acc, _lib.ptr(ws1), st)
+            _lib.check(rc, "lla_softmax_pass")
+
+        def loop():
+            for gi in range(G):
+                one(train_rows[gi % n_fold], train_y[gi % n_fold], gi, 0)
+
+        def grid_streamed():
+            oW.zero_(), ob.zero_(), ol.zero_()
+            for g0, idx in idxs:
+                rows = ds.take(idx, out=buf[:idx.numel()], check=False)
+                grid(rows, y[g0:g0 + idx.numel()], fold[g0:g0 + idx.numel()], 1)
+
+        def loop_streamed():
+            sW.zero_(), sb.zero_(), sl.zero_()
+            for gi in range(G):
+                for idx, labels in train_pieces[gi % n_fold]:
+                    one(ds.take(idx, out=buf[:idx.numel()], check=False), labels, gi, 1)
+
+        # the same sums from both paths before anything is timed (fp32 in different orders: relative to the largest sum)
+        grid(), loop()
+        torch.cuda.synchronize(dev)
+        scale = float(sW.abs().max())
+        err = float((oW - sW).abs().max()) / scale
+        lerr = 0.0 if hv else float(((ol - sl).abs() / sl.abs().clamp_min(1e-30)).max())
+        assert err < 1e-4 and lerr < 1e-5, f"arms disagree: {err:.2e} {lerr:.2e}"
+        keep = oW.clone()
+        grid_streamed()
+        torch.cuda.synchronize(dev)
+        assert float((oW - keep).abs().max()) / scale < 1e-4, "the streamed grid pass disagrees"
+        arms = {"(g) one lla_softmax_grid_pass, rows resident": grid, f"(s) {G} lla_softmax_pass calls, rows resident": loop,
+                "(g') streamed: take + lla_softmax_grid_pass": grid_streamed,
+                f"(s') streamed: {G} x (take + lla_softmax_pass)": loop_streamed}
+        times = interleaved(arms, inner, args.reps, dev)
+        say()
+        say(f"{'Hessian-vector' if hv else 'gradient'} mode, K = {K}, {n_cand} candidates x {n_fold} folds = {G} classifiers ({tiles} "
+            f"tiles): ms per pass over {N} rows, device events over {inner} back-to-back passes, {args.reps} interleaved runs   "
+            f"(max |(g) - (s)| / max |(s)| = {err:.1e})")
+        for k, ts in times.items():
+            runs = "  ".join(f"{x:9.4f}" for x in ts)
+            say(f"    {k:50s} {runs}   median {med(ts):9.4f} ms")
+        names = list(times)
+        for gk, sk in zip(names[0::2], names[1::2]):
+            gt, stt = times[gk], times[sk]
+            spread = max(stt) - min(stt)
+            verdict = "MET" if med(gt) < med(stt) - spread else "MISSED"
+            say(f"    {gk[:4].strip()} / {sk[:4].strip()} medians = {med(gt) / med(stt):.3f};  spread of {sk[:4].strip()} = {spread:.4f} ms;  "
+                f"{sk[:4].strip()} - {gk[:4].strip()} = {med(stt) - med(gt):+.4f} ms   -> bar {verdict}")
+    del train_rows, train_pieces
+
+    # the K > 32 fallback of LogisticProbeCV: lla_softmax_pass per classifier over ALL rows, held-out rows relabelled -1
+    K2, G2 = 1000, 4
+    y2 = torch.randint(0, K2, (N,), generator=g).to(torch.int32).to(dev)
+    yg = torch.where(fold[None, :] % 2 == torch.arange(G2, device=dev)[:, None] % 2, -1, y2[None, :]).to(torch.int32).contiguous()
+    W2, b2 = (torch.randn(G2, K2, C, generator=g) * 0.03).to(dev), (torch.randn(G2, K2, generator=g) * 0.1).to(dev)
+    o2W, o2b = torch.empty((G2, K2, C), device=dev), torch.empty((G2, K2), device=dev)
+    o2l = torch.empty((G2, K2), dtype=torch.float64, device=dev)
+    ws2 = torch.empty(int(L.lla_softmax_pass_workspace_bytes(C, K2, N)), dtype=torch.uint8, device=dev)
+
+    def fallback():
+        for gi in range(G2):
+            rc = L.lla_softmax_pass(_lib.ptr(Z), _lib.LLA_Z_F32, C, _lib.ptr(yg[gi]), N, C, _lib.ptr(W2[gi]), _lib.ptr(b2[gi]), None,
+                                    None, K2, C, None, _lib.ptr(o2W[gi]), _lib.ptr(o2b[gi]), _lib.ptr(o2l[gi]), 0, _lib.ptr(ws2), st)
+            _lib.check(rc, "lla_softmax_pass")
+    ts = interleaved({"fallback": fallback}, 2, args.reps, dev)["fallback"]
+    say()
+    say(f"K = {K2} fallback (2 candidates x 2 folds = {G2} lla_softmax_pass calls over all {N} rows, gradient mode): "
+        f"{'  '.join(f'{x:9.4f}' for x in ts)}   median {med(ts):9.4f} ms per pass   (reported, not gated)")
+
+    # whole call at the STL10 shape: the search in shared passes against the same search as a loop of fits
+    n, k = 5000, 10
+    labels = torch.arange(n) % k
+    mu = torch.randn(k, C, generator=g) * 0.1
+    Xd = (mu[labels] + torch.randn(n, C, generator=g) * 0.5).to(dev)
+    cands = LogisticProbeCV.logspace(8, 1e-3, 10.0)
+    LogisticProbeCV(cands[:2], cv=5).fit(Xd[:512], labels[:512])            # (code objects loaded)
+    torch.cuda.synchronize(dev)
+    t0 = time.perf_counter()
+    cv = LogisticProbeCV(cands, cv=5).fit(Xd, labels)
+    torch.cuda.synchronize(dev)
+    cv_s = time.perf_counter() - t0
+    fold5 = torch.empty(n, dtype=torch.int64)
+    for c in range(k):                                                   # the r-th row of a class goes to fold r % 5
+        at = torch.nonzero(labels == c)[:, 0]
+        fold5[at] = torch.arange(at.numel()) % 5
+    t0 = time.perf_counter()
+    passes, scores = 0, torch.zeros(len(cands), 5, dtype=torch.float64)
+    for c, (Cw, cwt) in enumerate(cands):
+        for f in range(5):
+            tr, te = torch.nonzero(fold5 != f)[:, 0].to(dev), torch.nonzero(fold5 == f)[:, 0].to(dev)
+            p = LogisticProbe(C=Cw, class_weight=cwt).fit(Xd[tr], labels[tr.cpu()])
+            scores[c, f] = p.score(Xd[te], labels[te.cpu()])
+            passes += p.n_passes_ + 1
+    best = int(scores.mean(1).argmax())
+    p = LogisticProbe(C=cands[best][0], class_weight=cands[best][1]).fit(Xd, labels)
+    torch.cuda.synchronize(dev)
+    loop_s = time.perf_counter() - t0
+    say()
+    say(f"STL10-shaped search ({n} x {C}, K = {k}, 8 candidates x 5 folds + refit): LogisticProbeCV.fit {cv_s:.3f} s wall, "
+        f"{cv.n_passes_} passes, all converged {bool(cv.converged_.all())}, best {cv.best_index_} "
+        f"(mean accuracy {float(cv.mean_scores_[cv.best_index_]):.4f})")
+    say(f"    the same search as a loop of LogisticProbe.fit (40 fits + scores + 1 refit): {loop_s:.3f} s wall, {passes + p.n_passes_} "
+        f"passes, best {best} (mean accuracy {float(scores.mean(1)[best]):.4f}); max |score difference| "
+        f"{float((scores - cv.cv_scores_).abs().max()):.4f}   (reported, not gated)")
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--records", type=int, default=131072)
@@ -311,6 +473,8 @@ def main():
     ap.add_argument("--inner", type=int, default=0, help="calls per timed window (0: 40 at K = 10, 8 at K = 1000)")
     ap.add_argument("--grid", action="store_true", help="measure the cross-validated search (lla_svm_grid_pass) instead")
     ap.add_argument("--softmax", action="store_true", help="measure the softmax-regression pass (lla_softmax_pass) instead")
+    ap.add_argument("--softmax-grid", action="store_true",
+                    help="measure the cross-validated softmax regression (lla_softmax_grid_pass) instead")
     ap.add_argument("--out", default=None)
     args = ap.parse_args()
     if not torch.cuda.is_available():
@@ -345,8 +509,8 @@ def main():
     buf = torch.empty((min(group, N), C), dtype=torch.float32, device=dev)
     idxs = [(g0, torch.arange(g0, min(g0 + group, N), device=dev)) for g0 in range(0, N, group)]
 
-    if args.grid or args.softmax:
-        (grid_arms if args.grid else softmax_arms)(args, say, dev, ds, Z, g)
+    if args.grid or args.softmax or args.softmax_grid:
+        (grid_arms if args.grid else softmax_grid_arms if args.softmax_grid else softmax_arms)(args, say, dev, ds, Z, g)
         if args.out:
             with open(args.out, "w") as fh:
                 fh.write("\n".join(lines) + "\n")

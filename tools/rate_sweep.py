@@ -72,6 +72,10 @@ def main():
                          "class_weight, 5-fold up to 50 000 rows, one train / validation split above) with "
                          "lossyless_amd.LinearProbeCV on the device (adds linear_probe_cv_best, _validation_accuracy, "
                          "_accuracy and _fit_s)")
+    ap.add_argument("--device-logistic-cv", type=int, default=0, metavar="N",
+                    help="also run CLIP's linear-probe protocol (softmax regression, N values of C log-spaced in [1e-3, 10], the "
+                         "same folds as --device-probe-cv) with lossyless_amd.LogisticProbeCV on the device (adds "
+                         "logistic_probe_cv_best, _validation_accuracy, _accuracy and _fit_s)")
     args = ap.parse_args()
 
     weights = os.environ.get("LOSSYLESS_CLIP_WEIGHTS", "synthetic")
@@ -147,6 +151,17 @@ def main():
                                  linear_probe_cv_best=dict(cv.best_params_),
                                  linear_probe_cv_validation_accuracy=float(cv.mean_scores_[cv.best_index_]),
                                  linear_probe_cv_accuracy=float(cv.best_estimator_.score(comp.open_dataset(ft), np.asarray(Yt))))
+                if args.device_logistic_cv:
+                    from lossyless_amd import LogisticProbeCV
+                    folds = 5 if n <= 50000 else np.where(np.arange(n) % 10 == 0, 0, -1)
+                    t0 = time.perf_counter()
+                    cv = LogisticProbeCV(LogisticProbeCV.logspace(args.device_logistic_cv, 1e-3, 10.0), cv=folds)
+                    cv.fit(comp.open_dataset(f), np.asarray(Y))
+                    torch.cuda.synchronize()
+                    probe.update(logistic_probe_cv_fit_s=round(time.perf_counter() - t0, 3),
+                                 logistic_probe_cv_best=dict(cv.best_params_),
+                                 logistic_probe_cv_validation_accuracy=float(cv.mean_scores_[cv.best_index_]),
+                                 logistic_probe_cv_accuracy=float(cv.best_estimator_.score(comp.open_dataset(ft), np.asarray(Yt))))
         print(json.dumps(dict(rate_point=name, data=data, clip_weights=weights, images=n,
                               call=("Dataset(transform=RawRGB) -> compress_dataset(dataset, file, label_file, "
                                     f"dict(batch_size={args.batch}, num_workers={args.workers}))") if shaped
