@@ -619,6 +619,51 @@ int lla_softmax_grid_pass(const void *z, int z_dtype, int ld_z, const int32_t *y
                           const int32_t *group_held, const float *group_class_weight, float *out_W, float *out_b,
                           double *out_loss, int accumulate, void *workspace, void *stream);
 
+/* ---- A training step of the reference's MLP predictor (csrc/mlp.hip): what lla_gemm_f32, the forward half of an fp32
+ * Linear layer, lacks.  Everything is fp32, row-major, pitches in elements; v_mfma_f32_32x32x2_f32 (exact fp32 products,
+ * fp32 accumulation), no floating-point atomics, the order of every sum fixed by the shape alone (the same inputs give the
+ * same bits); refusals are LLA_EINVAL, decided before any device call; a zero-sized call is LLA_OK with no launch. */
+
+/* The input gradient of a Linear layer, with the ReLU backward of the layer below in its epilogue -- what autograd runs for
+ * `Linear -> ReLU` of the reference's MLP (lossyless/architectures.py:141-155, trained by lossyless/predictors.py:38-232):
+ *   dX[M][K] = dY[M][N] W[N][K],  then dX[i][k] = 0 where H[i][k] > 0 does not hold  (H == NULL: no mask)
+ * H [M][K] is the forward OUTPUT of the layer below (relu(a) > 0 iff a > 0; -0.0 and 0.0 mask).  The reduction runs over N:
+ * N % 4 == 0 (the caller pads the class dimension with zero columns), K % 4 == 0; ldy >= N, ldw >= K, ldh >= K, ldx >= K;
+ * ldy, ldh, ldx multiples of 4 and dY, H, dX 16-byte aligned.  Columns K .. ldx-1 of dX are not written. */
+int lla_gemm_f32_nn(const float *dY, int ldy, const float *W, int ldw, const float *H, int ldh, float *dX, int ldx,
+                    int M, int N, int K, void *stream);
+/* The weight and bias gradients of a Linear layer (the same lines of the reference):
+ *   dW[N][K] = dY[M][N]^T X[M][K];   db != NULL: db[n] = sum_i dY[i][n], added in row order.
+ * The reduction runs over the batch M, any M >= 1 (the staged operands of a ragged last chunk are zero-filled).  One
+ * workgroup owns an output tile over all of M: every element is ONE fma chain in row order, there is no workspace and no
+ * second kernel.  N % 4 == 0, K % 4 == 0; ldy >= N, ldx >= K, ldw >= K; ldy, ldx multiples of 4 and dY, X 16-byte aligned.
+ * Columns K .. ldw-1 of dW are not written. */
+int lla_gemm_f32_tn(const float *dY, int ldy, const float *X, int ldx, float *dW, int ldw, float *db, int M, int N, int K,
+                    void *stream);
+/* Softmax cross-entropy of a minibatch and its gradient with respect to the logits (F.cross_entropy and its backward:
+ * lossyless/predictors.py:172-186; the accuracy of :196-204):
+ *   logits [B][ld], the first K columns real;  y [B] int32;  with mx_i = max_k s_ik, se_i = sum_k exp(s_ik - mx_i):
+ *   dlogits[i][k] = scale (exp(s_ik - mx_i) / se_i - [y_i = k]) for k < K, and exactly 0 for K <= k < Kpad
+ *   *out_loss (double)   = sum_i (mx_i + log se_i - s_{i, y_i})
+ *   *out_correct (int32) = the rows whose argmax (the lowest index on ties, as torch.argmax) equals their label.
+ * A row whose label lies outside [0, K) gets a zero residual and counts in neither output.  The row maximum is always
+ * subtracted; expf / logf, no fast variants; the probability is a quotient, so its error does not grow with |lse| as
+ * exp(s - lse) does.  `scale` is the caller's: 1 / (rows of the minibatch with a valid label).  One wave per row; the row
+ * losses go through the workspace (lla_softmax_xent_workspace_bytes(B) bytes, 4-byte aligned) and are added in a fixed
+ * order in double.  1 <= K <= 1024, K <= Kpad <= ldd, K <= ld.  Columns Kpad .. ldd-1 of dlogits are not written. */
+size_t lla_softmax_xent_workspace_bytes(int B);
+int lla_softmax_xent(const float *logits, int ld, const int32_t *y, int B, int K, int Kpad, float scale, float *dlogits,
+                     int ldd, double *out_loss, int32_t *out_correct, void *workspace, void *stream);
+/* One fused update over flat buffers p, g, m, v [n] with the semantics of torch.optim.AdamW (the reference's optimiser:
+ * lossyless/predictors.py:206-232, config/optimizer/Adam.yaml / AdamW.yaml):
+ *   p <- p (1 - lr wd);  m <- beta1 m + (1 - beta1) g;  v <- beta2 v + (1 - beta2) g^2;
+ *   p <- p - (lr / bias_correction1) m / (sqrt(v) / sqrt(bias_correction2) + eps)
+ * bias_correction1 = 1 - beta1^t and bias_correction2 = 1 - beta2^t are the host's, in double.  weight_decay = 0 is plain
+ * Adam.  m and v are formed in double from the fp32 operands and rounded once; 16-byte loads and stores with a scalar tail
+ * for n % 4.  All four pointers 16-byte aligned; lr, eps, weight_decay >= 0, betas in [0, 1), corrections > 0. */
+int lla_adamw_step(float *p, const float *g, float *m, float *v, long long n, double lr, double beta1, double beta2,
+                   double eps, double weight_decay, double bias_correction1, double bias_correction2, void *stream);
+
 /* out[n][H][W][ldc] (first cout channels) = relu(conv3x3(in, stride 1, pad 1) + bias) as an IMPLICIT GEMM:
  * `in` is NHWC fp16 [n][H][W][pitch] (first cin channels used; cin % 64 == 0, or cin == 32), weights fp16
  * [cout][K] with K = 9 cin rounded up to a multiple of 64 (zero padded) in the order (kh, kw, c), bias fp32

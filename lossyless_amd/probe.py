@@ -1211,3 +1211,365 @@ class LogisticProbeCV:
             warnings.warn(f"LogisticProbeCV: {int((~converged).sum())} of {converged.numel()} classifiers stopped short of "
                           f"tol = {self.tol} after {self.max_iter} Newton steps", RuntimeWarning)
         return self
+
+
+# ---------------------------------------------------------------------- the reference's MLP predictor
+def _mlp_init(dims, generator):
+    """``weights_init`` of the reference (lossyless/helpers.py:153-178) for the Linear layers dims[l] -> dims[l + 1]:
+    ``kaiming_uniform_(nonlinearity="relu")`` -- U(-b, b), b = sqrt(2) sqrt(3 / fan_in) -- on every weight, drawn in fp32 on the
+    CPU from ``generator`` in layer order, and zero biases -> (weights, biases)."""
+    Ws, bs = [], []
+    for fan_in, fan_out in zip(dims[:-1], dims[1:]):
+        bound = (2.0 ** 0.5) * (3.0 / fan_in) ** 0.5
+        Ws.append(torch.empty((fan_out, fan_in), dtype=torch.float32).uniform_(-bound, bound, generator=generator))
+        bs.append(torch.zeros(fan_out, dtype=torch.float32))
+    return Ws, bs
+
+
+class _Adam:
+    """The hyper-parameters of a fit and the two bias corrections of step t, in double on the host (``lla_adamw_step``)."""
+
+    def __init__(self, lr, weight_decay, betas, eps):
+        self.lr, self.wd, self.b1, self.b2, self.eps = float(lr), float(weight_decay), float(betas[0]), float(betas[1]), float(eps)
+
+    def corrections(self, t):
+        return 1.0 - self.b1 ** t, 1.0 - self.b2 ** t
+
+
+class _TwinMLP:
+    """The float64 twin of a training step: forward, softmax cross-entropy, backward and AdamW written out by hand, formula
+    by formula what the kernels of csrc/mlp.hip compute -- no autograd, so that it can be tested against autograd.  The CPU
+    path of ``MLPProbe`` and the oracle of its GPU tests."""
+
+    def __init__(self, Ws, bs, adam):
+        self.Ws, self.bs = [W.to(torch.float64).clone() for W in Ws], [b.to(torch.float64).clone() for b in bs]
+        self.adam, self.t = adam, 0
+        self.m = [torch.zeros_like(p) for p in self.Ws + self.bs]
+        self.v = [torch.zeros_like(p) for p in self.Ws + self.bs]
+
+    def forward(self, x, pre=None):
+        """-> (logits, [x, h_1, ..., h_L]): h = relu(h W^T + b) (lla_gemm_f32, relu = 1), then the last Linear.  ``pre``, a
+        list, receives the hidden pre-activations."""
+        hs = [x.to(torch.float64)]
+        for W, b in zip(self.Ws[:-1], self.bs[:-1]):
+            a = hs[-1] @ W.T + b
+            if pre is not None:
+                pre.append(a)
+            hs.append(torch.where(a > 0, a, torch.zeros((), dtype=torch.float64)))
+        return hs[-1] @ self.Ws[-1].T + self.bs[-1], hs
+
+    @staticmethod
+    def xent(s, y):
+        """lla_softmax_xent -> (residual with scale = 1 / rows, sum of the row losses, rows got right)."""
+        mx = s.max(1, keepdim=True).values
+        e = torch.exp(s - mx)
+        se = e.sum(1, keepdim=True)
+        hot = torch.zeros_like(s).scatter_(1, y[:, None], 1.0)
+        loss = ((mx - s.gather(1, y[:, None])) + torch.log(se)).sum()
+        return (e / se - hot) * (1.0 / s.shape[0]), float(loss), int((s.argmax(1) == y).sum())
+
+    def gradients(self, x, y):
+        """-> (loss sum, rows right, dW per layer, db per layer) of the mean cross-entropy of the minibatch."""
+        s, hs = self.forward(x)
+        delta, loss, right = self.xent(s, y)
+        gW, gb = [None] * len(self.Ws), [None] * len(self.Ws)
+        for l in range(len(self.Ws) - 1, -1, -1):
+            gW[l], gb[l] = delta.T @ hs[l], delta.sum(0)                     # lla_gemm_f32_tn
+            if l > 0:                                                        # lla_gemm_f32_nn with the ReLU mask
+                delta = torch.where(hs[l] > 0, delta @ self.Ws[l], torch.zeros((), dtype=torch.float64))
+        return loss, right, gW, gb
+
+    def step(self, x, y):
+        loss, right, gW, gb = self.gradients(x, y)
+        a = self.adam
+        self.t += 1
+        bc1, bc2 = a.corrections(self.t)
+        for p, g, m, v in zip(self.Ws + self.bs, gW + gb, self.m, self.v):   # lla_adamw_step
+            p.mul_(1.0 - a.lr * a.wd)
+            m.copy_(a.b1 * m + (1.0 - a.b1) * g)
+            v.copy_(a.b2 * v + (1.0 - a.b2) * g * g)
+            p.sub_((a.lr / bc1) * m / (v.sqrt() / bc2 ** 0.5 + a.eps))
+        return loss, right
+
+    def epoch_totals(self, sums):
+        return float(sum(s[0] for s in sums)), int(sum(s[1] for s in sums))
+
+    def parameters(self, n_out):
+        return [W.clone() for W in self.Ws], [b.clone() for b in self.bs]
+
+
+def _f32_rows(z, C):
+    """fp32 rows as the GEMMs want them: unit column stride, a pitch that is a multiple of 4, 16-byte aligned -> (z, pitch)."""
+    if z.dtype != torch.float32:
+        z = z.float()
+    if z.stride(1) != 1 or (z.shape[0] > 1 and (z.stride(0) % 4 or z.stride(0) < C)) or z.data_ptr() % 16:
+        z = z.contiguous()
+    return z, (int(z.stride(0)) if z.shape[0] > 1 else C)
+
+
+class _DeviceMLP:
+    """The same step on the device.  Parameters, gradients and the two moments each live in ONE flat fp32 buffer (layer l's
+    weight [out_l][in_l], then its bias; the class dimension padded to a multiple of 8 with zero rows that never receive a
+    non-zero gradient), so the update is one ``lla_adamw_step``.  Per step: ``lla_gemm_f32`` forward (relu = 1 on the hidden
+    layers: the only activations kept), ``lla_softmax_xent``, then from the last layer ``lla_gemm_f32_tn`` (dW, db) and
+    ``lla_gemm_f32_nn`` with the ReLU mask (not for the first layer).  Nothing is read back during an epoch."""
+
+    def __init__(self, Ws, bs, adam, device, max_rows, n_classes, max_steps=0):
+        self.L, self.device, self.adam, self.t = _lib.lib(), device, adam, 0
+        self.K = int(n_classes)
+        self.dims = [int(Ws[0].shape[1])] + [int(W.shape[0]) for W in Ws[:-1]] + [-(-self.K // 8) * 8]
+        if any(d % 8 for d in self.dims[:-1]):
+            raise ValueError(f"the device path needs layer widths that are multiples of 8, got {self.dims[:-1]}")
+        sizes = [o * i + o for i, o in zip(self.dims[:-1], self.dims[1:])]
+        self.n = sum(sizes)
+        self.p = torch.zeros(self.n, dtype=torch.float32, device=device)
+        self.W, self.b = self._views(self.p)
+        for l, (W, b) in enumerate(zip(Ws, bs)):
+            self.W[l][:W.shape[0]].copy_(W.to(torch.float32))
+            self.b[l][:b.shape[0]].copy_(b.to(torch.float32))
+        self.rows = max(int(max_rows), 1)
+        self.acts = [torch.empty((self.rows, d), dtype=torch.float32, device=device) for d in self.dims[1:]]
+        if max_steps:                        # a training engine: gradients, moments, residuals and the per-step sums
+            self.g, self.m, self.v = (torch.zeros(self.n, dtype=torch.float32, device=device) for _ in range(3))
+            self.gW, self.gb = self._views(self.g)
+            self.dlogits = torch.empty((self.rows, self.dims[-1]), dtype=torch.float32, device=device)
+            width = max(self.dims[1:-1])
+            self.delta = [torch.empty((self.rows, width), dtype=torch.float32, device=device) for _ in range(2)]
+            self.loss = torch.zeros(max_steps, dtype=torch.float64, device=device)
+            self.right = torch.zeros(max_steps, dtype=torch.int32, device=device)
+            self.ws = torch.empty(int(self.L.lla_softmax_xent_workspace_bytes(self.rows)), dtype=torch.uint8, device=device)
+
+    def _views(self, flat):
+        Ws, bs, at = [], [], 0
+        for i, o in zip(self.dims[:-1], self.dims[1:]):
+            Ws.append(flat[at:at + o * i].view(o, i))
+            bs.append(flat[at + o * i:at + o * i + o])
+            at += o * i + o
+        return Ws, bs
+
+    def forward(self, z, st):
+        """-> logits [rows, Kpad] (a view of the last activation buffer) of the fp32 rows z."""
+        z, ld = _f32_rows(z, self.dims[0])
+        n = int(z.shape[0])
+        src, n_layers = z, len(self.W)
+        for l in range(n_layers):
+            i, o = self.dims[l], self.dims[l + 1]
+            rc = self.L.lla_gemm_f32(_lib.ptr(src), ld, _lib.ptr(self.W[l]), i, _lib.ptr(self.b[l]), _lib.ptr(self.acts[l]), o,
+                                     n, o, i, int(l < n_layers - 1), st)
+            _lib.check(rc, "lla_gemm_f32")
+            src, ld = self.acts[l], o
+        self._input = z
+        return self.acts[-1][:n]
+
+    def step(self, z, y, slot):
+        """One training step on the minibatch (z, y int32 class indexes); its loss sum and rows right go to ``slot``."""
+        n = int(z.shape[0])
+        L, a, n_layers = self.L, self.adam, len(self.W)
+        with torch.cuda.device(self.device):
+            st = _lib.stream_ptr(self.device)
+            self.forward(z, st)
+            kpad = self.dims[-1]
+            rc = L.lla_softmax_xent(_lib.ptr(self.acts[-1]), kpad, _lib.ptr(y), n, self.K, kpad, 1.0 / n, _lib.ptr(self.dlogits),
+                                    kpad, _lib.ptr(self.loss[slot:]), _lib.ptr(self.right[slot:]), _lib.ptr(self.ws), st)
+            _lib.check(rc, "lla_softmax_xent")
+            delta, ldd = self.dlogits, kpad
+            x0, ld0 = _f32_rows(self._input, self.dims[0])
+            for l in range(n_layers - 1, -1, -1):
+                i, o = self.dims[l], self.dims[l + 1]
+                below, ldb = (self.acts[l - 1], i) if l > 0 else (x0, ld0)
+                rc = L.lla_gemm_f32_tn(_lib.ptr(delta), ldd, _lib.ptr(below), ldb, _lib.ptr(self.gW[l]), i, _lib.ptr(self.gb[l]),
+                                       n, o, i, st)
+                _lib.check(rc, "lla_gemm_f32_tn")
+                if l > 0:
+                    out = self.delta[l % 2]
+                    rc = L.lla_gemm_f32_nn(_lib.ptr(delta), ldd, _lib.ptr(self.W[l]), i, _lib.ptr(below), ldb, _lib.ptr(out),
+                                           int(out.stride(0)), n, o, i, st)
+                    _lib.check(rc, "lla_gemm_f32_nn")
+                    delta, ldd = out, int(out.stride(0))
+            self.t += 1
+            bc1, bc2 = a.corrections(self.t)
+            rc = L.lla_adamw_step(_lib.ptr(self.p), _lib.ptr(self.g), _lib.ptr(self.m), _lib.ptr(self.v), self.n, a.lr, a.b1, a.b2,
+                                  a.eps, a.wd, bc1, bc2, st)
+            _lib.check(rc, "lla_adamw_step")
+        return slot
+
+    def epoch_totals(self, slots):
+        n = len(slots)
+        return float(self.loss[:n].sum()), int(self.right[:n].sum())
+
+    def parameters(self, n_out):
+        Ws = [W.clone() for W in self.W[:-1]] + [self.W[-1][:n_out].clone()]
+        return Ws, [b.clone() for b in self.b[:-1]] + [self.b[-1][:n_out].clone()]
+
+
+class MLPProbe(_Scores):
+    """``MLPProbe(hid_dim=2048, n_hid_layers=2, lr=1e-3, weight_decay=1e-5, betas=(0.9, 0.999), eps=1e-8, epochs=10,
+    batch_size=128, seed=0)``: the reference's non-linear predictor -- its ``MLP`` (lossyless/architectures.py:94-168) AT ITS
+    CLASS DEFAULTS (``norm_layer="identity"``, ``activation="ReLU"``, ``dropout_p=0``: Linear -> ReLU per hidden layer with
+    biases, then Linear), trained as lossyless/predictors.py:38-232 trains it: cross-entropy, AdamW (``weight_decay=0``: Adam)
+    on shuffled minibatches -- from a dataset that stays compressed in HBM.  It is NOT the reference's
+    ``config/architecture/mlp_probe.yaml``, which asks for batchnorm and dropout 0.2: ``norm_layer="batchnorm"``,
+    ``dropout_p > 0``, a learning-rate ``scheduler``, regression targets and fp16 rows are not built and raise ``ValueError``.
+
+    ``fit(data, labels=None, decode_group=65536)``
+        data    a ``CompressedLatents`` / ``HyperpriorLatents`` (its own labels unless ``labels`` is given), or a ``[N, C]``
+                tensor / array with ``labels``.  ``C % 8 == 0`` and ``hid_dim % 8 == 0``.
+        Initialisation is the reference's ``weights_init`` (``kaiming_uniform_(nonlinearity="relu")``, zero biases), drawn on
+        the CPU from ``torch.Generator().manual_seed(seed)`` in layer order; the same generator then gives every epoch its
+        order, ``torch.randperm(N, generator=g)``.  Latents are walked through ``data.batches(batch_size, shuffle=True,
+        generator=g, decode_group=decode_group)`` -- the random-access decode, a decode group per launch -- and a tensor is
+        indexed by the same permutation, so both see the same minibatches.  The last, shorter batch is kept (its loss is
+        the mean over its own rows).
+    GPU latents and CUDA tensors train in the kernels of csrc/mlp.hip (see ``_DeviceMLP``): deterministic, bit for bit.  CPU
+    latents and CPU tensors train in a float64 torch twin with a hand-written backward pass and AdamW (``_TwinMLP``).
+
+    After ``fit``: ``coefs_`` / ``intercepts_`` (one per Linear layer; fp32 on the device, float64 from the twin),
+    ``classes_`` (sorted unique labels; logit k belongs to ``classes_[k]``, for two classes too), ``loss_curve_`` (mean
+    training loss per epoch), ``accuracy_curve_``, ``n_steps_``.  ``decision_function`` returns the logits ``[N, K]`` (fp32
+    through ``lla_gemm_f32`` on the device, float64 on the CPU), ``predict_proba`` their softmax, ``predict`` labels,
+    ``score`` the mean accuracy.  ``state_dict()`` has the keys of the reference's ``MLP``: ``module.0.weight``,
+    ``module.0.bias``, ``module.4.weight``, ... (four modules per hidden block)."""
+
+    _PIECE = 8192            # rows per forward pass when scoring (activations of hid_dim floats per row)
+
+    def __init__(self, hid_dim=2048, n_hid_layers=2, lr=1e-3, weight_decay=1e-5, betas=(0.9, 0.999), eps=1e-8, epochs=10,
+                 batch_size=128, seed=0, norm_layer="identity", activation="ReLU", dropout_p=0, scheduler=None):
+        if norm_layer not in ("identity", None):
+            raise ValueError(f"norm_layer={norm_layer!r} is not built: MLPProbe is the reference's MLP with norm_layer='identity'")
+        if activation != "ReLU":
+            raise ValueError(f"activation={activation!r} is not built: MLPProbe is the reference's MLP with activation='ReLU'")
+        if dropout_p != 0:
+            raise ValueError("dropout_p > 0 is not built: MLPProbe is the reference's MLP with dropout_p=0")
+        if scheduler is not None:
+            raise ValueError("learning-rate schedulers are not built")
+        if int(hid_dim) < 8 or int(hid_dim) % 8:
+            raise ValueError(f"hid_dim must be a positive multiple of 8, got {hid_dim}")
+        if int(n_hid_layers) < 1 or int(epochs) < 1 or int(batch_size) < 1:
+            raise ValueError("n_hid_layers, epochs and batch_size must be at least 1")
+        if not lr > 0 or weight_decay < 0 or not eps >= 0 or not all(0 <= b < 1 for b in betas):
+            raise ValueError("need lr > 0, weight_decay >= 0, eps >= 0 and betas in [0, 1)")
+        self.hid_dim, self.n_hid_layers, self.epochs, self.batch_size = int(hid_dim), int(n_hid_layers), int(epochs), int(batch_size)
+        self.lr, self.weight_decay, self.betas, self.eps, self.seed = float(lr), float(weight_decay), tuple(betas), float(eps), int(seed)
+        self.coefs_ = self.intercepts_ = self.classes_ = None
+        self._packed = None
+
+    # ------------------------------------------------------------------ fit
+    @staticmethod
+    def _tensor(data):
+        t = data if isinstance(data, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(data))
+        if t.dim() != 2:
+            raise ValueError("data must be [N, C]")
+        if t.dtype == torch.float16:
+            raise ValueError("fp16 rows are not built for MLPProbe: pass float32")
+        if t.dtype not in (torch.float32, torch.float64) or (t.device.type == "cuda" and t.dtype != torch.float32):
+            t = t.to(torch.float32)
+        return t
+
+    def _epoch(self, data, rows, n, g, decode_group):
+        """-> (the epoch's order, an iterator over its minibatches of rows in that order)."""
+        bs = self.batch_size
+        if rows is None:                     # batches() draws randperm(n, generator=g) itself: the same draw from a copy of g
+            twin = torch.Generator()
+            twin.set_state(g.get_state())
+            order = torch.randperm(n, generator=twin)
+            walk = data.batches(bs, shuffle=True, generator=g, decode_group=decode_group)
+            return order, (b[0] if isinstance(b, tuple) else b for b in walk)
+        order = torch.randperm(n, generator=g)
+        group = max(int(decode_group) // bs, 1) * bs
+
+        def walk():
+            for g0 in range(0, n, group):
+                z = rows[order[g0:g0 + group].to(rows.device)]
+                for b0 in range(0, int(z.shape[0]), bs):
+                    yield z[b0:b0 + bs]
+        return order, walk()
+
+    def fit(self, data, labels=None, decode_group=65536):
+        if _is_latents(data):
+            rows, device, n, dim = None, data.device, len(data), int(data.z_dim)
+        else:
+            rows = self._tensor(data)
+            device, n, dim = rows.device, int(rows.shape[0]), int(rows.shape[1])
+        if dim % 8:
+            raise ValueError(f"in_dim must be a multiple of 8, got {dim}")
+        y = _labels_of(data, labels, n)
+        classes, _, _ = _class_indexes(y)
+        idx = torch.searchsorted(classes, y)                  # class k is classes_[k], for two classes too
+        K = int(classes.numel())
+        if K > 1024:
+            raise ValueError(f"lla_softmax_xent takes up to 1024 classes, got {K}")
+        g = torch.Generator().manual_seed(self.seed)
+        Ws, bs = _mlp_init([dim] + [self.hid_dim] * self.n_hid_layers + [K], g)
+        adam = _Adam(self.lr, self.weight_decay, self.betas, self.eps)
+        steps = -(-n // self.batch_size)
+        if device.type == "cuda":
+            engine = _DeviceMLP(Ws, bs, adam, device, min(self.batch_size, n), K, max_steps=steps)
+            idx = idx.to(torch.int32).to(device)
+        else:
+            engine = _TwinMLP(Ws, bs, adam)
+        self.loss_curve_, self.accuracy_curve_ = [], []
+        for _ in range(self.epochs):
+            order, walk = self._epoch(data, rows, n, g, decode_group)
+            y_epoch, at, sums = idx[order.to(idx.device)].contiguous(), 0, []
+            for z in walk:
+                bn = int(z.shape[0])
+                if device.type == "cuda":
+                    sums.append(engine.step(z, y_epoch[at:at + bn], len(sums)))
+                else:
+                    sums.append(engine.step(z, y_epoch[at:at + bn]))
+                at += bn
+            loss, right = engine.epoch_totals(sums)
+            self.loss_curve_.append(loss / n)
+            self.accuracy_curve_.append(right / n)
+        self.coefs_, self.intercepts_ = engine.parameters(K)
+        self.classes_, self.n_steps_, self._packed = classes.numpy(), engine.t, None
+        return self
+
+    # ------------------------------------------------------------------ predict
+    def _engine(self, dev):
+        """A forward-only device engine holding the fitted weights (cached per device)."""
+        if self._packed is None or self._packed[0] != str(dev):
+            eng = _DeviceMLP(self.coefs_, self.intercepts_, None, dev, self._PIECE, len(self.classes_))
+            self._packed = (str(dev), eng)
+        return self._packed[1]
+
+    def decision_function(self, data, rows_per_pass=65536):
+        if self.coefs_ is None:
+            raise RuntimeError("fit first")
+        if not _is_latents(data):
+            data = self._tensor(data)
+        rows = _Rows(data, rows_per_pass, False)
+        rows.first_pass = _is_latents(data)
+        K, C = len(self.classes_), int(self.coefs_[0].shape[1])
+        if rows.dim != C:
+            raise ValueError(f"data has {rows.dim} features, the probe was fitted on {C}")
+        try:
+            if rows.device.type == "cuda":
+                eng = self._engine(rows.device)
+                out = torch.empty((rows.n, K), dtype=torch.float32, device=rows.device)
+                with torch.cuda.device(rows.device):
+                    st = _lib.stream_ptr(rows.device)
+                    for g0, z in rows.groups():
+                        for r0 in range(0, int(z.shape[0]), self._PIECE):
+                            zz = z[r0:r0 + self._PIECE]
+                            out[g0 + r0:g0 + r0 + int(zz.shape[0])] = eng.forward(zz, st)[:, :K]
+                return out
+            twin = _TwinMLP([W.cpu() for W in self.coefs_], [b.cpu() for b in self.intercepts_], None)
+            parts = [twin.forward(z)[0] for _, z in rows.groups()]
+            return torch.cat(parts) if parts else torch.zeros((0, K), dtype=torch.float64)
+        finally:
+            rows.close()
+
+    def predict_proba(self, data, rows_per_pass=65536):
+        return torch.softmax(self.decision_function(data, rows_per_pass), 1)
+
+    def state_dict(self):
+        """The fitted weights under the keys of the reference's ``MLP`` (``module`` is Linear, Norm, Activation, Dropout per
+        hidden block, then Linear): fp32 CPU tensors that ``load_state_dict(strict=True)`` takes."""
+        if self.coefs_ is None:
+            raise RuntimeError("fit first")
+        out = {}
+        for l, (W, b) in enumerate(zip(self.coefs_, self.intercepts_)):
+            out[f"module.{4 * l}.weight"] = W.detach().to(torch.float32).cpu().clone()
+            out[f"module.{4 * l}.bias"] = b.detach().to(torch.float32).cpu().clone()
+        return out

@@ -1,0 +1,160 @@
+"""``MLPProbe``'s training step, measured (MI355X; writes its table to stdout and, with --out, to a file).
+
+For in 512, hid 2048 x 2, 10 and 1000 classes, batch 128 and 1024, two arms run the same step on resident fp32 rows:
+
+(a) the device path of ``MLPProbe`` (``_DeviceMLP.step``: 3 x ``lla_gemm_f32``, ``lla_softmax_xent``, 3 x ``lla_gemm_f32_tn``,
+    2 x ``lla_gemm_f32_nn``, ``lla_adamw_step``),
+(b) torch eager fp32 on the same device: ``nn.Sequential`` (Linear, ReLU, Linear, ReLU, Linear) + ``F.cross_entropy`` +
+    ``torch.optim.AdamW``.
+
+Every arm is warmed up, then timed with device events over ``--inner`` back-to-back steps; the arms are interleaved and the
+round is repeated ``--reps`` times (3), as tools/latents_bench.py does.  The kernels of (a) are then timed on their own the
+same way.  Last, the whole-epoch time of ``MLPProbe(epochs=1).fit`` from a resident ``CompressedLatents`` of ``--records``
+records (131072), decode included: a host clock around a call that ends in a device synchronise, three runs per batch size.
+
+usage (GPU box): python tools/mlp_probe_bench.py [--out profiles/mlp_probe.txt]
+"""
+import argparse
+import os
+import sys
+import tempfile
+import time
+
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+
+import torch  # noqa: E402
+
+import hubconf  # noqa: E402
+from lossyless_amd import MLPProbe, _lib  # noqa: E402
+from lossyless_amd.probe import _Adam, _DeviceMLP, _mlp_init  # noqa: E402
+from latents_bench import interleaved, med  # noqa: E402
+
+IN, HID, LAYERS = 512, 2048, 2
+
+
+def eager_arm(Ws, bs, x, y, dev):
+    nn = torch.nn
+    layers = []
+    for W, b in zip(Ws, bs):
+        lin = nn.Linear(W.shape[1], W.shape[0])
+        with torch.no_grad():
+            lin.weight.copy_(W), lin.bias.copy_(b)
+        layers += [lin, nn.ReLU()]
+    net = nn.Sequential(*layers[:-1]).to(dev)
+    opt = torch.optim.AdamW(net.parameters(), lr=1e-3, weight_decay=1e-5)
+    y64 = y.to(torch.int64)
+
+    def step():
+        opt.zero_grad(set_to_none=True)
+        torch.nn.functional.cross_entropy(net(x), y64).backward()
+        opt.step()
+    return step
+
+
+def kernels_of(eng, x, y):
+    """The launches of one step of (a), each as a call of its own on the engine's buffers."""
+    L, st, n = eng.L, _lib.stream_ptr(eng.device), int(x.shape[0])
+    d, kpad = eng.dims, eng.dims[-1]
+    eng.step(x, y, 0)
+    out = {"3 x lla_gemm_f32 (forward)": lambda: eng.forward(x, st),
+           "lla_softmax_xent": lambda: L.lla_softmax_xent(_lib.ptr(eng.acts[-1]), kpad, _lib.ptr(y), n, eng.K, kpad, 1.0 / n,
+                                                          _lib.ptr(eng.dlogits), kpad, _lib.ptr(eng.loss), _lib.ptr(eng.right),
+                                                          _lib.ptr(eng.ws), st)}
+    below = [x] + eng.acts[:-1]
+    delta = [eng.delta[1], eng.delta[0], eng.dlogits]      # any buffers of the right pitch: the values do not matter here
+    for l in (2, 1, 0):
+        i, o = d[l], d[l + 1]
+        dl, ldd = delta[l], int(delta[l].stride(0))
+        out[f"lla_gemm_f32_tn layer {l} (dW [{o}][{i}])"] = (
+            lambda l=l, i=i, o=o, dl=dl, ldd=ldd: L.lla_gemm_f32_tn(_lib.ptr(dl), ldd, _lib.ptr(below[l]), i, _lib.ptr(eng.gW[l]), i,
+                                                                    _lib.ptr(eng.gb[l]), n, o, i, st))
+        if l > 0:
+            dst = eng.delta[l % 2]
+            out[f"lla_gemm_f32_nn layer {l} (reduction {o})"] = (
+                lambda l=l, i=i, o=o, dl=dl, ldd=ldd, dst=dst: L.lla_gemm_f32_nn(_lib.ptr(dl), ldd, _lib.ptr(eng.W[l]), i,
+                                                                                 _lib.ptr(below[l]), i, _lib.ptr(dst),
+                                                                                 int(dst.stride(0)), n, o, i, st))
+    a = eng.adam
+    out[f"lla_adamw_step ({eng.n} parameters)"] = lambda: L.lla_adamw_step(_lib.ptr(eng.p), _lib.ptr(eng.g), _lib.ptr(eng.m),
+                                                                         _lib.ptr(eng.v), eng.n, a.lr, a.b1, a.b2, a.eps, a.wd,
+                                                                         0.1, 0.001, st)
+    return out
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--records", type=int, default=131072)
+    ap.add_argument("--reps", type=int, default=3)
+    ap.add_argument("--inner", type=int, default=200, help="steps per timed window")
+    ap.add_argument("--out", default=None)
+    args = ap.parse_args()
+    if not torch.cuda.is_available():
+        sys.exit("mlp_probe_bench.py measures on an MI355X: no GPU here, nothing measured")
+    lines = []
+
+    def say(s=""):
+        print(s, flush=True)
+        lines.append(s)
+
+    dev = torch.device("cuda", torch.cuda.current_device())
+    say(f"device: {torch.cuda.get_device_name(dev)}   MLP {IN} -> {HID} x {LAYERS} -> classes, fp32, AdamW(lr 1e-3, wd 1e-5)")
+    g = torch.Generator().manual_seed(0)
+    for K in (10, 1000):
+        for B in (128, 1024):
+            Ws, bs = _mlp_init([IN] + [HID] * LAYERS + [K], g)
+            x = torch.randn(B, IN, generator=g).to(dev)
+            y = torch.randint(0, K, (B,), generator=g).to(torch.int32).to(dev)
+            eng = _DeviceMLP(Ws, bs, _Adam(1e-3, 1e-5, (0.9, 0.999), 1e-8), dev, B, K, max_steps=1)
+            arms = {"(a) MLPProbe device step": lambda: eng.step(x, y, 0), "(b) torch eager fp32 step": eager_arm(Ws, bs, x, y, dev)}
+            times = interleaved(arms, args.inner, args.reps, dev)
+            say()
+            say(f"classes {K}, batch {B}: ms per training step, device events over {args.inner} back-to-back steps, "
+                f"{args.reps} interleaved runs")
+            for k, ts in times.items():
+                say(f"    {k:44s} " + "  ".join(f"{t:9.4f}" for t in ts) + f"   median {med(ts):9.4f} ms")
+            a, b = times["(a) MLPProbe device step"], times["(b) torch eager fp32 step"]
+            say(f"    (a) / (b) medians = {med(a) / med(b):.3f};  spread of (b) = {max(b) - min(b):.4f} ms;  "
+                f"(a) - (b) = {med(a) - med(b):+.4f} ms")
+            times = interleaved(kernels_of(eng, x, y), args.inner, args.reps, dev)
+            say("    the launches of (a), timed on their own:")
+            for k, ts in times.items():
+                say(f"    {k:44s} " + "  ".join(f"{t:9.4f}" for t in ts) + f"   median {med(ts):9.4f} ms")
+            say(f"    sum of their medians {sum(med(ts) for ts in times.values()):.4f} ms")
+            del eng, arms
+
+    # the whole epoch from a resident container, decode included
+    comp, _ = hubconf.clip_compressor_b005(device="cuda", clip_weights="synthetic")
+    N, C = args.records, comp.z_dim
+    z = (torch.randn(N, C, generator=g) * 0.5).to(dev)
+    payload, offsets, _ = comp.entropy_bottleneck.encode_device(z, comp._tables(), record_prefix=True)
+    total = int(offsets[-1])
+    with tempfile.TemporaryDirectory() as d:
+        f = os.path.join(d, "Z.bin")
+        with open(f, "wb") as fh:
+            fh.write(N.to_bytes(4, "big"))
+            fh.write(payload[:total].cpu().numpy().tobytes())
+        ds = comp.open_dataset(f)
+    del z, payload
+    labels = torch.arange(N) % 10
+    say()
+    say(f"one epoch of MLPProbe.fit from a resident CompressedLatents: N = {len(ds)} records, {ds.nbytes / 2**20:.1f} MiB "
+        f"compressed, 10 classes; host clock around fit(epochs=1), which ends in a synchronise (initialisation, the decode "
+        f"of 2 groups of 65536 records and the label gather included); one warm-up fit, then {args.reps} runs")
+    for B in (128, 1024):
+        runs = []
+        for r in range(args.reps + 1):
+            torch.cuda.synchronize(dev)
+            t0 = time.perf_counter()
+            probe = MLPProbe(epochs=1, batch_size=B).fit(ds, labels)
+            torch.cuda.synchronize(dev)
+            runs.append(time.perf_counter() - t0)
+        runs = runs[1:]
+        say(f"    batch {B:5d} ({probe.n_steps_} steps)   " + "  ".join(f"{t:8.3f}" for t in runs) +
+            f"   median {med(runs):8.3f} s   {1e3 * med(runs) / probe.n_steps_:.4f} ms / step   loss {probe.loss_curve_[-1]:.4f}")
+    if args.out:
+        with open(args.out, "w") as fh:
+            fh.write("\n".join(lines) + "\n")
+
+
+if __name__ == "__main__":
+    main()

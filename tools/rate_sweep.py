@@ -76,6 +76,10 @@ def main():
                     help="also run CLIP's linear-probe protocol (softmax regression, N values of C log-spaced in [1e-3, 10], the "
                          "same folds as --device-probe-cv) with lossyless_amd.LogisticProbeCV on the device (adds "
                          "logistic_probe_cv_best, _validation_accuracy, _accuracy and _fit_s)")
+    ap.add_argument("--device-mlp", action="store_true",
+                    help="also train lossyless_amd.MLPProbe (the reference's MLP predictor at its class defaults: 2 x 2048 "
+                         "hidden units, AdamW, 10 epochs of shuffled minibatches of 128) on the device from the container kept "
+                         "compressed (adds mlp_probe_accuracy and mlp_probe_fit_s)")
     args = ap.parse_args()
 
     weights = os.environ.get("LOSSYLESS_CLIP_WEIGHTS", "synthetic")
@@ -162,6 +166,13 @@ def main():
                                  logistic_probe_cv_best=dict(cv.best_params_),
                                  logistic_probe_cv_validation_accuracy=float(cv.mean_scores_[cv.best_index_]),
                                  logistic_probe_cv_accuracy=float(cv.best_estimator_.score(comp.open_dataset(ft), np.asarray(Yt))))
+                if args.device_mlp:
+                    from lossyless_amd import MLPProbe
+                    t0 = time.perf_counter()
+                    mlp = MLPProbe().fit(comp.open_dataset(f), np.asarray(Y))
+                    torch.cuda.synchronize()
+                    probe.update(mlp_probe_fit_s=round(time.perf_counter() - t0, 3),
+                                 mlp_probe_accuracy=float(mlp.score(comp.open_dataset(ft), np.asarray(Yt))))
         print(json.dumps(dict(rate_point=name, data=data, clip_weights=weights, images=n,
                               call=("Dataset(transform=RawRGB) -> compress_dataset(dataset, file, label_file, "
                                     f"dict(batch_size={args.batch}, num_workers={args.workers}))") if shaped
