@@ -664,6 +664,37 @@ int lla_softmax_xent(const float *logits, int ld, const int32_t *y, int B, int K
 int lla_adamw_step(float *p, const float *g, float *m, float *v, long long n, double lr, double beta1, double beta2,
                    double eps, double weight_decay, double bias_correction1, double bias_correction2, void *stream);
 
+/* ---- BatchNorm1d -> ReLU -> Dropout of the predictor's hidden blocks, training mode (csrc/batchnorm.hip).  The reference's
+ * predictor is configured (config/architecture/mlp_probe.yaml) with norm_layer batchnorm and dropout_p 0.2, for which
+ * lossyless/architectures.py:137-153 builds each hidden block as Linear(bias=False) -> BatchNorm1d -> ReLU -> Dropout(p).
+ * Conventions of the block above: fp32, row-major, pitches in elements, no floating-point atomics, the order of every sum
+ * fixed by (B, N) alone, LLA_EINVAL before any device call, a zero-sized call LLA_OK with no launch, no workspace.  Every
+ * sum and every element is formed in double and rounded once to fp32.  N % 4 == 0, every pitch >= N and a multiple of 4,
+ * every pointer 16-byte aligned; B == 1 is LLA_EINVAL (torch refuses one value per channel in training as well). */
+
+/* Forward of BatchNorm1d (training) -> ReLU -> Dropout (lossyless/architectures.py:143-145,150-152) from the pre-norm
+ * activations a [B][lda] (lla_gemm_f32 with bias = NULL).  Per column j:
+ *   mean_j = (1/B) sum_i a_ij;  var_j = (1/B) sum_i (a_ij - mean_j)^2  (biased, two-pass);  rstd_j = 1 / sqrt(var_j + eps)
+ *   out_ij = keep_ij ? max(gamma_j (a_ij - mean_j) rstd_j + beta_j, 0) s : 0,   s = (float)(1 / (1 - (double)p))
+ *   running_mean_j <- (1 - momentum) running_mean_j + momentum mean_j
+ *   running_var_j  <- (1 - momentum) running_var_j  + momentum var_j B / (B - 1)        (both NULL: not tracked)
+ * mean [N] and rstd [N] are written for lla_bn_bwd; `a` is only read and must differ from `out`.
+ * keep_ij: Philox4x32-10 with key (seed & 0xffffffff, seed >> 32) and counter (e & 0xffffffff, e >> 32, step, layer),
+ * e = (i N + j) / 4; output word j % 4 gives u = (float)(word >> 8) 2^-24 and keep_ij = (u >= (float)p): a function of
+ * (seed, step, layer, i, j) alone.  p == 0 draws nothing and out is the ReLU exactly.  0 <= p < 1, eps >= 0,
+ * 0 <= momentum <= 1.  Columns N .. ldo-1 of out are not written. */
+int lla_bn_relu_dropout_fwd(const float *a, int lda, const float *gamma, const float *beta, float *out, int ldo,
+                            float *mean, float *rstd, float *running_mean, float *running_var, int B, int N, double eps,
+                            double momentum, double p, uint64_t seed, uint32_t step, uint32_t layer, void *stream);
+/* Backward of the same three modules (what autograd runs for the same lines).  g [B][ldg] is the gradient with respect to
+ * `out` already masked by [out > 0] -- lla_gemm_f32_nn with H = out delivers it: out > 0 iff the ReLU passed and the element
+ * was kept -- so only the factor s is missing.  With gh = s g and xhat = (a - mean) rstd (a, mean, rstd of the forward):
+ *   dbeta_j = sum_i gh_ij;   dgamma_j = sum_i gh_ij xhat_ij;
+ *   da_ij = gamma_j rstd_j (gh_ij - dbeta_j / B - xhat_ij dgamma_j / B)
+ * da [B][ldda] may be g itself (in place) and must differ from a.  Columns N .. ldda-1 of da are not written. */
+int lla_bn_bwd(const float *g, int ldg, const float *a, int lda, const float *gamma, const float *mean, const float *rstd,
+               double p, float *dgamma, float *dbeta, float *da, int ldda, int B, int N, void *stream);
+
 /* out[n][H][W][ldc] (first cout channels) = relu(conv3x3(in, stride 1, pad 1) + bias) as an IMPLICIT GEMM:
  * `in` is NHWC fp16 [n][H][W][pitch] (first cin channels used; cin % 64 == 0, or cin == 32), weights fp16
  * [cout][K] with K = 9 cin rounded up to a multiple of 64 (zero padded) in the order (kh, kw, c), bias fp32

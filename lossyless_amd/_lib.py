@@ -105,6 +105,9 @@ _SIGNATURES = {
     "lla_softmax_xent_workspace_bytes": (_sz, [_i]),
     "lla_softmax_xent": (_i, [_vp, _i, _vp, _i, _i, _i, ctypes.c_float, _vp, _i, _vp, _vp, _vp, _vp]),
     "lla_adamw_step": (_i, [_vp, _vp, _vp, _vp, ctypes.c_longlong] + [ctypes.c_double] * 7 + [_vp]),
+    "lla_bn_relu_dropout_fwd": (_i, [_vp, _i, _vp, _vp, _vp, _i, _vp, _vp, _vp, _vp, _i, _i] + [ctypes.c_double] * 3
+                                + [ctypes.c_uint64, ctypes.c_uint32, ctypes.c_uint32, _vp]),
+    "lla_bn_bwd": (_i, [_vp, _i, _vp, _i, _vp, _vp, _vp, ctypes.c_double, _vp, _vp, _vp, _i, _i, _i, _vp]),
     "lla_conv3x3_relu_f16": (_i, [_vp, _i, _i, _i, _i, _i, _vp, _vp, _vp, _i, _i, _vp]),
     "lla_conv3x3_direct_relu_f16": (_i, [_vp, _i, _i, _i, _i, _i, _vp, _i, _vp, _vp, _i, _i, _i, _vp]),
     "lla_conv3x3_rgb_s2_relu_f16": (_i, [_vp, _i, _i, _i, _vp, _i, _vp, _vp, _i, _vp]),

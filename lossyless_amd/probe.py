@@ -1408,8 +1408,9 @@ class MLPProbe(_Scores):
     CLASS DEFAULTS (``norm_layer="identity"``, ``activation="ReLU"``, ``dropout_p=0``: Linear -> ReLU per hidden layer with
     biases, then Linear), trained as lossyless/predictors.py:38-232 trains it: cross-entropy, AdamW (``weight_decay=0``: Adam)
     on shuffled minibatches -- from a dataset that stays compressed in HBM.  It is NOT the reference's
-    ``config/architecture/mlp_probe.yaml``, which asks for batchnorm and dropout 0.2: ``norm_layer="batchnorm"``,
-    ``dropout_p > 0``, a learning-rate ``scheduler``, regression targets and fp16 rows are not built and raise ``ValueError``.
+    ``config/architecture/mlp_probe.yaml``, which asks for batchnorm and dropout 0.2 -- that is ``BatchNormMLPProbe`` below:
+    ``norm_layer="batchnorm"``, ``dropout_p > 0`` and a learning-rate ``scheduler`` raise ``ValueError`` here, as do regression
+    targets and fp16 rows, which are not built.
 
     ``fit(data, labels=None, decode_group=65536)``
         data    a ``CompressedLatents`` / ``HyperpriorLatents`` (its own labels unless ``labels`` is given), or a ``[N, C]``
@@ -1435,13 +1436,14 @@ class MLPProbe(_Scores):
     def __init__(self, hid_dim=2048, n_hid_layers=2, lr=1e-3, weight_decay=1e-5, betas=(0.9, 0.999), eps=1e-8, epochs=10,
                  batch_size=128, seed=0, norm_layer="identity", activation="ReLU", dropout_p=0, scheduler=None):
         if norm_layer not in ("identity", None):
-            raise ValueError(f"norm_layer={norm_layer!r} is not built: MLPProbe is the reference's MLP with norm_layer='identity'")
+            raise ValueError(f"norm_layer={norm_layer!r} is not built here: MLPProbe is the reference's MLP with norm_layer='identity' "
+                             "(batchnorm: BatchNormMLPProbe)")
         if activation != "ReLU":
             raise ValueError(f"activation={activation!r} is not built: MLPProbe is the reference's MLP with activation='ReLU'")
         if dropout_p != 0:
-            raise ValueError("dropout_p > 0 is not built: MLPProbe is the reference's MLP with dropout_p=0")
+            raise ValueError("dropout_p > 0 is not built here: MLPProbe is the reference's MLP with dropout_p=0 (dropout: BatchNormMLPProbe)")
         if scheduler is not None:
-            raise ValueError("learning-rate schedulers are not built")
+            raise ValueError("learning-rate schedulers are not built here (scheduler=: BatchNormMLPProbe)")
         if int(hid_dim) < 8 or int(hid_dim) % 8:
             raise ValueError(f"hid_dim must be a positive multiple of 8, got {hid_dim}")
         if int(n_hid_layers) < 1 or int(epochs) < 1 or int(batch_size) < 1:
@@ -1572,4 +1574,416 @@ class MLPProbe(_Scores):
         for l, (W, b) in enumerate(zip(self.coefs_, self.intercepts_)):
             out[f"module.{4 * l}.weight"] = W.detach().to(torch.float32).cpu().clone()
             out[f"module.{4 * l}.bias"] = b.detach().to(torch.float32).cpu().clone()
+        return out
+
+
+# ------------------------------------------------- the reference's predictor as configured: batchnorm, dropout, a schedule
+def philox4x32_10(counter, key):
+    """Philox4x32-10 (Salmon et al., SC'11) on the CPU: ``counter`` [..., 4] and ``key`` [..., 2] of 32-bit words (anything
+    numpy broadcasts) -> uint32 [..., 4].  The definition csrc/batchnorm.hip draws its dropout masks from."""
+    c = np.asarray(counter, dtype=np.uint64) & np.uint64(0xFFFFFFFF)
+    k = np.asarray(key, dtype=np.uint64) & np.uint64(0xFFFFFFFF)
+    shape = np.broadcast_shapes(c.shape[:-1], k.shape[:-1])
+    c0, c1, c2, c3 = (np.broadcast_to(c[..., i], shape).copy() for i in range(4))
+    k0, k1 = (np.broadcast_to(k[..., i], shape).copy() for i in range(2))
+    mask, sh = np.uint64(0xFFFFFFFF), np.uint64(32)
+    for _ in range(10):
+        p0, p1 = np.uint64(0xD2511F53) * c0, np.uint64(0xCD9E8D57) * c2          # 32 x 32 -> 64 bits: no overflow
+        c0, c1, c2, c3 = (p1 >> sh) ^ c1 ^ k0, p1 & mask, (p0 >> sh) ^ c3 ^ k1, p0 & mask
+        k0, k1 = (k0 + np.uint64(0x9E3779B9)) & mask, (k1 + np.uint64(0xBB67AE85)) & mask
+    return np.stack([c0, c1, c2, c3], -1).astype(np.uint32)
+
+
+def dropout_keep(seed, step, layer, rows, cols, p):
+    """The keep pattern of ``lla_bn_relu_dropout_fwd`` -> bool tensor [rows, cols] (``cols % 4 == 0``): the quad of columns
+    j .. j + 3 of row i takes the four words of Philox4x32-10 with key (seed_lo, seed_hi) and counter (e_lo, e_hi, step,
+    layer), e = (i cols + j) / 4; a word w gives u = (w >> 8) 2^-24 and the element is kept iff u >= float32(p)."""
+    if cols % 4:
+        raise ValueError("cols must be a multiple of 4")
+    seed = int(seed) & 0xFFFFFFFFFFFFFFFF
+    e = np.arange(rows * cols // 4, dtype=np.uint64)
+    counter = np.stack([e & np.uint64(0xFFFFFFFF), e >> np.uint64(32), np.full_like(e, int(step) & 0xFFFFFFFF),
+                        np.full_like(e, int(layer) & 0xFFFFFFFF)], -1)
+    words = philox4x32_10(counter, np.array([seed & 0xFFFFFFFF, seed >> 32], dtype=np.uint64))
+    u = (words >> np.uint32(8)).astype(np.float32) * np.float32(2.0 ** -24)
+    return torch.from_numpy((u >= np.float32(p)).reshape(rows, cols))
+
+
+def _dropout_scale(p):
+    """s = (float)(1 / (1 - (double)p)), as a Python float holding the fp32 value."""
+    return float(np.float32(1.0 / (1.0 - float(p))))
+
+
+def lr_schedule(scheduler, lr, epochs, decay_factor=100, k_steps=3):
+    """The learning rate of every epoch -> list of ``epochs`` doubles, as lossyless/helpers.py:536-545 builds the schedulers
+    and ``torch.optim.lr_scheduler`` steps them once per epoch (the chained form: each rate is the previous one times a
+    factor).  None: constant.  "unifmultistep": ``MultiStepLR`` with milestones ``(epochs // (k_steps + 1)) i``, i = 1 ..
+    k_steps, and ``gamma = (1 / decay_factor) ** (1 / k_steps)``.  "expdecay": ``ExponentialLR`` with
+    ``gamma = (1 / decay_factor) ** (1 / epochs)``."""
+    lr, epochs = float(lr), int(epochs)
+    if scheduler is None:
+        return [lr] * epochs
+    if scheduler == "unifmultistep":
+        delta = epochs // (k_steps + 1)
+        milestones = [delta * i for i in range(1, k_steps + 1)]
+        gamma = (1 / decay_factor) ** (1 / k_steps)
+        out = []
+        for e in range(epochs):
+            n = milestones.count(e)
+            lr = lr * gamma ** n if n else lr
+            out.append(lr)
+        return out
+    if scheduler == "expdecay":
+        gamma = (1 / decay_factor) ** (1 / epochs)
+        out = []
+        for e in range(epochs):
+            lr = lr * gamma if e else lr
+            out.append(lr)
+        return out
+    raise ValueError(f"scheduler={scheduler!r} is not built: None, 'unifmultistep' or 'expdecay'")
+
+
+def _fold_batchnorm(Ws, b_last, gammas, betas, rms, rvs, eps):
+    """Evaluation-mode BatchNorm1d folded into the bias-free Linear below it, in float64 on the host:
+    W' = diag(gamma / sqrt(rv + eps)) W,  b' = beta - gamma rm / sqrt(rv + eps)  -> (weights, biases) of a plain ReLU MLP."""
+    fW, fb = [], []
+    for W, ga, be, rm, rv in zip(Ws[:-1], gammas, betas, rms, rvs):
+        sc = ga.double().cpu() / torch.sqrt(rv.double().cpu() + eps)
+        fW.append(sc[:, None] * W.double().cpu())
+        fb.append(be.double().cpu() - sc * rm.double().cpu())
+    return fW + [Ws[-1].double().cpu()], fb + [b_last.double().cpu()]
+
+
+class _TwinBNMLP:
+    """The float64 twin of a training step of Linear(bias=False) -> BatchNorm1d -> ReLU -> Dropout blocks and a last Linear:
+    every formula of csrc/batchnorm.hip and csrc/mlp.hip written out by hand, no autograd.  The CPU path of
+    ``BatchNormMLPProbe`` and the oracle of its GPU tests.  ``step`` numbers the minibatches from 0 (the dropout counter)."""
+
+    def __init__(self, Ws, b_last, adam, p, seed, momentum, eps):
+        f64 = torch.float64
+        self.Ws, self.b = [W.to(f64).clone() for W in Ws], b_last.to(f64).clone()
+        self.gammas = [torch.ones(W.shape[0], dtype=f64) for W in Ws[:-1]]
+        self.betas = [torch.zeros(W.shape[0], dtype=f64) for W in Ws[:-1]]
+        self.rms = [torch.zeros(W.shape[0], dtype=f64) for W in Ws[:-1]]
+        self.rvs = [torch.ones(W.shape[0], dtype=f64) for W in Ws[:-1]]
+        self.adam, self.t, self.p, self.s, self.seed = adam, 0, float(p), _dropout_scale(p), int(seed)
+        self.momentum, self.eps = float(momentum), float(eps)
+        self._state = None
+
+    def _params(self):
+        return self.Ws + self.gammas + self.betas + [self.b]
+
+    def keep(self, step, layer, rows, cols):
+        return dropout_keep(self.seed, step, layer, rows, cols, self.p)
+
+    def gradients(self, x, y, track=False):
+        """-> (loss sum, rows right, grads) of the mean cross-entropy of the minibatch, grads in the order of
+        ``_params()``: dW per layer, dgamma per block, dbeta per block, db of the last layer.  ``track``: also update the
+        running statistics, as the forward of a module in training mode does."""
+        zero = torch.zeros((), dtype=torch.float64)
+        B = int(x.shape[0])
+        hs, xhats, rstds = [x.to(torch.float64)], [], []
+        for l, (W, ga, be) in enumerate(zip(self.Ws[:-1], self.gammas, self.betas)):
+            a = hs[-1] @ W.T                                                 # lla_gemm_f32, bias = NULL
+            mean = a.sum(0) / B                                              # lla_bn_relu_dropout_fwd
+            d = a - mean
+            var = (d * d).sum(0) / B
+            rstd = 1.0 / torch.sqrt(var + self.eps)
+            yv = ga * (d * rstd) + be
+            h = torch.where(yv > 0, yv, zero)
+            if self.p > 0:
+                h = torch.where(self.keep(self.t, l, B, int(a.shape[1])), h * self.s, zero)
+            if track:
+                self.rms[l] = (1.0 - self.momentum) * self.rms[l] + self.momentum * mean
+                self.rvs[l] = (1.0 - self.momentum) * self.rvs[l] + self.momentum * (var * (B / (B - 1)))
+            hs.append(h), xhats.append(d * rstd), rstds.append(rstd)
+        s = hs[-1] @ self.Ws[-1].T + self.b
+        delta, loss, right = _TwinMLP.xent(s, y)
+        n = len(self.Ws)
+        gW, gg, gb = [None] * n, [None] * (n - 1), [None] * (n - 1)
+        gW[-1], g_last = delta.T @ hs[-1], delta.sum(0)                      # lla_gemm_f32_tn
+        g = torch.where(hs[-1] > 0, delta @ self.Ws[-1], zero)               # lla_gemm_f32_nn with H = out
+        for l in range(n - 2, -1, -1):
+            gh = self.s * g if self.p > 0 else g                             # lla_bn_bwd
+            gb[l], gg[l] = gh.sum(0), (gh * xhats[l]).sum(0)
+            da = self.gammas[l] * rstds[l] * (gh - gb[l] / B - xhats[l] * (gg[l] / B))
+            gW[l] = da.T @ hs[l]                                             # lla_gemm_f32_tn, db = NULL
+            if l > 0:
+                g = torch.where(hs[l] > 0, da @ self.Ws[l], zero)
+        return loss, right, gW + gg + gb + [g_last]
+
+    def step(self, x, y):
+        loss, right, grads = self.gradients(x, y, track=True)
+        a = self.adam
+        if self._state is None:
+            self._state = [(torch.zeros_like(p), torch.zeros_like(p)) for p in self._params()]
+        self.t += 1
+        bc1, bc2 = a.corrections(self.t)
+        for p, g, (m, v) in zip(self._params(), grads, self._state):         # lla_adamw_step
+            p.mul_(1.0 - a.lr * a.wd)
+            m.copy_(a.b1 * m + (1.0 - a.b1) * g)
+            v.copy_(a.b2 * v + (1.0 - a.b2) * g * g)
+            p.sub_((a.lr / bc1) * m / (v.sqrt() / bc2 ** 0.5 + a.eps))
+        return loss, right
+
+    def epoch_totals(self, sums):
+        return float(sum(s[0] for s in sums)), int(sum(s[1] for s in sums))
+
+    def fitted(self, n_out):
+        """-> (Ws, b_last, gammas, betas, running means, running variances), copies."""
+        return tuple([t.clone() for t in group] for group in (self.Ws, [self.b], self.gammas, self.betas, self.rms, self.rvs))
+
+
+class _DeviceBNMLP:
+    """The same step on the device, beside ``_DeviceMLP``.  Parameters, gradients and the two moments each live in ONE flat
+    fp32 buffer -- per hidden block its weight [out][in], gamma [out], beta [out]; then the last weight [Kpad][in] and its
+    bias [Kpad] -- so one ``lla_adamw_step`` updates everything, gamma and beta included (the reference hands
+    ``self.parameters()`` to one group: lossyless/predictors.py:226).  Running statistics live outside it.  Per step and
+    block: ``lla_gemm_f32`` (bias = NULL, relu = 0) into the pre-norm buffer, ``lla_bn_relu_dropout_fwd`` into the
+    activation; the last ``lla_gemm_f32`` and ``lla_softmax_xent``; then per layer from the top ``lla_gemm_f32_tn`` and
+    ``lla_gemm_f32_nn`` with H = the block's output, and ``lla_bn_bwd`` in place on that gradient.  Nothing is read back
+    during an epoch."""
+
+    def __init__(self, Ws, b_last, adam, device, max_rows, n_classes, max_steps, p, seed, momentum, eps):
+        self.L, self.device, self.adam, self.t = _lib.lib(), device, adam, 0
+        self.K, self.p, self.seed, self.momentum, self.eps = int(n_classes), float(p), int(seed), float(momentum), float(eps)
+        self.dims = [int(Ws[0].shape[1])] + [int(W.shape[0]) for W in Ws[:-1]] + [-(-self.K // 8) * 8]
+        if any(d % 8 for d in self.dims[:-1]):
+            raise ValueError(f"the device path needs layer widths that are multiples of 8, got {self.dims[:-1]}")
+        pairs = list(zip(self.dims[:-1], self.dims[1:]))
+        self.n = sum(o * i + 2 * o for i, o in pairs[:-1]) + pairs[-1][1] * pairs[-1][0] + pairs[-1][1]
+        f32 = dict(dtype=torch.float32, device=device)
+        self.flat = [torch.zeros(self.n, **f32) for _ in range(4)]           # parameters, gradients, first and second moment
+        (self.W, self.gamma, self.beta, self.b), (self.gW, self.ggamma, self.gbeta, self.gb) = map(self._views, self.flat[:2])
+        for l, W in enumerate(Ws):
+            self.W[l][:W.shape[0]].copy_(W.to(torch.float32))
+        self.b[:b_last.shape[0]].copy_(b_last.to(torch.float32))
+        for ga in self.gamma:
+            ga.fill_(1.0)
+        hidden = self.dims[1:-1]
+        self.rm = [torch.zeros(o, **f32) for o in hidden]
+        self.rv = [torch.ones(o, **f32) for o in hidden]
+        self.mean = [torch.empty(o, **f32) for o in hidden]
+        self.rstd = [torch.empty(o, **f32) for o in hidden]
+        self.rows = max(int(max_rows), 2)
+        self.pre = [torch.empty((self.rows, o), **f32) for o in hidden]
+        self.acts = [torch.empty((self.rows, o), **f32) for o in self.dims[1:]]
+        self.dlogits = torch.empty((self.rows, self.dims[-1]), **f32)
+        self.delta = [torch.empty((self.rows, o), **f32) for o in hidden]
+        self.loss = torch.zeros(max_steps, dtype=torch.float64, device=device)
+        self.right = torch.zeros(max_steps, dtype=torch.int32, device=device)
+        self.ws = torch.empty(int(self.L.lla_softmax_xent_workspace_bytes(self.rows)), dtype=torch.uint8, device=device)
+
+    def _views(self, flat):
+        Ws, gammas, betas, at = [], [], [], 0
+        for i, o in list(zip(self.dims[:-1], self.dims[1:]))[:-1]:
+            Ws.append(flat[at:at + o * i].view(o, i))
+            gammas.append(flat[at + o * i:at + o * i + o])
+            betas.append(flat[at + o * i + o:at + o * i + 2 * o])
+            at += o * i + 2 * o
+        i, o = self.dims[-2], self.dims[-1]
+        Ws.append(flat[at:at + o * i].view(o, i))
+        return Ws, gammas, betas, flat[at + o * i:at + o * i + o]
+
+    def step(self, z, y, slot):
+        """One training step on the minibatch (z, y int32 class indexes); its loss sum and rows right go to ``slot``."""
+        n = int(z.shape[0])
+        L, a, P, n_layers = self.L, self.adam, _lib.ptr, len(self.W)
+        with torch.cuda.device(self.device):
+            st = _lib.stream_ptr(self.device)
+            x0, ld0 = _f32_rows(z, self.dims[0])
+            src, ld = x0, ld0
+            for l in range(n_layers - 1):
+                i, o = self.dims[l], self.dims[l + 1]
+                _lib.check(L.lla_gemm_f32(P(src), ld, P(self.W[l]), i, None, P(self.pre[l]), o, n, o, i, 0, st), "lla_gemm_f32")
+                rc = L.lla_bn_relu_dropout_fwd(P(self.pre[l]), o, P(self.gamma[l]), P(self.beta[l]), P(self.acts[l]), o,
+                                               P(self.mean[l]), P(self.rstd[l]), P(self.rm[l]), P(self.rv[l]), n, o, self.eps,
+                                               self.momentum, self.p, self.seed, self.t, l, st)
+                _lib.check(rc, "lla_bn_relu_dropout_fwd")
+                src, ld = self.acts[l], o
+            i, kpad = self.dims[-2], self.dims[-1]
+            _lib.check(L.lla_gemm_f32(P(src), ld, P(self.W[-1]), i, P(self.b), P(self.acts[-1]), kpad, n, kpad, i, 0, st),
+                       "lla_gemm_f32")
+            rc = L.lla_softmax_xent(P(self.acts[-1]), kpad, P(y), n, self.K, kpad, 1.0 / n, P(self.dlogits), kpad,
+                                    P(self.loss[slot:]), P(self.right[slot:]), P(self.ws), st)
+            _lib.check(rc, "lla_softmax_xent")
+            delta, ldd = self.dlogits, kpad
+            for l in range(n_layers - 1, -1, -1):
+                i, o = self.dims[l], self.dims[l + 1]
+                below, ldb = (self.acts[l - 1], i) if l > 0 else (x0, ld0)
+                db = self.gb if l == n_layers - 1 else None
+                _lib.check(L.lla_gemm_f32_tn(P(delta), ldd, P(below), ldb, P(self.gW[l]), i, P(db), n, o, i, st), "lla_gemm_f32_tn")
+                if l > 0:
+                    out = self.delta[l - 1]
+                    _lib.check(L.lla_gemm_f32_nn(P(delta), ldd, P(self.W[l]), i, P(below), ldb, P(out), i, n, o, i, st),
+                               "lla_gemm_f32_nn")
+                    rc = L.lla_bn_bwd(P(out), i, P(self.pre[l - 1]), i, P(self.gamma[l - 1]), P(self.mean[l - 1]),
+                                      P(self.rstd[l - 1]), self.p, P(self.ggamma[l - 1]), P(self.gbeta[l - 1]), P(out), i, n, i, st)
+                    _lib.check(rc, "lla_bn_bwd")
+                    delta, ldd = out, i
+            self.t += 1
+            bc1, bc2 = a.corrections(self.t)
+            rc = L.lla_adamw_step(P(self.flat[0]), P(self.flat[1]), P(self.flat[2]), P(self.flat[3]), self.n, a.lr, a.b1, a.b2,
+                                  a.eps, a.wd, bc1, bc2, st)
+            _lib.check(rc, "lla_adamw_step")
+        return slot
+
+    def epoch_totals(self, slots):
+        n = len(slots)
+        return float(self.loss[:n].sum()), int(self.right[:n].sum())
+
+    def fitted(self, n_out):
+        Ws = [W.clone() for W in self.W[:-1]] + [self.W[-1][:n_out].clone()]
+        return (Ws, [self.b[:n_out].clone()], [t.clone() for t in self.gamma], [t.clone() for t in self.beta],
+                [t.clone() for t in self.rm], [t.clone() for t in self.rv])
+
+
+class BatchNormMLPProbe(_Scores):
+    """``BatchNormMLPProbe(hid_dim=2048, n_hid_layers=2, lr=3e-4, weight_decay=1e-5, betas=(0.9, 0.999), eps=1e-8, epochs=10,
+    batch_size=128, seed=0, norm_layer="batchnorm", activation="ReLU", dropout_p=0.2, scheduler=None, decay_factor=100,
+    k_steps=3, bn_momentum=0.1, bn_eps=1e-5)``: the reference's predictor AS ITS CONFIGURATION BUILDS IT
+    (config/architecture/mlp_probe.yaml with ``optimizer_pred: AdamW_lr3e-4_w1e-5``): every hidden block of its ``MLP``
+    (lossyless/architectures.py:94-168) is Linear(bias=False) -> BatchNorm1d -> ReLU -> Dropout(p), the last Linear has a
+    bias, and all parameters -- gamma and beta included -- are one AdamW group (lossyless/predictors.py:226).  Trained on
+    shuffled minibatches from a dataset that stays compressed in HBM, exactly as ``MLPProbe`` walks it.
+
+    ``scheduler``  None, ``"unifmultistep"`` (the configuration's ``unifmultistep100``: ``decay_factor=100, k_steps=3``) or
+        ``"expdecay"`` over ``epochs``, stepped once per epoch (``lr_schedule``; lossyless/helpers.py:536-545).  The rate of
+        every epoch is ``lr_curve_``.
+    ``norm_layer`` any string containing ``"batch"``, as the reference's ``get_Normalization``; ``"identity"`` is ``MLPProbe``.
+    Initialisation: ``MLPProbe``'s draw for the weights from ``torch.Generator().manual_seed(seed)``, gamma = 1, beta = 0, a
+    zero last bias; then the 64-bit dropout seed (two 32-bit draws, low word first); then every epoch's permutation.  The
+    dropout mask is ``dropout_keep(seed, step, layer, ...)`` with ``step`` the number of steps taken before: a function of the
+    seed and the position alone, the same on the device and on the CPU.  A last minibatch of ONE row cannot be normalised:
+    ``fit`` raises before any training.
+
+    GPU latents and CUDA tensors train in the kernels of csrc/batchnorm.hip and csrc/mlp.hip (``_DeviceBNMLP``):
+    deterministic, bit for bit.  CPU data trains in the float64 twin (``_TwinBNMLP``).  ``decision_function`` / ``predict`` /
+    ``predict_proba`` / ``score`` are evaluation mode: running statistics, no dropout -- each block folded on the host in
+    float64 into a Linear with a bias and run as ``MLPProbe`` runs its forward pass (fp32 on the device, float64 on the CPU).
+
+    After ``fit``: ``coefs_`` (one weight per Linear), ``intercepts_`` (the last Linear's bias, a list of one), ``bn_weights_``,
+    ``bn_biases_``, ``running_means_``, ``running_vars_``, ``num_batches_tracked_``, ``classes_``, ``loss_curve_``,
+    ``accuracy_curve_`` (training mode, with dropout), ``lr_curve_``, ``n_steps_``.  ``state_dict()`` has the keys of the
+    reference's module and loads with ``strict=True``."""
+
+    _tensor = staticmethod(MLPProbe._tensor)
+    _epoch = MLPProbe._epoch
+
+    def __init__(self, hid_dim=2048, n_hid_layers=2, lr=3e-4, weight_decay=1e-5, betas=(0.9, 0.999), eps=1e-8, epochs=10,
+                 batch_size=128, seed=0, norm_layer="batchnorm", activation="ReLU", dropout_p=0.2, scheduler=None,
+                 decay_factor=100, k_steps=3, bn_momentum=0.1, bn_eps=1e-5):
+        if not isinstance(norm_layer, str) or "batch" not in norm_layer:
+            raise ValueError(f"norm_layer={norm_layer!r}: BatchNormMLPProbe is the reference's MLP with a batchnorm norm_layer; "
+                             "norm_layer='identity' is MLPProbe")
+        if activation != "ReLU":
+            raise ValueError(f"activation={activation!r} is not built: only activation='ReLU'")
+        if not 0 <= dropout_p < 1 or not float(np.float32(dropout_p)) < 1:
+            raise ValueError(f"dropout_p must satisfy 0 <= dropout_p < 1, got {dropout_p}")
+        if scheduler not in (None, "unifmultistep", "expdecay"):
+            raise ValueError(f"scheduler={scheduler!r} is not built: None, 'unifmultistep' or 'expdecay'")
+        if not decay_factor > 0 or int(k_steps) < 1:
+            raise ValueError("need decay_factor > 0 and k_steps >= 1")
+        if int(hid_dim) < 8 or int(hid_dim) % 8:
+            raise ValueError(f"hid_dim must be a positive multiple of 8, got {hid_dim}")
+        if int(n_hid_layers) < 1 or int(epochs) < 1 or int(batch_size) < 2:
+            raise ValueError("n_hid_layers and epochs must be at least 1, batch_size at least 2")
+        if not lr > 0 or weight_decay < 0 or not eps >= 0 or not all(0 <= b < 1 for b in betas):
+            raise ValueError("need lr > 0, weight_decay >= 0, eps >= 0 and betas in [0, 1)")
+        if not 0 <= bn_momentum <= 1 or not bn_eps >= 0:
+            raise ValueError("need 0 <= bn_momentum <= 1 and bn_eps >= 0")
+        self.hid_dim, self.n_hid_layers, self.epochs, self.batch_size = int(hid_dim), int(n_hid_layers), int(epochs), int(batch_size)
+        self.lr, self.weight_decay, self.betas, self.eps, self.seed = float(lr), float(weight_decay), tuple(betas), float(eps), int(seed)
+        self.dropout_p, self.scheduler, self.decay_factor, self.k_steps = float(dropout_p), scheduler, decay_factor, int(k_steps)
+        self.bn_momentum, self.bn_eps = float(bn_momentum), float(bn_eps)
+        self.coefs_ = self.intercepts_ = self.classes_ = None
+        self._folded = None
+
+    def fit(self, data, labels=None, decode_group=65536):
+        if _is_latents(data):
+            rows, device, n, dim = None, data.device, len(data), int(data.z_dim)
+        else:
+            rows = self._tensor(data)
+            device, n, dim = rows.device, int(rows.shape[0]), int(rows.shape[1])
+        if dim % 8:
+            raise ValueError(f"in_dim must be a multiple of 8, got {dim}")
+        if n % self.batch_size == 1:
+            raise ValueError(f"N = {n} rows with batch_size = {self.batch_size} leave a last minibatch of one row, which batchnorm "
+                             "cannot normalise: choose another batch_size (no row is dropped silently)")
+        y = _labels_of(data, labels, n)
+        classes, _, _ = _class_indexes(y)
+        idx = torch.searchsorted(classes, y)
+        K = int(classes.numel())
+        if K > 1024:
+            raise ValueError(f"lla_softmax_xent takes up to 1024 classes, got {K}")
+        g = torch.Generator().manual_seed(self.seed)
+        Ws, bs = _mlp_init([dim] + [self.hid_dim] * self.n_hid_layers + [K], g)
+        lo, hi = (int(w) for w in torch.randint(0, 2 ** 32, (2,), generator=g, dtype=torch.int64))
+        self.dropout_seed_ = lo | (hi << 32)
+        self.lr_curve_ = lr_schedule(self.scheduler, self.lr, self.epochs, self.decay_factor, self.k_steps)
+        adam = _Adam(self.lr, self.weight_decay, self.betas, self.eps)
+        steps = -(-n // self.batch_size)
+        if device.type == "cuda":
+            engine = _DeviceBNMLP(Ws, bs[-1], adam, device, min(self.batch_size, n), K, steps, self.dropout_p,
+                                  self.dropout_seed_, self.bn_momentum, self.bn_eps)
+            idx = idx.to(torch.int32).to(device)
+        else:
+            engine = _TwinBNMLP(Ws, bs[-1], adam, self.dropout_p, self.dropout_seed_, self.bn_momentum, self.bn_eps)
+        self.loss_curve_, self.accuracy_curve_ = [], []
+        for epoch in range(self.epochs):
+            adam.lr = self.lr_curve_[epoch]
+            order, walk = self._epoch(data, rows, n, g, decode_group)
+            y_epoch, at, sums = idx[order.to(idx.device)].contiguous(), 0, []
+            for z in walk:
+                bn = int(z.shape[0])
+                if device.type == "cuda":
+                    sums.append(engine.step(z, y_epoch[at:at + bn], len(sums)))
+                else:
+                    sums.append(engine.step(z, y_epoch[at:at + bn]))
+                at += bn
+            loss, right = engine.epoch_totals(sums)
+            self.loss_curve_.append(loss / n)
+            self.accuracy_curve_.append(right / n)
+        self.coefs_, self.intercepts_, self.bn_weights_, self.bn_biases_, self.running_means_, self.running_vars_ = engine.fitted(K)
+        self.classes_, self.n_steps_, self.num_batches_tracked_, self._folded = classes.numpy(), engine.t, engine.t, None
+        return self
+
+    def _eval_probe(self):
+        """The fitted network in evaluation mode as a plain ReLU MLP (``_fold_batchnorm``, rounded once to fp32 where the
+        fit ran on the device), held by an ``MLPProbe`` whose forward pass scores it."""
+        if self.coefs_ is None:
+            raise RuntimeError("fit first")
+        if self._folded is None:
+            fW, fb = _fold_batchnorm(self.coefs_, self.intercepts_[0], self.bn_weights_, self.bn_biases_, self.running_means_,
+                                     self.running_vars_, self.bn_eps)
+            inner = MLPProbe(hid_dim=self.hid_dim, n_hid_layers=self.n_hid_layers)
+            dev, dtype = self.coefs_[0].device, self.coefs_[0].dtype
+            inner.coefs_, inner.intercepts_ = [W.to(dtype).to(dev) for W in fW], [b.to(dtype).to(dev) for b in fb]
+            inner.classes_ = self.classes_
+            self._folded = inner
+        return self._folded
+
+    def decision_function(self, data, rows_per_pass=65536):
+        return self._eval_probe().decision_function(data, rows_per_pass)
+
+    def predict_proba(self, data, rows_per_pass=65536):
+        return torch.softmax(self.decision_function(data, rows_per_pass), 1)
+
+    def state_dict(self):
+        """The fitted tensors under the keys of the reference's ``MLP`` (``module`` is Linear, BatchNorm1d, ReLU, Dropout per
+        hidden block, then Linear): CPU tensors (fp32, ``num_batches_tracked`` int64) that ``load_state_dict(strict=True)``
+        takes."""
+        if self.coefs_ is None:
+            raise RuntimeError("fit first")
+        f32 = lambda t: t.detach().to(torch.float32).cpu().clone()          # noqa: E731
+        out, n = {}, len(self.coefs_) - 1
+        for l in range(n):
+            out[f"module.{4 * l}.weight"] = f32(self.coefs_[l])
+            out[f"module.{4 * l + 1}.weight"] = f32(self.bn_weights_[l])
+            out[f"module.{4 * l + 1}.bias"] = f32(self.bn_biases_[l])
+            out[f"module.{4 * l + 1}.running_mean"] = f32(self.running_means_[l])
+            out[f"module.{4 * l + 1}.running_var"] = f32(self.running_vars_[l])
+            out[f"module.{4 * l + 1}.num_batches_tracked"] = torch.tensor(self.num_batches_tracked_, dtype=torch.int64)
+        out[f"module.{4 * n}.weight"] = f32(self.coefs_[n])
+        out[f"module.{4 * n}.bias"] = f32(self.intercepts_[0])
         return out

@@ -80,6 +80,10 @@ def main():
                     help="also train lossyless_amd.MLPProbe (the reference's MLP predictor at its class defaults: 2 x 2048 "
                          "hidden units, AdamW, 10 epochs of shuffled minibatches of 128) on the device from the container kept "
                          "compressed (adds mlp_probe_accuracy and mlp_probe_fit_s)")
+    ap.add_argument("--device-mlp-config", action="store_true",
+                    help="also train lossyless_amd.BatchNormMLPProbe (the reference's predictor as config/main.yaml wires it: "
+                         "mlp_probe.yaml's batchnorm and dropout 0.2, AdamW lr 3e-4 wd 1e-5, unifmultistep100) the same way (adds "
+                         "mlp_config_probe_accuracy and mlp_config_probe_fit_s)")
     args = ap.parse_args()
 
     weights = os.environ.get("LOSSYLESS_CLIP_WEIGHTS", "synthetic")
@@ -173,6 +177,13 @@ def main():
                     torch.cuda.synchronize()
                     probe.update(mlp_probe_fit_s=round(time.perf_counter() - t0, 3),
                                  mlp_probe_accuracy=float(mlp.score(comp.open_dataset(ft), np.asarray(Yt))))
+                if args.device_mlp_config:
+                    from lossyless_amd import BatchNormMLPProbe
+                    t0 = time.perf_counter()
+                    bn_mlp = BatchNormMLPProbe(scheduler="unifmultistep").fit(comp.open_dataset(f), np.asarray(Y))
+                    torch.cuda.synchronize()
+                    probe.update(mlp_config_probe_fit_s=round(time.perf_counter() - t0, 3),
+                                 mlp_config_probe_accuracy=float(bn_mlp.score(comp.open_dataset(ft), np.asarray(Yt))))
         print(json.dumps(dict(rate_point=name, data=data, clip_weights=weights, images=n,
                               call=("Dataset(transform=RawRGB) -> compress_dataset(dataset, file, label_file, "
                                     f"dict(batch_size={args.batch}, num_workers={args.workers}))") if shaped
