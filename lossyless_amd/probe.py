@@ -1236,16 +1236,47 @@ class _Adam:
         return 1.0 - self.b1 ** t, 1.0 - self.b2 ** t
 
 
-class _TwinMLP:
+def _adamw(params, grads, moments, a, t):
+    """``lla_adamw_step`` on the host: step ``t`` of AdamW with the hyper-parameters ``a`` on a list of tensors, in place;
+    ``moments`` holds (m, v) per parameter."""
+    bc1, bc2 = a.corrections(t)
+    for p, g, (m, v) in zip(params, grads, moments):
+        p.mul_(1.0 - a.lr * a.wd)
+        m.copy_(a.b1 * m + (1.0 - a.b1) * g)
+        v.copy_(a.b2 * v + (1.0 - a.b2) * g * g)
+        p.sub_((a.lr / bc1) * m / (v.sqrt() / bc2 ** 0.5 + a.eps))
+
+
+class _Twin:
+    """What the two float64 twins share: the AdamW update of ``_params()`` and the sums of an epoch.  With ``step(x, y)``
+    and ``fitted(n_out)`` of its own a twin has the interface of the device engine (``_DeviceMLP``)."""
+
+    def __init__(self, adam):
+        self.adam, self.t, self.sums = adam, 0, []
+        self.moments = [(torch.zeros_like(p), torch.zeros_like(p)) for p in self._params()]
+
+    def _update(self, loss, right, grads):
+        self.t += 1
+        _adamw(self._params(), grads, self.moments, self.adam, self.t)
+        self.sums.append((loss, right))
+
+    def epoch_totals(self):
+        """-> (loss sum, rows right) over the steps since the last call."""
+        sums, self.sums = self.sums, []
+        return float(sum(s[0] for s in sums)), int(sum(s[1] for s in sums))
+
+
+class _TwinMLP(_Twin):
     """The float64 twin of a training step: forward, softmax cross-entropy, backward and AdamW written out by hand, formula
     by formula what the kernels of csrc/mlp.hip compute -- no autograd, so that it can be tested against autograd.  The CPU
     path of ``MLPProbe`` and the oracle of its GPU tests."""
 
     def __init__(self, Ws, bs, adam):
         self.Ws, self.bs = [W.to(torch.float64).clone() for W in Ws], [b.to(torch.float64).clone() for b in bs]
-        self.adam, self.t = adam, 0
-        self.m = [torch.zeros_like(p) for p in self.Ws + self.bs]
-        self.v = [torch.zeros_like(p) for p in self.Ws + self.bs]
+        super().__init__(adam)
+
+    def _params(self):
+        return self.Ws + self.bs
 
     def forward(self, x, pre=None):
         """-> (logits, [x, h_1, ..., h_L]): h = relu(h W^T + b) (lla_gemm_f32, relu = 1), then the last Linear.  ``pre``, a
@@ -1281,20 +1312,10 @@ class _TwinMLP:
 
     def step(self, x, y):
         loss, right, gW, gb = self.gradients(x, y)
-        a = self.adam
-        self.t += 1
-        bc1, bc2 = a.corrections(self.t)
-        for p, g, m, v in zip(self.Ws + self.bs, gW + gb, self.m, self.v):   # lla_adamw_step
-            p.mul_(1.0 - a.lr * a.wd)
-            m.copy_(a.b1 * m + (1.0 - a.b1) * g)
-            v.copy_(a.b2 * v + (1.0 - a.b2) * g * g)
-            p.sub_((a.lr / bc1) * m / (v.sqrt() / bc2 ** 0.5 + a.eps))
-        return loss, right
+        self._update(loss, right, gW + gb)                                   # lla_adamw_step
 
-    def epoch_totals(self, sums):
-        return float(sum(s[0] for s in sums)), int(sum(s[1] for s in sums))
-
-    def parameters(self, n_out):
+    def fitted(self, n_out):
+        """-> (weights, biases), copies."""
         return [W.clone() for W in self.Ws], [b.clone() for b in self.bs]
 
 
@@ -1308,101 +1329,250 @@ def _f32_rows(z, C):
 
 
 class _DeviceMLP:
-    """The same step on the device.  Parameters, gradients and the two moments each live in ONE flat fp32 buffer (layer l's
-    weight [out_l][in_l], then its bias; the class dimension padded to a multiple of 8 with zero rows that never receive a
-    non-zero gradient), so the update is one ``lla_adamw_step``.  Per step: ``lla_gemm_f32`` forward (relu = 1 on the hidden
-    layers: the only activations kept), ``lla_softmax_xent``, then from the last layer ``lla_gemm_f32_tn`` (dW, db) and
-    ``lla_gemm_f32_nn`` with the ReLU mask (not for the first layer).  Nothing is read back during an epoch."""
+    """The same step on the device, for either kind of hidden block.  ``bn=None``: a plain block, one ``lla_gemm_f32`` with
+    bias and relu = 1.  ``bn=(dropout p, seed, momentum, eps)``: a batchnorm block, ``lla_gemm_f32`` (bias = NULL, relu = 0)
+    into the pre-norm buffer, then ``lla_bn_relu_dropout_fwd`` into the activation.  Parameters, gradients and the two
+    moments each live in ONE flat fp32 buffer (``flat[0 .. 3]``: layer l's weight [out_l][in_l], then its bias -- under a
+    batchnorm block gamma and beta instead; the class dimension padded to a multiple of 8 with zero rows that never receive
+    a non-zero gradient), so one ``lla_adamw_step`` updates everything, gamma and beta included (the reference hands
+    ``self.parameters()`` to one group: lossyless/predictors.py:226).  Running statistics live outside it.  Every launch is a
+    method of its own and ``step`` is their sequence.  Step k of an epoch writes its loss sum and rows right to slot k;
+    nothing is read back before ``epoch_totals()``.  ``max_steps=0`` is a forward-only engine: no gradients, moments,
+    residuals or sums."""
 
-    def __init__(self, Ws, bs, adam, device, max_rows, n_classes, max_steps=0):
-        self.L, self.device, self.adam, self.t = _lib.lib(), device, adam, 0
-        self.K = int(n_classes)
+    def __init__(self, Ws, bs, adam, device, max_rows, n_classes, max_steps=0, bn=None):
+        self.L, self.device, self.adam, self.t, self.k = _lib.lib(), device, adam, 0, 0
+        self.K, self.bn = int(n_classes), bn is not None
         self.dims = [int(Ws[0].shape[1])] + [int(W.shape[0]) for W in Ws[:-1]] + [-(-self.K // 8) * 8]
         if any(d % 8 for d in self.dims[:-1]):
             raise ValueError(f"the device path needs layer widths that are multiples of 8, got {self.dims[:-1]}")
-        sizes = [o * i + o for i, o in zip(self.dims[:-1], self.dims[1:])]
-        self.n = sum(sizes)
-        self.p = torch.zeros(self.n, dtype=torch.float32, device=device)
-        self.W, self.b = self._views(self.p)
-        for l, (W, b) in enumerate(zip(Ws, bs)):
+        hidden, f32 = self.dims[1:-1], dict(dtype=torch.float32, device=device)
+        self.n = sum(o * i + o for i, o in zip(self.dims[:-1], self.dims[1:])) + self.bn * sum(hidden)
+        self.flat = [torch.zeros(self.n, **f32) for _ in range(4 if max_steps else 1)]     # parameters; gradients, two moments
+        self.W, self.b, self.gamma, self.beta = self._views(self.flat[0])
+        for l, W in enumerate(Ws):
             self.W[l][:W.shape[0]].copy_(W.to(torch.float32))
-            self.b[l][:b.shape[0]].copy_(b.to(torch.float32))
-        self.rows = max(int(max_rows), 1)
-        self.acts = [torch.empty((self.rows, d), dtype=torch.float32, device=device) for d in self.dims[1:]]
-        if max_steps:                        # a training engine: gradients, moments, residuals and the per-step sums
-            self.g, self.m, self.v = (torch.zeros(self.n, dtype=torch.float32, device=device) for _ in range(3))
-            self.gW, self.gb = self._views(self.g)
-            self.dlogits = torch.empty((self.rows, self.dims[-1]), dtype=torch.float32, device=device)
-            width = max(self.dims[1:-1])
-            self.delta = [torch.empty((self.rows, width), dtype=torch.float32, device=device) for _ in range(2)]
+        for b, src in zip(self.b, bs):
+            if b is not None:
+                b[:src.shape[0]].copy_(src.to(torch.float32))
+        for ga in self.gamma:
+            ga.fill_(1.0)
+        self.rows = max(int(max_rows), 2 if self.bn else 1)
+        self.acts = [torch.empty((self.rows, o), **f32) for o in self.dims[1:]]
+        if self.bn:
+            self.p, self.seed, self.momentum, self.eps = float(bn[0]), int(bn[1]), float(bn[2]), float(bn[3])
+            self.rm, self.rv = [torch.zeros(o, **f32) for o in hidden], [torch.ones(o, **f32) for o in hidden]
+            self.mean, self.rstd = [torch.empty(o, **f32) for o in hidden], [torch.empty(o, **f32) for o in hidden]
+            self.pre = [torch.empty((self.rows, o), **f32) for o in hidden]
+        if max_steps:                        # a training engine: views of the gradients, residuals and the per-step sums
+            self.gW, self.gb, self.ggamma, self.gbeta = self._views(self.flat[1])
+            self.dlogits = torch.empty((self.rows, self.dims[-1]), **f32)
+            self.delta = [torch.empty((self.rows, o), **f32) for o in hidden]
             self.loss = torch.zeros(max_steps, dtype=torch.float64, device=device)
             self.right = torch.zeros(max_steps, dtype=torch.int32, device=device)
             self.ws = torch.empty(int(self.L.lla_softmax_xent_workspace_bytes(self.rows)), dtype=torch.uint8, device=device)
 
     def _views(self, flat):
-        Ws, bs, at = [], [], 0
-        for i, o in zip(self.dims[:-1], self.dims[1:]):
+        """-> (weight per layer, bias per layer -- None under a batchnorm block --, gamma per block, beta per block)."""
+        Ws, bs, gammas, betas, at = [], [], [], [], 0
+        for l, (i, o) in enumerate(zip(self.dims[:-1], self.dims[1:])):
             Ws.append(flat[at:at + o * i].view(o, i))
-            bs.append(flat[at + o * i:at + o * i + o])
-            at += o * i + o
-        return Ws, bs
+            at += o * i
+            if self.bn and l < len(self.dims) - 2:
+                gammas.append(flat[at:at + o]), betas.append(flat[at + o:at + 2 * o]), bs.append(None)
+                at += 2 * o
+            else:
+                bs.append(flat[at:at + o])
+                at += o
+        return Ws, bs, gammas, betas
 
-    def forward(self, z, st):
-        """-> logits [rows, Kpad] (a view of the last activation buffer) of the fp32 rows z."""
-        z, ld = _f32_rows(z, self.dims[0])
-        n = int(z.shape[0])
-        src, n_layers = z, len(self.W)
-        for l in range(n_layers):
+    def forward(self, x, ld, st):
+        """-> logits [rows, Kpad] (a view of the last activation buffer) of the fp32 rows x of pitch ld (``_f32_rows``)."""
+        n, last = int(x.shape[0]), len(self.W) - 1
+        for l in range(last + 1):
             i, o = self.dims[l], self.dims[l + 1]
-            rc = self.L.lla_gemm_f32(_lib.ptr(src), ld, _lib.ptr(self.W[l]), i, _lib.ptr(self.b[l]), _lib.ptr(self.acts[l]), o,
-                                     n, o, i, int(l < n_layers - 1), st)
+            block = self.bn and l < last
+            rc = self.L.lla_gemm_f32(_lib.ptr(x), ld, _lib.ptr(self.W[l]), i, _lib.ptr(self.b[l]),
+                                     _lib.ptr(self.pre[l] if block else self.acts[l]), o, n, o, i, int(l < last and not self.bn), st)
             _lib.check(rc, "lla_gemm_f32")
-            src, ld = self.acts[l], o
-        self._input = z
+            if block:
+                self.bn_fwd(l, n, st)
+            x, ld = self.acts[l], o
         return self.acts[-1][:n]
 
-    def step(self, z, y, slot):
-        """One training step on the minibatch (z, y int32 class indexes); its loss sum and rows right go to ``slot``."""
+    def bn_fwd(self, l, n, st):
+        """Block l's pre-norm buffer -> its activation; batch and running statistics; the dropout mask of step ``t``."""
+        P, o = _lib.ptr, self.dims[l + 1]
+        rc = self.L.lla_bn_relu_dropout_fwd(P(self.pre[l]), o, P(self.gamma[l]), P(self.beta[l]), P(self.acts[l]), o,
+                                            P(self.mean[l]), P(self.rstd[l]), P(self.rm[l]), P(self.rv[l]), n, o, self.eps,
+                                            self.momentum, self.p, self.seed, self.t, l, st)
+        _lib.check(rc, "lla_bn_relu_dropout_fwd")
+
+    def xent(self, y, n, st):
+        """The logits and y -> the residual (scale 1 / n) in ``dlogits``; the loss sum and rows right in slot ``k``."""
+        P, kpad = _lib.ptr, self.dims[-1]
+        rc = self.L.lla_softmax_xent(P(self.acts[-1]), kpad, P(y), n, self.K, kpad, 1.0 / n, P(self.dlogits), kpad,
+                                     P(self.loss[self.k:]), P(self.right[self.k:]), P(self.ws), st)
+        _lib.check(rc, "lla_softmax_xent")
+
+    def tn(self, l, delta, ldd, below, ldb, n, st):
+        """Layer l's dW = delta^T below, and the column sums of delta as db where the layer has a bias."""
+        P, i, o = _lib.ptr, self.dims[l], self.dims[l + 1]
+        rc = self.L.lla_gemm_f32_tn(P(delta), ldd, P(below), ldb, P(self.gW[l]), i, P(self.gb[l]), n, o, i, st)
+        _lib.check(rc, "lla_gemm_f32_tn")
+
+    def nn(self, l, delta, ldd, below, ldb, n, st):
+        """-> the gradient below layer l (pitch in_l): delta W_l where ``below``, the output of block l - 1, is positive."""
+        P, i, o, out = _lib.ptr, self.dims[l], self.dims[l + 1], self.delta[l - 1]
+        rc = self.L.lla_gemm_f32_nn(P(delta), ldd, P(self.W[l]), i, P(below), ldb, P(out), i, n, o, i, st)
+        _lib.check(rc, "lla_gemm_f32_nn")
+        return out
+
+    def bn_bwd(self, l, g, da, n, st):
+        """The gradient g of block l's output -> dgamma, dbeta and the gradient da of its pre-norm buffer (in place: da = g)."""
+        P, o = _lib.ptr, self.dims[l + 1]
+        rc = self.L.lla_bn_bwd(P(g), o, P(self.pre[l]), o, P(self.gamma[l]), P(self.mean[l]), P(self.rstd[l]), self.p,
+                               P(self.ggamma[l]), P(self.gbeta[l]), P(da), o, n, o, st)
+        _lib.check(rc, "lla_bn_bwd")
+
+    def adamw(self, bc1, bc2, st):
+        P, a = _lib.ptr, self.adam
+        rc = self.L.lla_adamw_step(P(self.flat[0]), P(self.flat[1]), P(self.flat[2]), P(self.flat[3]), self.n, a.lr, a.b1, a.b2,
+                                   a.eps, a.wd, bc1, bc2, st)
+        _lib.check(rc, "lla_adamw_step")
+
+    def step(self, z, y):
+        """One training step on the minibatch (z, y int32 class indexes), the epoch's next."""
+        if self.k == self.loss.numel():
+            raise RuntimeError(f"the engine was sized for {self.k} steps an epoch: epoch_totals() starts the next one")
         n = int(z.shape[0])
-        L, a, n_layers = self.L, self.adam, len(self.W)
         with torch.cuda.device(self.device):
             st = _lib.stream_ptr(self.device)
-            self.forward(z, st)
-            kpad = self.dims[-1]
-            rc = L.lla_softmax_xent(_lib.ptr(self.acts[-1]), kpad, _lib.ptr(y), n, self.K, kpad, 1.0 / n, _lib.ptr(self.dlogits),
-                                    kpad, _lib.ptr(self.loss[slot:]), _lib.ptr(self.right[slot:]), _lib.ptr(self.ws), st)
-            _lib.check(rc, "lla_softmax_xent")
-            delta, ldd = self.dlogits, kpad
-            x0, ld0 = _f32_rows(self._input, self.dims[0])
-            for l in range(n_layers - 1, -1, -1):
-                i, o = self.dims[l], self.dims[l + 1]
-                below, ldb = (self.acts[l - 1], i) if l > 0 else (x0, ld0)
-                rc = L.lla_gemm_f32_tn(_lib.ptr(delta), ldd, _lib.ptr(below), ldb, _lib.ptr(self.gW[l]), i, _lib.ptr(self.gb[l]),
-                                       n, o, i, st)
-                _lib.check(rc, "lla_gemm_f32_tn")
+            x, ld = _f32_rows(z, self.dims[0])
+            self.forward(x, ld, st)
+            self.xent(y, n, st)
+            delta, ldd = self.dlogits, self.dims[-1]
+            for l in range(len(self.W) - 1, -1, -1):
+                below, ldb = (self.acts[l - 1], self.dims[l]) if l > 0 else (x, ld)
+                self.tn(l, delta, ldd, below, ldb, n, st)
                 if l > 0:
-                    out = self.delta[l % 2]
-                    rc = L.lla_gemm_f32_nn(_lib.ptr(delta), ldd, _lib.ptr(self.W[l]), i, _lib.ptr(below), ldb, _lib.ptr(out),
-                                           int(out.stride(0)), n, o, i, st)
-                    _lib.check(rc, "lla_gemm_f32_nn")
-                    delta, ldd = out, int(out.stride(0))
+                    delta, ldd = self.nn(l, delta, ldd, below, ldb, n, st), self.dims[l]
+                    if self.bn:
+                        self.bn_bwd(l - 1, delta, delta, n, st)
             self.t += 1
-            bc1, bc2 = a.corrections(self.t)
-            rc = L.lla_adamw_step(_lib.ptr(self.p), _lib.ptr(self.g), _lib.ptr(self.m), _lib.ptr(self.v), self.n, a.lr, a.b1, a.b2,
-                                  a.eps, a.wd, bc1, bc2, st)
-            _lib.check(rc, "lla_adamw_step")
-        return slot
+            self.k += 1
+            self.adamw(*self.adam.corrections(self.t), st)
 
-    def epoch_totals(self, slots):
-        n = len(slots)
-        return float(self.loss[:n].sum()), int(self.right[:n].sum())
+    def epoch_totals(self):
+        """-> (loss sum, rows right) over the epoch's steps, in one read-back; the next step is the next epoch's first."""
+        k, self.k = self.k, 0
+        loss, right = torch.stack((self.loss[:k].sum(), self.right[:k].sum().double())).tolist()
+        return loss, int(right)
 
-    def parameters(self, n_out):
+    def fitted(self, n_out):
+        """-> (weights, biases), copies without the padding; with batchnorm blocks (weights, [the last bias], gammas, betas,
+        running means, running variances)."""
         Ws = [W.clone() for W in self.W[:-1]] + [self.W[-1][:n_out].clone()]
-        return Ws, [b.clone() for b in self.b[:-1]] + [self.b[-1][:n_out].clone()]
+        if not self.bn:
+            return Ws, [b.clone() for b in self.b[:-1]] + [self.b[-1][:n_out].clone()]
+        rest = (self.gamma, self.beta, self.rm, self.rv)
+        return (Ws, [self.b[-1][:n_out].clone()]) + tuple([t.clone() for t in group] for group in rest)
 
 
-class MLPProbe(_Scores):
+class _MinibatchProbe(_Scores):
+    """What ``MLPProbe`` and ``BatchNormMLPProbe`` share: the hyper-parameters of the network and of AdamW, the walk over
+    shuffled minibatches, and the fit around an engine -- ``_DeviceMLP`` on the device, a float64 twin on the CPU, one
+    interface: ``step(z, y)``, ``epoch_totals()``, ``fitted(n_out)``.  A subclass gives ``_trainer`` (-> the engine and the
+    learning rate of every epoch, or None for a constant one; it may draw from the generator) and ``_store``."""
+
+    _MIN_ROWS, _COUNTS = 1, "n_hid_layers, epochs and batch_size must be at least 1"     # (rows a minibatch needs)
+    coefs_ = intercepts_ = None
+
+    def __init__(self, hid_dim, n_hid_layers, lr, weight_decay, betas, eps, epochs, batch_size, seed):
+        if int(hid_dim) < 8 or int(hid_dim) % 8:
+            raise ValueError(f"hid_dim must be a positive multiple of 8, got {hid_dim}")
+        if int(n_hid_layers) < 1 or int(epochs) < 1 or int(batch_size) < self._MIN_ROWS:
+            raise ValueError(self._COUNTS)
+        if not lr > 0 or weight_decay < 0 or not eps >= 0 or not all(0 <= b < 1 for b in betas):
+            raise ValueError("need lr > 0, weight_decay >= 0, eps >= 0 and betas in [0, 1)")
+        self.hid_dim, self.n_hid_layers, self.epochs, self.batch_size = int(hid_dim), int(n_hid_layers), int(epochs), int(batch_size)
+        self.lr, self.weight_decay, self.betas, self.eps, self.seed = float(lr), float(weight_decay), tuple(betas), float(eps), int(seed)
+
+    @staticmethod
+    def _tensor(data):
+        t = data if isinstance(data, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(data))
+        if t.dim() != 2:
+            raise ValueError("data must be [N, C]")
+        if t.dtype == torch.float16:
+            raise ValueError("fp16 rows are not built for MLPProbe: pass float32")
+        if t.dtype not in (torch.float32, torch.float64) or (t.device.type == "cuda" and t.dtype != torch.float32):
+            t = t.to(torch.float32)
+        return t
+
+    def _epoch(self, data, rows, n, g, decode_group):
+        """-> (the epoch's order, an iterator over its minibatches of rows in that order)."""
+        bs = self.batch_size
+        if rows is None:                     # batches() draws randperm(n, generator=g) itself: the same draw from a copy of g
+            twin = torch.Generator()
+            twin.set_state(g.get_state())
+            order = torch.randperm(n, generator=twin)
+            walk = data.batches(bs, shuffle=True, generator=g, decode_group=decode_group)
+            return order, (b[0] if isinstance(b, tuple) else b for b in walk)
+        order = torch.randperm(n, generator=g)
+        group = max(int(decode_group) // bs, 1) * bs
+
+        def walk():
+            for g0 in range(0, n, group):
+                z = rows[order[g0:g0 + group].to(rows.device)]
+                for b0 in range(0, int(z.shape[0]), bs):
+                    yield z[b0:b0 + bs]
+        return order, walk()
+
+    def fit(self, data, labels=None, decode_group=65536):
+        if _is_latents(data):
+            rows, device, n, dim = None, data.device, len(data), int(data.z_dim)
+        else:
+            rows = self._tensor(data)
+            device, n, dim = rows.device, int(rows.shape[0]), int(rows.shape[1])
+        if dim % 8:
+            raise ValueError(f"in_dim must be a multiple of 8, got {dim}")
+        if 0 < n % self.batch_size < self._MIN_ROWS:
+            raise ValueError(f"N = {n} rows with batch_size = {self.batch_size} leave a last minibatch of one row, which batchnorm "
+                             "cannot normalise: choose another batch_size (no row is dropped silently)")
+        y = _labels_of(data, labels, n)
+        classes, _, _ = _class_indexes(y)
+        idx = torch.searchsorted(classes, y)                  # class k is classes_[k], for two classes too
+        K = int(classes.numel())
+        if K > 1024:
+            raise ValueError(f"lla_softmax_xent takes up to 1024 classes, got {K}")
+        g = torch.Generator().manual_seed(self.seed)
+        Ws, bs = _mlp_init([dim] + [self.hid_dim] * self.n_hid_layers + [K], g)
+        adam = _Adam(self.lr, self.weight_decay, self.betas, self.eps)
+        engine, rates = self._trainer(Ws, bs, adam, g, device, min(self.batch_size, n), K, -(-n // self.batch_size))
+        if device.type == "cuda":
+            idx = idx.to(torch.int32).to(device)
+        self.loss_curve_, self.accuracy_curve_ = [], []
+        for epoch in range(self.epochs):
+            if rates is not None:
+                adam.lr = rates[epoch]
+            order, walk = self._epoch(data, rows, n, g, decode_group)
+            y_epoch, at = idx[order.to(idx.device)].contiguous(), 0
+            for z in walk:
+                bn = int(z.shape[0])
+                engine.step(z, y_epoch[at:at + bn])
+                at += bn
+            loss, right = engine.epoch_totals()
+            self.loss_curve_.append(loss / n)
+            self.accuracy_curve_.append(right / n)
+        self.classes_, self.n_steps_ = classes.numpy(), engine.t
+        self._store(*engine.fitted(K))
+        return self
+
+    def predict_proba(self, data, rows_per_pass=65536):
+        return torch.softmax(self.decision_function(data, rows_per_pass), 1)
+
+
+class MLPProbe(_MinibatchProbe):
     """``MLPProbe(hid_dim=2048, n_hid_layers=2, lr=1e-3, weight_decay=1e-5, betas=(0.9, 0.999), eps=1e-8, epochs=10,
     batch_size=128, seed=0)``: the reference's non-linear predictor -- its ``MLP`` (lossyless/architectures.py:94-168) AT ITS
     CLASS DEFAULTS (``norm_layer="identity"``, ``activation="ReLU"``, ``dropout_p=0``: Linear -> ReLU per hidden layer with
@@ -1444,88 +1614,17 @@ class MLPProbe(_Scores):
             raise ValueError("dropout_p > 0 is not built here: MLPProbe is the reference's MLP with dropout_p=0 (dropout: BatchNormMLPProbe)")
         if scheduler is not None:
             raise ValueError("learning-rate schedulers are not built here (scheduler=: BatchNormMLPProbe)")
-        if int(hid_dim) < 8 or int(hid_dim) % 8:
-            raise ValueError(f"hid_dim must be a positive multiple of 8, got {hid_dim}")
-        if int(n_hid_layers) < 1 or int(epochs) < 1 or int(batch_size) < 1:
-            raise ValueError("n_hid_layers, epochs and batch_size must be at least 1")
-        if not lr > 0 or weight_decay < 0 or not eps >= 0 or not all(0 <= b < 1 for b in betas):
-            raise ValueError("need lr > 0, weight_decay >= 0, eps >= 0 and betas in [0, 1)")
-        self.hid_dim, self.n_hid_layers, self.epochs, self.batch_size = int(hid_dim), int(n_hid_layers), int(epochs), int(batch_size)
-        self.lr, self.weight_decay, self.betas, self.eps, self.seed = float(lr), float(weight_decay), tuple(betas), float(eps), int(seed)
-        self.coefs_ = self.intercepts_ = self.classes_ = None
+        super().__init__(hid_dim, n_hid_layers, lr, weight_decay, betas, eps, epochs, batch_size, seed)
         self._packed = None
 
     # ------------------------------------------------------------------ fit
-    @staticmethod
-    def _tensor(data):
-        t = data if isinstance(data, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(data))
-        if t.dim() != 2:
-            raise ValueError("data must be [N, C]")
-        if t.dtype == torch.float16:
-            raise ValueError("fp16 rows are not built for MLPProbe: pass float32")
-        if t.dtype not in (torch.float32, torch.float64) or (t.device.type == "cuda" and t.dtype != torch.float32):
-            t = t.to(torch.float32)
-        return t
-
-    def _epoch(self, data, rows, n, g, decode_group):
-        """-> (the epoch's order, an iterator over its minibatches of rows in that order)."""
-        bs = self.batch_size
-        if rows is None:                     # batches() draws randperm(n, generator=g) itself: the same draw from a copy of g
-            twin = torch.Generator()
-            twin.set_state(g.get_state())
-            order = torch.randperm(n, generator=twin)
-            walk = data.batches(bs, shuffle=True, generator=g, decode_group=decode_group)
-            return order, (b[0] if isinstance(b, tuple) else b for b in walk)
-        order = torch.randperm(n, generator=g)
-        group = max(int(decode_group) // bs, 1) * bs
-
-        def walk():
-            for g0 in range(0, n, group):
-                z = rows[order[g0:g0 + group].to(rows.device)]
-                for b0 in range(0, int(z.shape[0]), bs):
-                    yield z[b0:b0 + bs]
-        return order, walk()
-
-    def fit(self, data, labels=None, decode_group=65536):
-        if _is_latents(data):
-            rows, device, n, dim = None, data.device, len(data), int(data.z_dim)
-        else:
-            rows = self._tensor(data)
-            device, n, dim = rows.device, int(rows.shape[0]), int(rows.shape[1])
-        if dim % 8:
-            raise ValueError(f"in_dim must be a multiple of 8, got {dim}")
-        y = _labels_of(data, labels, n)
-        classes, _, _ = _class_indexes(y)
-        idx = torch.searchsorted(classes, y)                  # class k is classes_[k], for two classes too
-        K = int(classes.numel())
-        if K > 1024:
-            raise ValueError(f"lla_softmax_xent takes up to 1024 classes, got {K}")
-        g = torch.Generator().manual_seed(self.seed)
-        Ws, bs = _mlp_init([dim] + [self.hid_dim] * self.n_hid_layers + [K], g)
-        adam = _Adam(self.lr, self.weight_decay, self.betas, self.eps)
-        steps = -(-n // self.batch_size)
+    def _trainer(self, Ws, bs, adam, g, device, rows, K, steps):
         if device.type == "cuda":
-            engine = _DeviceMLP(Ws, bs, adam, device, min(self.batch_size, n), K, max_steps=steps)
-            idx = idx.to(torch.int32).to(device)
-        else:
-            engine = _TwinMLP(Ws, bs, adam)
-        self.loss_curve_, self.accuracy_curve_ = [], []
-        for _ in range(self.epochs):
-            order, walk = self._epoch(data, rows, n, g, decode_group)
-            y_epoch, at, sums = idx[order.to(idx.device)].contiguous(), 0, []
-            for z in walk:
-                bn = int(z.shape[0])
-                if device.type == "cuda":
-                    sums.append(engine.step(z, y_epoch[at:at + bn], len(sums)))
-                else:
-                    sums.append(engine.step(z, y_epoch[at:at + bn]))
-                at += bn
-            loss, right = engine.epoch_totals(sums)
-            self.loss_curve_.append(loss / n)
-            self.accuracy_curve_.append(right / n)
-        self.coefs_, self.intercepts_ = engine.parameters(K)
-        self.classes_, self.n_steps_, self._packed = classes.numpy(), engine.t, None
-        return self
+            return _DeviceMLP(Ws, bs, adam, device, rows, K, steps), None
+        return _TwinMLP(Ws, bs, adam), None
+
+    def _store(self, coefs, intercepts):
+        self.coefs_, self.intercepts_, self._packed = coefs, intercepts, None
 
     # ------------------------------------------------------------------ predict
     def _engine(self, dev):
@@ -1554,16 +1653,13 @@ class MLPProbe(_Scores):
                     for g0, z in rows.groups():
                         for r0 in range(0, int(z.shape[0]), self._PIECE):
                             zz = z[r0:r0 + self._PIECE]
-                            out[g0 + r0:g0 + r0 + int(zz.shape[0])] = eng.forward(zz, st)[:, :K]
+                            out[g0 + r0:g0 + r0 + int(zz.shape[0])] = eng.forward(*_f32_rows(zz, C), st)[:, :K]
                 return out
             twin = _TwinMLP([W.cpu() for W in self.coefs_], [b.cpu() for b in self.intercepts_], None)
             parts = [twin.forward(z)[0] for _, z in rows.groups()]
             return torch.cat(parts) if parts else torch.zeros((0, K), dtype=torch.float64)
         finally:
             rows.close()
-
-    def predict_proba(self, data, rows_per_pass=65536):
-        return torch.softmax(self.decision_function(data, rows_per_pass), 1)
 
     def state_dict(self):
         """The fitted weights under the keys of the reference's ``MLP`` (``module`` is Linear, Norm, Activation, Dropout per
@@ -1654,7 +1750,7 @@ def _fold_batchnorm(Ws, b_last, gammas, betas, rms, rvs, eps):
     return fW + [Ws[-1].double().cpu()], fb + [b_last.double().cpu()]
 
 
-class _TwinBNMLP:
+class _TwinBNMLP(_Twin):
     """The float64 twin of a training step of Linear(bias=False) -> BatchNorm1d -> ReLU -> Dropout blocks and a last Linear:
     every formula of csrc/batchnorm.hip and csrc/mlp.hip written out by hand, no autograd.  The CPU path of
     ``BatchNormMLPProbe`` and the oracle of its GPU tests.  ``step`` numbers the minibatches from 0 (the dropout counter)."""
@@ -1666,9 +1762,8 @@ class _TwinBNMLP:
         self.betas = [torch.zeros(W.shape[0], dtype=f64) for W in Ws[:-1]]
         self.rms = [torch.zeros(W.shape[0], dtype=f64) for W in Ws[:-1]]
         self.rvs = [torch.ones(W.shape[0], dtype=f64) for W in Ws[:-1]]
-        self.adam, self.t, self.p, self.s, self.seed = adam, 0, float(p), _dropout_scale(p), int(seed)
-        self.momentum, self.eps = float(momentum), float(eps)
-        self._state = None
+        self.p, self.s, self.seed, self.momentum, self.eps = float(p), _dropout_scale(p), int(seed), float(momentum), float(eps)
+        super().__init__(adam)
 
     def _params(self):
         return self.Ws + self.gammas + self.betas + [self.b]
@@ -1713,132 +1808,14 @@ class _TwinBNMLP:
         return loss, right, gW + gg + gb + [g_last]
 
     def step(self, x, y):
-        loss, right, grads = self.gradients(x, y, track=True)
-        a = self.adam
-        if self._state is None:
-            self._state = [(torch.zeros_like(p), torch.zeros_like(p)) for p in self._params()]
-        self.t += 1
-        bc1, bc2 = a.corrections(self.t)
-        for p, g, (m, v) in zip(self._params(), grads, self._state):         # lla_adamw_step
-            p.mul_(1.0 - a.lr * a.wd)
-            m.copy_(a.b1 * m + (1.0 - a.b1) * g)
-            v.copy_(a.b2 * v + (1.0 - a.b2) * g * g)
-            p.sub_((a.lr / bc1) * m / (v.sqrt() / bc2 ** 0.5 + a.eps))
-        return loss, right
-
-    def epoch_totals(self, sums):
-        return float(sum(s[0] for s in sums)), int(sum(s[1] for s in sums))
+        self._update(*self.gradients(x, y, track=True))                      # lla_adamw_step
 
     def fitted(self, n_out):
         """-> (Ws, b_last, gammas, betas, running means, running variances), copies."""
         return tuple([t.clone() for t in group] for group in (self.Ws, [self.b], self.gammas, self.betas, self.rms, self.rvs))
 
 
-class _DeviceBNMLP:
-    """The same step on the device, beside ``_DeviceMLP``.  Parameters, gradients and the two moments each live in ONE flat
-    fp32 buffer -- per hidden block its weight [out][in], gamma [out], beta [out]; then the last weight [Kpad][in] and its
-    bias [Kpad] -- so one ``lla_adamw_step`` updates everything, gamma and beta included (the reference hands
-    ``self.parameters()`` to one group: lossyless/predictors.py:226).  Running statistics live outside it.  Per step and
-    block: ``lla_gemm_f32`` (bias = NULL, relu = 0) into the pre-norm buffer, ``lla_bn_relu_dropout_fwd`` into the
-    activation; the last ``lla_gemm_f32`` and ``lla_softmax_xent``; then per layer from the top ``lla_gemm_f32_tn`` and
-    ``lla_gemm_f32_nn`` with H = the block's output, and ``lla_bn_bwd`` in place on that gradient.  Nothing is read back
-    during an epoch."""
-
-    def __init__(self, Ws, b_last, adam, device, max_rows, n_classes, max_steps, p, seed, momentum, eps):
-        self.L, self.device, self.adam, self.t = _lib.lib(), device, adam, 0
-        self.K, self.p, self.seed, self.momentum, self.eps = int(n_classes), float(p), int(seed), float(momentum), float(eps)
-        self.dims = [int(Ws[0].shape[1])] + [int(W.shape[0]) for W in Ws[:-1]] + [-(-self.K // 8) * 8]
-        if any(d % 8 for d in self.dims[:-1]):
-            raise ValueError(f"the device path needs layer widths that are multiples of 8, got {self.dims[:-1]}")
-        pairs = list(zip(self.dims[:-1], self.dims[1:]))
-        self.n = sum(o * i + 2 * o for i, o in pairs[:-1]) + pairs[-1][1] * pairs[-1][0] + pairs[-1][1]
-        f32 = dict(dtype=torch.float32, device=device)
-        self.flat = [torch.zeros(self.n, **f32) for _ in range(4)]           # parameters, gradients, first and second moment
-        (self.W, self.gamma, self.beta, self.b), (self.gW, self.ggamma, self.gbeta, self.gb) = map(self._views, self.flat[:2])
-        for l, W in enumerate(Ws):
-            self.W[l][:W.shape[0]].copy_(W.to(torch.float32))
-        self.b[:b_last.shape[0]].copy_(b_last.to(torch.float32))
-        for ga in self.gamma:
-            ga.fill_(1.0)
-        hidden = self.dims[1:-1]
-        self.rm = [torch.zeros(o, **f32) for o in hidden]
-        self.rv = [torch.ones(o, **f32) for o in hidden]
-        self.mean = [torch.empty(o, **f32) for o in hidden]
-        self.rstd = [torch.empty(o, **f32) for o in hidden]
-        self.rows = max(int(max_rows), 2)
-        self.pre = [torch.empty((self.rows, o), **f32) for o in hidden]
-        self.acts = [torch.empty((self.rows, o), **f32) for o in self.dims[1:]]
-        self.dlogits = torch.empty((self.rows, self.dims[-1]), **f32)
-        self.delta = [torch.empty((self.rows, o), **f32) for o in hidden]
-        self.loss = torch.zeros(max_steps, dtype=torch.float64, device=device)
-        self.right = torch.zeros(max_steps, dtype=torch.int32, device=device)
-        self.ws = torch.empty(int(self.L.lla_softmax_xent_workspace_bytes(self.rows)), dtype=torch.uint8, device=device)
-
-    def _views(self, flat):
-        Ws, gammas, betas, at = [], [], [], 0
-        for i, o in list(zip(self.dims[:-1], self.dims[1:]))[:-1]:
-            Ws.append(flat[at:at + o * i].view(o, i))
-            gammas.append(flat[at + o * i:at + o * i + o])
-            betas.append(flat[at + o * i + o:at + o * i + 2 * o])
-            at += o * i + 2 * o
-        i, o = self.dims[-2], self.dims[-1]
-        Ws.append(flat[at:at + o * i].view(o, i))
-        return Ws, gammas, betas, flat[at + o * i:at + o * i + o]
-
-    def step(self, z, y, slot):
-        """One training step on the minibatch (z, y int32 class indexes); its loss sum and rows right go to ``slot``."""
-        n = int(z.shape[0])
-        L, a, P, n_layers = self.L, self.adam, _lib.ptr, len(self.W)
-        with torch.cuda.device(self.device):
-            st = _lib.stream_ptr(self.device)
-            x0, ld0 = _f32_rows(z, self.dims[0])
-            src, ld = x0, ld0
-            for l in range(n_layers - 1):
-                i, o = self.dims[l], self.dims[l + 1]
-                _lib.check(L.lla_gemm_f32(P(src), ld, P(self.W[l]), i, None, P(self.pre[l]), o, n, o, i, 0, st), "lla_gemm_f32")
-                rc = L.lla_bn_relu_dropout_fwd(P(self.pre[l]), o, P(self.gamma[l]), P(self.beta[l]), P(self.acts[l]), o,
-                                               P(self.mean[l]), P(self.rstd[l]), P(self.rm[l]), P(self.rv[l]), n, o, self.eps,
-                                               self.momentum, self.p, self.seed, self.t, l, st)
-                _lib.check(rc, "lla_bn_relu_dropout_fwd")
-                src, ld = self.acts[l], o
-            i, kpad = self.dims[-2], self.dims[-1]
-            _lib.check(L.lla_gemm_f32(P(src), ld, P(self.W[-1]), i, P(self.b), P(self.acts[-1]), kpad, n, kpad, i, 0, st),
-                       "lla_gemm_f32")
-            rc = L.lla_softmax_xent(P(self.acts[-1]), kpad, P(y), n, self.K, kpad, 1.0 / n, P(self.dlogits), kpad,
-                                    P(self.loss[slot:]), P(self.right[slot:]), P(self.ws), st)
-            _lib.check(rc, "lla_softmax_xent")
-            delta, ldd = self.dlogits, kpad
-            for l in range(n_layers - 1, -1, -1):
-                i, o = self.dims[l], self.dims[l + 1]
-                below, ldb = (self.acts[l - 1], i) if l > 0 else (x0, ld0)
-                db = self.gb if l == n_layers - 1 else None
-                _lib.check(L.lla_gemm_f32_tn(P(delta), ldd, P(below), ldb, P(self.gW[l]), i, P(db), n, o, i, st), "lla_gemm_f32_tn")
-                if l > 0:
-                    out = self.delta[l - 1]
-                    _lib.check(L.lla_gemm_f32_nn(P(delta), ldd, P(self.W[l]), i, P(below), ldb, P(out), i, n, o, i, st),
-                               "lla_gemm_f32_nn")
-                    rc = L.lla_bn_bwd(P(out), i, P(self.pre[l - 1]), i, P(self.gamma[l - 1]), P(self.mean[l - 1]),
-                                      P(self.rstd[l - 1]), self.p, P(self.ggamma[l - 1]), P(self.gbeta[l - 1]), P(out), i, n, i, st)
-                    _lib.check(rc, "lla_bn_bwd")
-                    delta, ldd = out, i
-            self.t += 1
-            bc1, bc2 = a.corrections(self.t)
-            rc = L.lla_adamw_step(P(self.flat[0]), P(self.flat[1]), P(self.flat[2]), P(self.flat[3]), self.n, a.lr, a.b1, a.b2,
-                                  a.eps, a.wd, bc1, bc2, st)
-            _lib.check(rc, "lla_adamw_step")
-        return slot
-
-    def epoch_totals(self, slots):
-        n = len(slots)
-        return float(self.loss[:n].sum()), int(self.right[:n].sum())
-
-    def fitted(self, n_out):
-        Ws = [W.clone() for W in self.W[:-1]] + [self.W[-1][:n_out].clone()]
-        return (Ws, [self.b[:n_out].clone()], [t.clone() for t in self.gamma], [t.clone() for t in self.beta],
-                [t.clone() for t in self.rm], [t.clone() for t in self.rv])
-
-
-class BatchNormMLPProbe(_Scores):
+class BatchNormMLPProbe(_MinibatchProbe):
     """``BatchNormMLPProbe(hid_dim=2048, n_hid_layers=2, lr=3e-4, weight_decay=1e-5, betas=(0.9, 0.999), eps=1e-8, epochs=10,
     batch_size=128, seed=0, norm_layer="batchnorm", activation="ReLU", dropout_p=0.2, scheduler=None, decay_factor=100,
     k_steps=3, bn_momentum=0.1, bn_eps=1e-5)``: the reference's predictor AS ITS CONFIGURATION BUILDS IT
@@ -1857,7 +1834,7 @@ class BatchNormMLPProbe(_Scores):
     seed and the position alone, the same on the device and on the CPU.  A last minibatch of ONE row cannot be normalised:
     ``fit`` raises before any training.
 
-    GPU latents and CUDA tensors train in the kernels of csrc/batchnorm.hip and csrc/mlp.hip (``_DeviceBNMLP``):
+    GPU latents and CUDA tensors train in the kernels of csrc/batchnorm.hip and csrc/mlp.hip (``_DeviceMLP`` with ``bn``):
     deterministic, bit for bit.  CPU data trains in the float64 twin (``_TwinBNMLP``).  ``decision_function`` / ``predict`` /
     ``predict_proba`` / ``score`` are evaluation mode: running statistics, no dropout -- each block folded on the host in
     float64 into a Linear with a bias and run as ``MLPProbe`` runs its forward pass (fp32 on the device, float64 on the CPU).
@@ -1867,8 +1844,7 @@ class BatchNormMLPProbe(_Scores):
     ``accuracy_curve_`` (training mode, with dropout), ``lr_curve_``, ``n_steps_``.  ``state_dict()`` has the keys of the
     reference's module and loads with ``strict=True``."""
 
-    _tensor = staticmethod(MLPProbe._tensor)
-    _epoch = MLPProbe._epoch
+    _MIN_ROWS, _COUNTS = 2, "n_hid_layers and epochs must be at least 1, batch_size at least 2"
 
     def __init__(self, hid_dim=2048, n_hid_layers=2, lr=3e-4, weight_decay=1e-5, betas=(0.9, 0.999), eps=1e-8, epochs=10,
                  batch_size=128, seed=0, norm_layer="batchnorm", activation="ReLU", dropout_p=0.2, scheduler=None,
@@ -1884,69 +1860,25 @@ class BatchNormMLPProbe(_Scores):
             raise ValueError(f"scheduler={scheduler!r} is not built: None, 'unifmultistep' or 'expdecay'")
         if not decay_factor > 0 or int(k_steps) < 1:
             raise ValueError("need decay_factor > 0 and k_steps >= 1")
-        if int(hid_dim) < 8 or int(hid_dim) % 8:
-            raise ValueError(f"hid_dim must be a positive multiple of 8, got {hid_dim}")
-        if int(n_hid_layers) < 1 or int(epochs) < 1 or int(batch_size) < 2:
-            raise ValueError("n_hid_layers and epochs must be at least 1, batch_size at least 2")
-        if not lr > 0 or weight_decay < 0 or not eps >= 0 or not all(0 <= b < 1 for b in betas):
-            raise ValueError("need lr > 0, weight_decay >= 0, eps >= 0 and betas in [0, 1)")
+        super().__init__(hid_dim, n_hid_layers, lr, weight_decay, betas, eps, epochs, batch_size, seed)
         if not 0 <= bn_momentum <= 1 or not bn_eps >= 0:
             raise ValueError("need 0 <= bn_momentum <= 1 and bn_eps >= 0")
-        self.hid_dim, self.n_hid_layers, self.epochs, self.batch_size = int(hid_dim), int(n_hid_layers), int(epochs), int(batch_size)
-        self.lr, self.weight_decay, self.betas, self.eps, self.seed = float(lr), float(weight_decay), tuple(betas), float(eps), int(seed)
         self.dropout_p, self.scheduler, self.decay_factor, self.k_steps = float(dropout_p), scheduler, decay_factor, int(k_steps)
         self.bn_momentum, self.bn_eps = float(bn_momentum), float(bn_eps)
-        self.coefs_ = self.intercepts_ = self.classes_ = None
         self._folded = None
 
-    def fit(self, data, labels=None, decode_group=65536):
-        if _is_latents(data):
-            rows, device, n, dim = None, data.device, len(data), int(data.z_dim)
-        else:
-            rows = self._tensor(data)
-            device, n, dim = rows.device, int(rows.shape[0]), int(rows.shape[1])
-        if dim % 8:
-            raise ValueError(f"in_dim must be a multiple of 8, got {dim}")
-        if n % self.batch_size == 1:
-            raise ValueError(f"N = {n} rows with batch_size = {self.batch_size} leave a last minibatch of one row, which batchnorm "
-                             "cannot normalise: choose another batch_size (no row is dropped silently)")
-        y = _labels_of(data, labels, n)
-        classes, _, _ = _class_indexes(y)
-        idx = torch.searchsorted(classes, y)
-        K = int(classes.numel())
-        if K > 1024:
-            raise ValueError(f"lla_softmax_xent takes up to 1024 classes, got {K}")
-        g = torch.Generator().manual_seed(self.seed)
-        Ws, bs = _mlp_init([dim] + [self.hid_dim] * self.n_hid_layers + [K], g)
+    def _trainer(self, Ws, bs, adam, g, device, rows, K, steps):
         lo, hi = (int(w) for w in torch.randint(0, 2 ** 32, (2,), generator=g, dtype=torch.int64))
         self.dropout_seed_ = lo | (hi << 32)
         self.lr_curve_ = lr_schedule(self.scheduler, self.lr, self.epochs, self.decay_factor, self.k_steps)
-        adam = _Adam(self.lr, self.weight_decay, self.betas, self.eps)
-        steps = -(-n // self.batch_size)
+        bn = (self.dropout_p, self.dropout_seed_, self.bn_momentum, self.bn_eps)
         if device.type == "cuda":
-            engine = _DeviceBNMLP(Ws, bs[-1], adam, device, min(self.batch_size, n), K, steps, self.dropout_p,
-                                  self.dropout_seed_, self.bn_momentum, self.bn_eps)
-            idx = idx.to(torch.int32).to(device)
-        else:
-            engine = _TwinBNMLP(Ws, bs[-1], adam, self.dropout_p, self.dropout_seed_, self.bn_momentum, self.bn_eps)
-        self.loss_curve_, self.accuracy_curve_ = [], []
-        for epoch in range(self.epochs):
-            adam.lr = self.lr_curve_[epoch]
-            order, walk = self._epoch(data, rows, n, g, decode_group)
-            y_epoch, at, sums = idx[order.to(idx.device)].contiguous(), 0, []
-            for z in walk:
-                bn = int(z.shape[0])
-                if device.type == "cuda":
-                    sums.append(engine.step(z, y_epoch[at:at + bn], len(sums)))
-                else:
-                    sums.append(engine.step(z, y_epoch[at:at + bn]))
-                at += bn
-            loss, right = engine.epoch_totals(sums)
-            self.loss_curve_.append(loss / n)
-            self.accuracy_curve_.append(right / n)
-        self.coefs_, self.intercepts_, self.bn_weights_, self.bn_biases_, self.running_means_, self.running_vars_ = engine.fitted(K)
-        self.classes_, self.n_steps_, self.num_batches_tracked_, self._folded = classes.numpy(), engine.t, engine.t, None
-        return self
+            return _DeviceMLP(Ws, bs, adam, device, rows, K, steps, bn), self.lr_curve_
+        return _TwinBNMLP(Ws, bs[-1], adam, *bn), self.lr_curve_
+
+    def _store(self, coefs, intercepts, gammas, betas, rms, rvs):
+        self.coefs_, self.intercepts_, self.bn_weights_, self.bn_biases_ = coefs, intercepts, gammas, betas
+        self.running_means_, self.running_vars_, self.num_batches_tracked_, self._folded = rms, rvs, self.n_steps_, None
 
     def _eval_probe(self):
         """The fitted network in evaluation mode as a plain ReLU MLP (``_fold_batchnorm``, rounded once to fp32 where the
@@ -1965,9 +1897,6 @@ class BatchNormMLPProbe(_Scores):
 
     def decision_function(self, data, rows_per_pass=65536):
         return self._eval_probe().decision_function(data, rows_per_pass)
-
-    def predict_proba(self, data, rows_per_pass=65536):
-        return torch.softmax(self.decision_function(data, rows_per_pass), 1)
 
     def state_dict(self):
         """The fitted tensors under the keys of the reference's ``MLP`` (``module`` is Linear, BatchNorm1d, ReLU, Dropout per

@@ -15,7 +15,7 @@ records (131072), decode included: a host clock around a call that ends in a dev
 With ``--bn`` the same four shapes and the same protocol measure ``BatchNormMLPProbe``'s step instead, three
 interleaved arms:
 
-(c) its device path (``_DeviceBNMLP.step``: the launches of (a) -- the hidden GEMMs without bias and ReLU -- plus 2 x
+(c) its device path (``_DeviceMLP.step`` with ``bn``: the launches of (a) -- the hidden GEMMs without bias and ReLU -- plus 2 x
     ``lla_bn_relu_dropout_fwd`` and 2 x ``lla_bn_bwd``),
 (d) torch eager fp32 on the same device: ``nn.Sequential`` (Linear(bias=False), BatchNorm1d, ReLU, Dropout(0.2) per block, then
     Linear) in training mode + ``F.cross_entropy`` + ``torch.optim.AdamW``,
@@ -38,7 +38,7 @@ import torch  # noqa: E402
 
 import hubconf  # noqa: E402
 from lossyless_amd import BatchNormMLPProbe, MLPProbe, _lib  # noqa: E402
-from lossyless_amd.probe import _Adam, _DeviceBNMLP, _DeviceMLP, _mlp_init  # noqa: E402
+from lossyless_amd.probe import _Adam, _DeviceMLP, _f32_rows, _mlp_init  # noqa: E402
 from latents_bench import interleaved, med  # noqa: E402
 
 IN, HID, LAYERS = 512, 2048, 2
@@ -63,33 +63,28 @@ def eager_arm(Ws, bs, x, y, dev):
     return step
 
 
+def one_step(eng, x, y):
+    """An arm: one training step of an engine sized for one step an epoch, each into slot 0."""
+    def arm():
+        eng.step(x, y)
+        eng.k = 0
+    return arm
+
+
 def kernels_of(eng, x, y):
-    """The launches of one step of (a), each as a call of its own on the engine's buffers."""
-    L, st, n = eng.L, _lib.stream_ptr(eng.device), int(x.shape[0])
-    d, kpad = eng.dims, eng.dims[-1]
-    eng.step(x, y, 0)
-    out = {"3 x lla_gemm_f32 (forward)": lambda: eng.forward(x, st),
-           "lla_softmax_xent": lambda: L.lla_softmax_xent(_lib.ptr(eng.acts[-1]), kpad, _lib.ptr(y), n, eng.K, kpad, 1.0 / n,
-                                                          _lib.ptr(eng.dlogits), kpad, _lib.ptr(eng.loss), _lib.ptr(eng.right),
-                                                          _lib.ptr(eng.ws), st)}
+    """The launches of one step of (a), each as a call of the engine's own method on the engine's buffers."""
+    st, n, d = _lib.stream_ptr(eng.device), int(x.shape[0]), eng.dims
+    one_step(eng, x, y)()
+    out = {"3 x lla_gemm_f32 (forward)": lambda: eng.forward(*_f32_rows(x, d[0]), st),
+           "lla_softmax_xent": lambda: eng.xent(y, n, st)}
     below = [x] + eng.acts[:-1]
-    delta = [eng.delta[1], eng.delta[0], eng.dlogits]      # any buffers of the right pitch: the values do not matter here
+    delta = eng.delta + [eng.dlogits]                      # layer l's incoming gradient: the values do not matter here
     for l in (2, 1, 0):
         i, o = d[l], d[l + 1]
-        dl, ldd = delta[l], int(delta[l].stride(0))
-        out[f"lla_gemm_f32_tn layer {l} (dW [{o}][{i}])"] = (
-            lambda l=l, i=i, o=o, dl=dl, ldd=ldd: L.lla_gemm_f32_tn(_lib.ptr(dl), ldd, _lib.ptr(below[l]), i, _lib.ptr(eng.gW[l]), i,
-                                                                    _lib.ptr(eng.gb[l]), n, o, i, st))
+        out[f"lla_gemm_f32_tn layer {l} (dW [{o}][{i}])"] = lambda l=l, i=i, o=o: eng.tn(l, delta[l], o, below[l], i, n, st)
         if l > 0:
-            dst = eng.delta[l % 2]
-            out[f"lla_gemm_f32_nn layer {l} (reduction {o})"] = (
-                lambda l=l, i=i, o=o, dl=dl, ldd=ldd, dst=dst: L.lla_gemm_f32_nn(_lib.ptr(dl), ldd, _lib.ptr(eng.W[l]), i,
-                                                                                 _lib.ptr(below[l]), i, _lib.ptr(dst),
-                                                                                 int(dst.stride(0)), n, o, i, st))
-    a = eng.adam
-    out[f"lla_adamw_step ({eng.n} parameters)"] = lambda: L.lla_adamw_step(_lib.ptr(eng.p), _lib.ptr(eng.g), _lib.ptr(eng.m),
-                                                                         _lib.ptr(eng.v), eng.n, a.lr, a.b1, a.b2, a.eps, a.wd,
-                                                                         0.1, 0.001, st)
+            out[f"lla_gemm_f32_nn layer {l} (reduction {o})"] = lambda l=l, i=i, o=o: eng.nn(l, delta[l], o, below[l], i, n, st)
+    out[f"lla_adamw_step ({eng.n} parameters)"] = lambda: eng.adamw(0.1, 0.001, st)
     return out
 
 
@@ -119,15 +114,42 @@ def bn_eager_arm(Ws, b_last, x, y, dev):
 
 
 def bn_kernels_of(eng, x, y):
-    """The two new launches of one step of (c), on the second block's buffers, each as a call of its own."""
-    L, st, n, P = eng.L, _lib.stream_ptr(eng.device), int(x.shape[0]), _lib.ptr
-    eng.step(x, y, 0)
-    o, g, da = eng.dims[2], eng.delta[0], torch.empty_like(eng.delta[0])
-    return {"lla_bn_relu_dropout_fwd": lambda: L.lla_bn_relu_dropout_fwd(
-                P(eng.pre[1]), o, P(eng.gamma[1]), P(eng.beta[1]), P(eng.acts[1]), o, P(eng.mean[1]), P(eng.rstd[1]), P(eng.rm[1]),
-                P(eng.rv[1]), n, o, eng.eps, eng.momentum, eng.p, eng.seed, 1, 1, st),
-            "lla_bn_bwd": lambda: L.lla_bn_bwd(P(g), o, P(eng.pre[1]), o, P(eng.gamma[1]), P(eng.mean[1]), P(eng.rstd[1]), eng.p,
-                                               P(eng.ggamma[1]), P(eng.gbeta[1]), P(da), o, n, o, st)}
+    """The two new launches of one step of (c), on the second block's buffers, each as a call of the engine's own method."""
+    st, n = _lib.stream_ptr(eng.device), int(x.shape[0])
+    one_step(eng, x, y)()
+    g, da = eng.delta[0], torch.empty_like(eng.delta[0])
+    return {"lla_bn_relu_dropout_fwd": lambda: eng.bn_fwd(1, n, st), "lla_bn_bwd": lambda: eng.bn_bwd(1, g, da, n, st)}
+
+
+def resident_dataset(args, g, dev):
+    """-> (a resident ``CompressedLatents`` of ``--records`` records, their labels in 10 classes)."""
+    comp, _ = hubconf.clip_compressor_b005(device="cuda", clip_weights="synthetic")
+    N = args.records
+    z = (torch.randn(N, comp.z_dim, generator=g) * 0.5).to(dev)
+    payload, offsets, _ = comp.entropy_bottleneck.encode_device(z, comp._tables(), record_prefix=True)
+    total = int(offsets[-1])
+    with tempfile.TemporaryDirectory() as d:
+        f = os.path.join(d, "Z.bin")
+        with open(f, "wb") as fh:
+            fh.write(N.to_bytes(4, "big"))
+            fh.write(payload[:total].cpu().numpy().tobytes())
+        ds = comp.open_dataset(f)
+    return ds, torch.arange(N) % 10
+
+
+def time_fits(Probe, ds, labels, args, say, dev):
+    """One warm-up ``Probe(epochs=1).fit`` and ``--reps`` timed ones per batch size, a host clock around each."""
+    for B in (128, 1024):
+        runs = []
+        for r in range(args.reps + 1):
+            torch.cuda.synchronize(dev)
+            t0 = time.perf_counter()
+            probe = Probe(epochs=1, batch_size=B).fit(ds, labels)
+            torch.cuda.synchronize(dev)
+            runs.append(time.perf_counter() - t0)
+        runs = runs[1:]
+        say(f"    batch {B:5d} ({probe.n_steps_} steps)   " + "  ".join(f"{t:8.3f}" for t in runs) +
+            f"   median {med(runs):8.3f} s   {1e3 * med(runs) / probe.n_steps_:.4f} ms / step   loss {probe.loss_curve_[-1]:.4f}")
 
 
 def bn_main(args, say, dev):
@@ -140,9 +162,9 @@ def bn_main(args, say, dev):
             Ws, bs = _mlp_init([IN] + [HID] * LAYERS + [K], g)
             x = torch.randn(B, IN, generator=g).to(dev)
             y = torch.randint(0, K, (B,), generator=g).to(torch.int32).to(dev)
-            plain = _DeviceMLP(Ws, bs, _Adam(1e-3, 1e-5, (0.9, 0.999), 1e-8), dev, B, K, max_steps=1)
-            eng = _DeviceBNMLP(Ws, bs[-1], _Adam(3e-4, 1e-5, (0.9, 0.999), 1e-8), dev, B, K, 1, DROPOUT, 12345, 0.1, 1e-5)
-            arms = {C: lambda: eng.step(x, y, 0), D: bn_eager_arm(Ws, bs[-1], x, y, dev), A: lambda: plain.step(x, y, 0)}
+            plain = _DeviceMLP(Ws, bs, _Adam(1e-3, 1e-5, (0.9, 0.999), 1e-8), dev, B, K, 1)
+            eng = _DeviceMLP(Ws, bs, _Adam(3e-4, 1e-5, (0.9, 0.999), 1e-8), dev, B, K, 1, (DROPOUT, 12345, 0.1, 1e-5))
+            arms = {C: one_step(eng, x, y), D: bn_eager_arm(Ws, bs[-1], x, y, dev), A: one_step(plain, x, y)}
             times = interleaved(arms, args.inner, args.reps, dev)
             say()
             say(f"classes {K}, batch {B}: ms per training step, device events over {args.inner} back-to-back steps, "
@@ -163,34 +185,12 @@ def bn_main(args, say, dev):
                     f"{rate / 1e12:.3f} TB/s   {rate / wgs / 1e9:.1f} GB/s per workgroup of {wgs}")
             say(f"    2 x (forward + backward) = {2 * total:.4f} ms = {100 * 2 * total / c:.1f} % of (c)")
             del eng, plain, arms
-    comp, _ = hubconf.clip_compressor_b005(device="cuda", clip_weights="synthetic")
-    N, Cz = args.records, comp.z_dim
-    z = (torch.randn(N, Cz, generator=g) * 0.5).to(dev)
-    payload, offsets, _ = comp.entropy_bottleneck.encode_device(z, comp._tables(), record_prefix=True)
-    total = int(offsets[-1])
-    with tempfile.TemporaryDirectory() as d:
-        f = os.path.join(d, "Z.bin")
-        with open(f, "wb") as fh:
-            fh.write(N.to_bytes(4, "big"))
-            fh.write(payload[:total].cpu().numpy().tobytes())
-        ds = comp.open_dataset(f)
-    del z, payload
-    labels = torch.arange(N) % 10
+    ds, labels = resident_dataset(args, g, dev)
     say()
     say(f"one epoch of BatchNormMLPProbe.fit from a resident CompressedLatents: N = {len(ds)} records, 10 classes; host clock around "
         f"fit(epochs=1), which ends in a synchronise (initialisation, decode and label gather included); one warm-up fit, then "
         f"{args.reps} runs")
-    for B in (128, 1024):
-        runs = []
-        for r in range(args.reps + 1):
-            torch.cuda.synchronize(dev)
-            t0 = time.perf_counter()
-            probe = BatchNormMLPProbe(epochs=1, batch_size=B).fit(ds, labels)
-            torch.cuda.synchronize(dev)
-            runs.append(time.perf_counter() - t0)
-        runs = runs[1:]
-        say(f"    batch {B:5d} ({probe.n_steps_} steps)   " + "  ".join(f"{t:8.3f}" for t in runs) +
-            f"   median {med(runs):8.3f} s   {1e3 * med(runs) / probe.n_steps_:.4f} ms / step   loss {probe.loss_curve_[-1]:.4f}")
+    time_fits(BatchNormMLPProbe, ds, labels, args, say, dev)
 
 
 def main():
@@ -223,8 +223,8 @@ def main():
             Ws, bs = _mlp_init([IN] + [HID] * LAYERS + [K], g)
             x = torch.randn(B, IN, generator=g).to(dev)
             y = torch.randint(0, K, (B,), generator=g).to(torch.int32).to(dev)
-            eng = _DeviceMLP(Ws, bs, _Adam(1e-3, 1e-5, (0.9, 0.999), 1e-8), dev, B, K, max_steps=1)
-            arms = {"(a) MLPProbe device step": lambda: eng.step(x, y, 0), "(b) torch eager fp32 step": eager_arm(Ws, bs, x, y, dev)}
+            eng = _DeviceMLP(Ws, bs, _Adam(1e-3, 1e-5, (0.9, 0.999), 1e-8), dev, B, K, 1)
+            arms = {"(a) MLPProbe device step": one_step(eng, x, y), "(b) torch eager fp32 step": eager_arm(Ws, bs, x, y, dev)}
             times = interleaved(arms, args.inner, args.reps, dev)
             say()
             say(f"classes {K}, batch {B}: ms per training step, device events over {args.inner} back-to-back steps, "
@@ -242,34 +242,12 @@ def main():
             del eng, arms
 
     # the whole epoch from a resident container, decode included
-    comp, _ = hubconf.clip_compressor_b005(device="cuda", clip_weights="synthetic")
-    N, C = args.records, comp.z_dim
-    z = (torch.randn(N, C, generator=g) * 0.5).to(dev)
-    payload, offsets, _ = comp.entropy_bottleneck.encode_device(z, comp._tables(), record_prefix=True)
-    total = int(offsets[-1])
-    with tempfile.TemporaryDirectory() as d:
-        f = os.path.join(d, "Z.bin")
-        with open(f, "wb") as fh:
-            fh.write(N.to_bytes(4, "big"))
-            fh.write(payload[:total].cpu().numpy().tobytes())
-        ds = comp.open_dataset(f)
-    del z, payload
-    labels = torch.arange(N) % 10
+    ds, labels = resident_dataset(args, g, dev)
     say()
     say(f"one epoch of MLPProbe.fit from a resident CompressedLatents: N = {len(ds)} records, {ds.nbytes / 2**20:.1f} MiB "
         f"compressed, 10 classes; host clock around fit(epochs=1), which ends in a synchronise (initialisation, the decode "
         f"of 2 groups of 65536 records and the label gather included); one warm-up fit, then {args.reps} runs")
-    for B in (128, 1024):
-        runs = []
-        for r in range(args.reps + 1):
-            torch.cuda.synchronize(dev)
-            t0 = time.perf_counter()
-            probe = MLPProbe(epochs=1, batch_size=B).fit(ds, labels)
-            torch.cuda.synchronize(dev)
-            runs.append(time.perf_counter() - t0)
-        runs = runs[1:]
-        say(f"    batch {B:5d} ({probe.n_steps_} steps)   " + "  ".join(f"{t:8.3f}" for t in runs) +
-            f"   median {med(runs):8.3f} s   {1e3 * med(runs) / probe.n_steps_:.4f} ms / step   loss {probe.loss_curve_[-1]:.4f}")
+    time_fits(MLPProbe, ds, labels, args, say, dev)
     if args.out:
         with open(args.out, "w") as fh:
             fh.write("\n".join(lines) + "\n")
