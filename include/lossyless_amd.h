@@ -619,6 +619,41 @@ int lla_softmax_grid_pass(const void *z, int z_dtype, int ld_z, const int32_t *y
                           const int32_t *group_held, const float *group_class_weight, float *out_W, float *out_b,
                           double *out_loss, int accumulate, void *workspace, void *stream);
 
+/* One data pass of a weighted k-nearest-neighbour classifier (lossyless_amd/csrc/knn.hip) -- the training-free protocol
+ * for judging frozen features (Wu et al. 2018, "Unsupervised Feature Learning via Non-Parametric Instance Discrimination",
+ * sec. 3.4; DINO, Caron et al. 2021, sec. 4.1: cosine similarity, the k best neighbours, each voting exp(s / T)); the
+ * reference has no k-NN.  Every query of the resident block q [Q][C] (fp32, pitch ld_q) keeps a running list of its k best
+ * (score, global index) pairs over the train rows seen so far; this call shows it the n rows z [n][C] (pitch ld_z;
+ * LLA_Z_F32, or LLA_Z_F16 widened exactly) whose global indexes are row_base .. row_base + n - 1.
+ *   metric 0: s_ij = q_i . z_j     metric 1: s_ij = (q_i . z_j) * (1 / sqrt(sum_c z_jc^2))   (0 for a row of zeros)
+ * -- exact fp32 products, fp32 accumulation (v_mfma_f32_32x32x2_f32), the reciprocal norm in fp32 in an order fixed by C;
+ * the caller normalises the queries.  q_self [Q] (NULL: none) names per query one global index that is never listed
+ * (leave-one-out).  accumulate = 0 starts from empty lists, 1 continues what earlier calls with the same (Q, k) and
+ * workspace left.  Scores never reach memory: the lists live in `workspace` (lla_knn_pass_workspace_bytes(Q, k) bytes, 0
+ * for a refused shape; O(Q k walkers), nothing proportional to Q n), one per walker of the split train range.
+ * Order: (score descending, global index ascending), a total order, and a score's bits depend on (q_i, z_j, C, metric)
+ * alone, so the lists lla_knn_finish returns are a pure function of the rows shown: the same bits for any split into calls.
+ * C % 8 == 0, 8 <= C <= 1024, 1 <= k <= 256, Q >= 1, metric 0 / 1, ld_q, ld_z >= C and multiples of 4, q and z 16-byte
+ * (fp16: 8-byte) aligned, row_base >= 0 and row_base + n <= INT32_MAX: anything else is LLA_EINVAL before any device call.
+ * n == 0: LLA_OK without a launch, nothing is touched (the first call of a search shows at least one row).  The last
+ * 8 bytes of the workspace count the insertions of all calls since the caller zeroed them (a diagnostic: tools/knn_bench.py). */
+size_t lla_knn_pass_workspace_bytes(int Q, int k);
+int lla_knn_pass(const float *q, int ld_q, int Q, const void *z, int z_dtype, int ld_z, int n, int C, int row_base, int k,
+                 int metric, const int32_t *q_self, int accumulate, void *workspace, void *stream);
+
+/* Merges the walkers' lists of lla_knn_pass (same Q, k, workspace) in walker order under the same total order and writes
+ * the first k_out <= k entries of every list -- the lists are sorted, so they are the query's top k_out: one search serves
+ * every smaller k -- to top_val [Q][k_out] fp32 and top_idx [Q][k_out] int32, best first; slots beyond the rows seen hold
+ * (-inf, -1); r below runs over the k_out entries.  With labels [N]
+ * (class indexes in [0, K); any other label does not vote), it also writes
+ *   votes[i][c] = sum_r exp((s_ir - s_i0) * inv_T) [labels[idx_ir] == c]      (votes [Q][K] fp32)
+ * the weights of Wu et al. / DINO scaled by exp(-s_i0 / T) so that nothing overflows (inv_T = 0: every neighbour votes 1);
+ * the sum runs serially in rank order, one thread per (query, class): no floating-point atomics.  labels == NULL: votes is
+ * not touched (K is ignored).  The workspace is only read, so the call may be repeated with another k_out or inv_T.
+ * 1 <= k_out <= k <= 256, Q >= 1, K >= 1 with labels; anything else is LLA_EINVAL before any launch. */
+int lla_knn_finish(int Q, int k, int k_out, const int32_t *labels, int K, float inv_T, float *top_val, int32_t *top_idx,
+                   float *votes, const void *workspace, void *stream);
+
 /* ---- A training step of the reference's MLP predictor (csrc/mlp.hip): what lla_gemm_f32, the forward half of an fp32
  * Linear layer, lacks.  Everything is fp32, row-major, pitches in elements; v_mfma_f32_32x32x2_f32 (exact fp32 products,
  * fp32 accumulation), no floating-point atomics, the order of every sum fixed by the shape alone (the same inputs give the

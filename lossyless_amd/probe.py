@@ -1916,3 +1916,251 @@ class BatchNormMLPProbe(_MinibatchProbe):
         out[f"module.{4 * n}.weight"] = f32(self.coefs_[n])
         out[f"module.{4 * n}.bias"] = f32(self.intercepts_[0])
         return out
+
+
+# ---------------------------------------------------------------------------------------------------------------- k-NN
+def _knn_merge(val, idx, s, g0, k):
+    """The float64 twin's list update: the running lists (val, idx) [Q, <= k] and the scores s [Q, g] of rows g0 .. g0 + g - 1
+    -> the k best of both by (score descending, index ascending).  A stable descending sort keeps equal scores in the order
+    they come in, and they come in index order: a group's columns ascend, and every index of the running list (itself in
+    that order among equals) lies below g0."""
+    sv, si = torch.sort(s, dim=1, descending=True, stable=True)
+    val = torch.cat([val, sv[:, :k]], 1)
+    idx = torch.cat([idx, si[:, :k] + g0], 1)
+    val, order = torch.sort(val, dim=1, descending=True, stable=True)
+    return val[:, :k].contiguous(), torch.gather(idx, 1, order)[:, :k].contiguous()
+
+
+def _knn_votes64(val, idx, y, K, inv_T):
+    """votes[i, c] = sum_r exp((s_ir - s_i0) inv_T) [y[idx_ir] == c] in float64, added serially in rank order."""
+    Q, k = val.shape
+    votes = torch.zeros((Q, K), dtype=torch.float64, device=val.device)
+    w = torch.exp((val - val[:, :1]) * inv_T)
+    rows = torch.arange(Q, device=val.device)
+    for r in range(k):
+        seen = idx[:, r] >= 0
+        votes[rows[seen], y[idx[seen, r]]] += w[seen, r]
+    return votes
+
+
+class KNNProbe:
+    """``KNNProbe(k=20, T=0.07, metric="cosine", weights="softmax")``: the weighted k-nearest-neighbour classifier of Wu et
+    al. 2018 and DINO -- the training-free protocol for judging frozen features -- and the way to get *neighbours* out of a
+    container.  A query's k best fitted rows by cosine similarity (``metric="dot"``: by inner product) vote for their class
+    with weight ``exp(s / T)`` (``weights="uniform"``: 1); the class with the most votes wins, a tie going to the lower
+    class index.  Nothing proportional to queries x rows is ever held: a block of queries stays resident, the fitted rows
+    are walked once per block, one decode group at a time, through ``lla_knn_pass`` (csrc/knn.hip), whose scores never leave
+    the chip, and ``lla_knn_finish`` writes the lists and the votes.
+
+    ``fit(data, labels=None)``
+        data    a ``CompressedLatents`` / ``HyperpriorLatents`` (it stays compressed: only its labels are taken), or an
+                ``[N, C]`` tensor / array.  Without labels only ``kneighbors`` works.
+    ``kneighbors(queries=None, k=None, rows_per_pass=65536, queries_per_pass=8192, exclude_self=False)``
+        -> (similarity ``[Q, k]``, index ``[Q, k]`` int64 into the fitted rows), best first, ordered by (similarity
+        descending, index ascending): duplicates of a row come out lowest index first.  fp32 from the device, float64 from
+        the CPU twin.  ``exclude_self=True`` (the queries must be the fitted data: the same object, or ``None``) skips every
+        query's own row -- the leave-one-out search that ``k`` and ``T`` are chosen by.
+    ``predict_proba`` (votes / their sum), ``predict``, ``score(queries, labels=None, ...)`` take the same arguments;
+    ``score_grid(queries, ks, Ts, labels=None, ...)`` -> ``{(k, T): accuracy}`` from ONE search at ``max(ks)``: the lists
+    are sorted, so a query's top k' is the head of its top k.
+
+    The lists are a pure function of the data: the same bits for any ``rows_per_pass`` and ``queries_per_pass``.  The device
+    needs ``C % 8 == 0``, ``C <= 1024`` and ``k <= 256``.  CPU data (``device="cpu"`` latents, CPU tensors) run a float64
+    torch twin with the same contract, a block of ``queries_per_pass x rows_per_pass`` scores at a time."""
+
+    def __init__(self, k=20, T=0.07, metric="cosine", weights="softmax"):
+        if int(k) < 1 or not T > 0:
+            raise ValueError("k must be at least 1 and T positive")
+        if metric not in ("cosine", "dot") or weights not in ("softmax", "uniform"):
+            raise ValueError(f"metric must be 'cosine' or 'dot' and weights 'softmax' or 'uniform', got {metric!r}, {weights!r}")
+        self.k, self.T, self.metric, self.weights = int(k), float(T), metric, weights
+        self.classes_ = None
+        self._data = None
+
+    # ------------------------------------------------------------------ fit
+    def fit(self, data, labels=None):
+        rows = _Rows(data, 1, False)
+        if rows.n < 1:
+            raise ValueError("no rows to fit")
+        self._data, self._n, self._dim, self._device = data, rows.n, rows.dim, rows.device
+        if labels is None and not (_is_latents(data) and data._labels is not None):
+            self._y = self._labels = self.classes_ = None
+        else:
+            self._labels = _labels_of(data, labels, rows.n)
+            classes = torch.unique(self._labels)
+            self._y = torch.searchsorted(classes, self._labels)
+            self.classes_ = classes.numpy()
+        self._y_dev = None
+        return self
+
+    # ------------------------------------------------------------------ the search
+    def _inv_T(self, T):
+        return 0.0 if self.weights == "uniform" else 1.0 / float(T)
+
+    def _search(self, queries, k, rows_per_pass, queries_per_pass, exclude_self, lists, grid):
+        """One neighbour search at ``k`` -> (similarity, index) if ``lists``, and the votes [Q, K] of every (k', inv_T) of
+        ``grid``."""
+        if self._data is None:
+            raise RuntimeError("fit first")
+        if queries is None:
+            queries = self._data
+        if exclude_self and queries is not self._data:
+            raise ValueError("exclude_self needs the queries to be the fitted data (the same object, or queries=None)")
+        k, dev = int(k), self._device
+        on_device = dev.type == "cuda"
+        usable = self._n - (1 if exclude_self else 0)
+        if k < 1 or k > usable:
+            raise ValueError(f"k = {k} for {usable} usable fitted rows")
+        if grid and self._y is None:
+            raise ValueError("no labels: fit with labels=, or with latents opened with a label_file")
+        if any(kk < 1 or kk > k for kk, _ in grid):
+            raise ValueError("every k of the grid must lie in [1, max(ks)]")
+        qrows = _Rows(queries, queries_per_pass, False)
+        qrows.first_pass = _is_latents(queries)
+        train = _Rows(self._data, rows_per_pass, False)
+        train.first_pass = _is_latents(self._data)
+        if qrows.dim != self._dim:
+            raise ValueError(f"the queries have {qrows.dim} features, the probe was fitted on {self._dim}")
+        C, K = self._dim, 0 if self._y is None else len(self.classes_)
+        if on_device:
+            if C % 8 or not 8 <= C <= 1024:
+                raise ValueError(f"the device k-NN needs a feature width that is a multiple of 8 in [8, 1024], got {C}")
+            if k > 256:
+                raise ValueError(f"the device k-NN keeps lists of at most 256 neighbours, got k = {k}")
+            if grid and (self._y_dev is None or self._y_dev.device != dev):
+                self._y_dev = self._y.to(torch.int32).to(dev)
+        dt = torch.float32 if on_device else torch.float64
+        sims, idxs, votes = [], [], [[] for _ in grid]
+        cosine = self.metric == "cosine"
+        try:
+            for b0, qz in qrows.groups():
+                B = int(qz.shape[0])
+                qn = qz.to(dev).to(torch.float64)
+                if cosine:                       # (a row of zeros stays zero: its similarities are 0)
+                    norm = qn.norm(dim=1, keepdim=True)
+                    qn = qn / torch.where(norm > 0, norm, torch.ones_like(norm))
+                own = torch.arange(b0, b0 + B, device=dev) if exclude_self else None
+                if on_device:
+                    val, idx, vs = self._device_block(qn.to(torch.float32).contiguous(), train, k, own, lists, grid, K)
+                else:
+                    val, idx, vs = self._host_block(qn, train, k, own, grid, K)
+                if lists:
+                    sims.append(val), idxs.append(idx)
+                for slot, v in zip(votes, vs):
+                    slot.append(v)
+        finally:
+            qrows.close()
+            train.close()
+        cat = lambda parts, width, dtype: (torch.cat(parts) if parts else                       # noqa: E731
+                                           torch.zeros((0, width), dtype=dtype, device=dev))
+        out_lists = (cat(sims, k, dt), cat(idxs, k, torch.int64)) if lists else None
+        return out_lists, [cat(v, K, dt) for v in votes]
+
+    def _device_block(self, qn, train, k, own, lists, grid, K):
+        L, dev = _lib.lib(), qn.device
+        B, C = int(qn.shape[0]), int(qn.shape[1])
+        nbytes = int(L.lla_knn_pass_workspace_bytes(B, k))
+        if nbytes == 0:
+            raise ValueError(f"lla_knn_pass refuses Q = {B}, k = {k}")
+        ws = torch.empty(nbytes, dtype=torch.uint8, device=dev)
+        own32 = None if own is None else own.to(torch.int32)
+        metric = 1 if self.metric == "cosine" else 0
+        with torch.cuda.device(dev):
+            st = _lib.stream_ptr(dev)
+            accumulate = 0
+            for g0, z in train.groups():
+                g = int(z.shape[0])
+                zt = _lib.LLA_Z_F16 if z.dtype == torch.float16 else _lib.LLA_Z_F32
+                rc = L.lla_knn_pass(_lib.ptr(qn), C, B, _lib.ptr(z), zt, int(z.stride(0)) if g > 1 else C, g, C, g0, k, metric,
+                                    _lib.ptr(own32), accumulate, _lib.ptr(ws), st)
+                _lib.check(rc, "lla_knn_pass")
+                accumulate = 1
+            val = idx = None
+            vs = []
+            for kk, inv_T in grid or [(k, 0.0)]:
+                tv = torch.empty((B, kk), dtype=torch.float32, device=dev)
+                ti = torch.empty((B, kk), dtype=torch.int32, device=dev)
+                v = torch.empty((B, K), dtype=torch.float32, device=dev) if grid else None
+                rc = L.lla_knn_finish(B, k, kk, _lib.ptr(self._y_dev if grid else None), K, inv_T, _lib.ptr(tv), _lib.ptr(ti),
+                                      _lib.ptr(v), _lib.ptr(ws), st)
+                _lib.check(rc, "lla_knn_finish")
+                if grid:
+                    vs.append(v)
+                if kk == k:
+                    val, idx = tv, ti
+            if lists and val is None:            # (no entry of the grid asked for all k)
+                val = torch.empty((B, k), dtype=torch.float32, device=dev)
+                idx = torch.empty((B, k), dtype=torch.int32, device=dev)
+                _lib.check(L.lla_knn_finish(B, k, k, None, 0, 0.0, _lib.ptr(val), _lib.ptr(idx), None, _lib.ptr(ws), st),
+                           "lla_knn_finish")
+        return val, (idx.to(torch.int64) if lists else None), vs
+
+    def _host_block(self, qn, train, k, own, grid, K):
+        B = int(qn.shape[0])
+        val = torch.zeros((B, 0), dtype=torch.float64)
+        idx = torch.zeros((B, 0), dtype=torch.int64)
+        for g0, z in train.groups():
+            z = z.to(torch.float64)
+            s = qn @ z.T
+            if self.metric == "cosine":
+                ss = (z * z).sum(1)
+                s = s * torch.where(ss > 0, 1.0 / torch.sqrt(ss), torch.zeros_like(ss))[None, :]
+            if own is not None:                  # (k <= N - 1 finite scores: a skipped row never stays listed)
+                mine = (own >= g0) & (own < g0 + z.shape[0])
+                s[torch.nonzero(mine)[:, 0], own[mine] - g0] = -float("inf")
+            val, idx = _knn_merge(val, idx, s, g0, k)
+        y = self._y
+        return val, idx, [_knn_votes64(val[:, :kk], idx[:, :kk], y, K, inv_T) for kk, inv_T in grid]
+
+    # ------------------------------------------------------------------ the public calls
+    def kneighbors(self, queries=None, k=None, rows_per_pass=65536, queries_per_pass=8192, exclude_self=False):
+        k = self.k if k is None else k
+        return self._search(queries, k, rows_per_pass, queries_per_pass, exclude_self, True, [])[0]
+
+    def _votes(self, queries, k, T, rows_per_pass, queries_per_pass, exclude_self):
+        k = self.k if k is None else int(k)
+        T = self.T if T is None else T
+        return self._search(queries, k, rows_per_pass, queries_per_pass, exclude_self, False, [(k, self._inv_T(T))])[1][0]
+
+    @staticmethod
+    def _winners(votes):
+        """argmax over the classes; a tie goes to the lower class index."""
+        K = votes.shape[1]
+        at = torch.arange(K, device=votes.device)[None, :].expand_as(votes)
+        return torch.where(votes == votes.amax(1, keepdim=True), at, torch.full_like(at, K)).amin(1)
+
+    def predict_proba(self, queries=None, k=None, T=None, rows_per_pass=65536, queries_per_pass=8192, exclude_self=False):
+        votes = self._votes(queries, k, T, rows_per_pass, queries_per_pass, exclude_self)
+        return votes / votes.sum(1, keepdim=True)
+
+    def predict(self, queries=None, k=None, T=None, rows_per_pass=65536, queries_per_pass=8192, exclude_self=False):
+        votes = self._votes(queries, k, T, rows_per_pass, queries_per_pass, exclude_self)
+        return torch.from_numpy(self.classes_).to(votes.device)[self._winners(votes)]
+
+    def _truth(self, queries, labels, n):
+        if queries is None or (queries is self._data and labels is None):
+            if labels is None:
+                return self._labels
+            queries = self._data
+        return _labels_of(queries, labels, n)
+
+    def score(self, queries=None, labels=None, k=None, T=None, rows_per_pass=65536, queries_per_pass=8192,
+              exclude_self=False):
+        pred = self.predict(queries, k, T, rows_per_pass, queries_per_pass, exclude_self)
+        y = self._truth(queries, labels, pred.numel()).to(pred.device)
+        return float((pred == y).double().mean())
+
+    def score_grid(self, queries, ks, Ts, labels=None, exclude_self=False, rows_per_pass=65536, queries_per_pass=8192):
+        ks, Ts = [int(k) for k in ks], [float(T) for T in Ts]
+        if not ks or not Ts:
+            raise ValueError("ks and Ts must not be empty")
+        grid = [(k, T) for k in ks for T in Ts]
+        votes = self._search(queries, max(ks), rows_per_pass, queries_per_pass, exclude_self, False,
+                             [(k, self._inv_T(T)) for k, T in grid])[1]
+        classes = torch.from_numpy(self.classes_)
+        out = {}
+        for key, v in zip(grid, votes):
+            pred = classes.to(v.device)[self._winners(v)]
+            y = self._truth(queries, labels, pred.numel()).to(pred.device)
+            out[key] = float((pred == y).double().mean())
+        return out

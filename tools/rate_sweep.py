@@ -84,6 +84,10 @@ def main():
                     help="also train lossyless_amd.BatchNormMLPProbe (the reference's predictor as config/main.yaml wires it: "
                          "mlp_probe.yaml's batchnorm and dropout 0.2, AdamW lr 3e-4 wd 1e-5, unifmultistep100) the same way (adds "
                          "mlp_config_probe_accuracy and mlp_config_probe_fit_s)")
+    ap.add_argument("--device-knn", action="store_true",
+                    help="also run the training-free protocol, lossyless_amd.KNNProbe (weighted k-NN: cosine, k = 20, T = 0.07), "
+                         "on the device from the container kept compressed (adds knn_probe_accuracy, the leave-one-out "
+                         "knn_probe_train_accuracy and knn_probe_s)")
     args = ap.parse_args()
 
     weights = os.environ.get("LOSSYLESS_CLIP_WEIGHTS", "synthetic")
@@ -184,6 +188,15 @@ def main():
                     torch.cuda.synchronize()
                     probe.update(mlp_config_probe_fit_s=round(time.perf_counter() - t0, 3),
                                  mlp_config_probe_accuracy=float(bn_mlp.score(comp.open_dataset(ft), np.asarray(Yt))))
+                if args.device_knn:
+                    from lossyless_amd import KNNProbe
+                    t0 = time.perf_counter()
+                    knn = KNNProbe(k=min(20, len(Y) - 1)).fit(comp.open_dataset(f), np.asarray(Y))
+                    knn_accuracy = float(knn.score(comp.open_dataset(ft), np.asarray(Yt)))
+                    knn_train = float(knn.score(None, exclude_self=True))
+                    torch.cuda.synchronize()
+                    probe.update(knn_probe_s=round(time.perf_counter() - t0, 3), knn_probe_accuracy=knn_accuracy,
+                                 knn_probe_train_accuracy=knn_train)
         print(json.dumps(dict(rate_point=name, data=data, clip_weights=weights, images=n,
                               call=("Dataset(transform=RawRGB) -> compress_dataset(dataset, file, label_file, "
                                     f"dict(batch_size={args.batch}, num_workers={args.workers}))") if shaped
