@@ -654,6 +654,37 @@ int lla_knn_pass(const float *q, int ld_q, int Q, const void *z, int z_dtype, in
 int lla_knn_finish(int Q, int k, int k_out, const int32_t *labels, int K, float inv_T, float *top_val, int32_t *top_idx,
                    float *votes, const void *workspace, void *stream);
 
+/* One Lloyd iteration of k-means (lossyless_amd/csrc/kmeans.hip) -- the unsupervised protocol for judging frozen features:
+ * cluster, then score the clusters against the labels (DeepCluster, Caron et al. 2018; SCAN, Van Gansbeke et al. 2020); the
+ * reference has no clustering.  lla_svm_pass's walk with an argmax over the centroids in the place of the hinge residual.
+ *   z [B][C] (pitch ld_z; LLA_Z_F32, or LLA_Z_F16 widened exactly); W [K][C] (pitch ld_w), b [K]: the centroids' affine scores.
+ *   n2_i = sum_c z_ic^2, in fp32 in an order fixed by C.
+ *   metric 0 (Euclidean):  s_ik = z_i . W_k + b_k           w_i = 1     dist_i = max(0, n2_i - 2 s_i,a_i)
+ *                          -- with W = the centres and b_k = -1/2 |c_k|^2, the squared distance to the nearest centre
+ *   metric 1 (spherical):  s_ik = (z_i . W_k) r_i + b_k     w_i = r_i   dist_i = 1 - s_i,a_i
+ *                          r_i = 1 / sqrt(n2_i), 0 for a row of zeros
+ *   a_i = argmax_k s_ik, the lowest k on ties;  out_assign [B] int32, out_dist [B] fp32: per row, always written.
+ *   out_sum[k] = sum_{i: a_i = k} w_i z_i  ([K][C], pitch ld_w),  out_count[k] = the number of such rows (an exact integer
+ *   in double),  out_stats[0] = sum_i dist_i,  out_stats[1] = sum_i n2_i  (double [2]).
+ * accumulate = 1 adds this call's totals to out_sum, out_count and out_stats (a dataset walked in decode groups).
+ * out_sum == NULL (predict only): only out_assign and out_dist are written; out_count and out_stats are not touched and
+ * may be NULL.
+ * A score's bits depend on (z_i, W_k, b_k, C, metric) alone -- exact fp32 products, fp32 accumulation
+ * (v_mfma_f32_32x32x2_f32) in an order fixed by C, one rounding for the scale and one for the add of b -- not on the row's
+ * place in a tile, a call or a walker's range, nor on the path: K <= 32 is one kernel (z is read once); K > 32 runs an assign
+ * kernel over all centroid tiles, then the sums walk once per centroid tile (the cost of an lla_svm_pass at that K).  The
+ * assignment is therefore a pure function of the rows and the centroids.  No floating-point atomics: workgroups leave partial
+ * sums in `workspace` (lla_kmeans_pass_workspace_bytes(C, K) bytes; 0 for a refused shape) and a last kernel adds them in
+ * workgroup order, counts and statistics in double; the grid depends on (B, K) alone: the same inputs give the same bits.
+ * C % 8 == 0, 8 <= C <= 1024, K >= 1, ld_z >= C, ld_w >= C, pitches multiples of 4, metric 0 / 1, z 16-byte (fp16: 8-byte)
+ * and W, out_sum, workspace 16-byte aligned; W, b, out_assign, out_dist, workspace not NULL (with out_sum: out_count and
+ * out_stats too); anything else is LLA_EINVAL, decided before any device call.  B == 0: LLA_OK, no pass is launched (the
+ * accumulated outputs are zeroed unless accumulate is set or out_sum is NULL, then nothing is touched). */
+size_t lla_kmeans_pass_workspace_bytes(int C, int K);
+int lla_kmeans_pass(const void *z, int z_dtype, int ld_z, int B, int C, const float *W, const float *b, int K, int ld_w,
+                    int metric, int32_t *out_assign, float *out_dist, float *out_sum, double *out_count, double *out_stats,
+                    int accumulate, void *workspace, void *stream);
+
 /* ---- A training step of the reference's MLP predictor (csrc/mlp.hip): what lla_gemm_f32, the forward half of an fp32
  * Linear layer, lacks.  Everything is fp32, row-major, pitches in elements; v_mfma_f32_32x32x2_f32 (exact fp32 products,
  * fp32 accumulation), no floating-point atomics, the order of every sum fixed by the shape alone (the same inputs give the

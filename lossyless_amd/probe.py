@@ -25,6 +25,9 @@ of a search over ``C`` and ``class_weight`` side by side and solves them in the 
 
 :class:`LogisticProbe` is the softmax-regression sibling: one problem that couples all classes (``lla_softmax_pass``, a
 joint Newton-CG), over the same walk of the rows and the same scoring path.
+
+:class:`KMeansProbe` is the unsupervised sibling: Lloyd's k-means over the same walk (``lla_kmeans_pass``, csrc/kmeans.hip:
+the argmax over the centres in the place of a residual), with the clusters scored against labels afterwards.
 """
 import warnings
 
@@ -2164,3 +2167,418 @@ class KNNProbe:
             y = self._truth(queries, labels, pred.numel()).to(pred.device)
             out[key] = float((pred == y).double().mean())
         return out
+
+
+# ------------------------------------------------------------------------------------------------------------- k-means
+def _first_argmax(s):
+    """argmax over the columns; a tie goes to the lowest index (``torch.argmax`` promises no order among equals)."""
+    K = s.shape[1]
+    at = torch.arange(K, device=s.device)[None, :].expand_as(s)
+    return torch.where(s == s.amax(1, keepdim=True), at, torch.full_like(at, K)).amin(1)
+
+
+def _unit_rows(z, fallback=None):
+    """Rows over their 2-norm; a row of zeros stays (or becomes the same row of ``fallback``)."""
+    norm = z.norm(dim=1, keepdim=True)
+    unit = z / torch.where(norm > 0, norm, torch.ones_like(norm))
+    return unit if fallback is None else torch.where(norm > 0, unit, fallback)
+
+
+def _take_rows(rows, idx):
+    """Rows ``idx`` of what a :class:`_Rows` walks, through the container's random access -> float64 on its device."""
+    idx = torch.as_tensor(idx, dtype=torch.int64).to(rows.device)
+    z = rows.latents.take(idx) if rows.latents is not None else rows.rows[idx]
+    if not bool(torch.isfinite(z).all()):
+        raise ValueError("non-finite values in the rows drawn")
+    return z.to(torch.float64)
+
+
+class _TwinKMeans:
+    """One Lloyd walk in float64 torch -- the CPU path of :class:`KMeansProbe` and the oracle of the GPU tests: the
+    quantities of ``lla_kmeans_pass`` from the same affine scores, ``_HOST_BLOCK`` rows at a time."""
+
+    def __init__(self, rows, K, cosine):
+        self.rows, self.K, self.cosine, self.n_passes = rows, int(K), bool(cosine), 0
+
+    @staticmethod
+    def round(centres):
+        return centres
+
+    def bias(self, centres):
+        return torch.zeros(self.K, dtype=torch.float64) if self.cosine else -0.5 * (centres * centres).sum(1)
+
+    def rows_of(self, z, W, b):
+        """-> (a, dist, w, n2) of the rows z [g, C] float64 against the scores z . W_k + b_k."""
+        n2 = (z * z).sum(1)
+        s = z @ W.T
+        if self.cosine:
+            w = torch.where(n2 > 0, 1.0 / torch.sqrt(n2), torch.zeros_like(n2))
+            s = s * w[:, None] + b
+        else:
+            w = torch.ones_like(n2)
+            s = s + b
+        a = _first_argmax(s)
+        best = torch.gather(s, 1, a[:, None])[:, 0]
+        return a, (1.0 - best if self.cosine else (n2 - 2.0 * best).clamp_min(0.0)), w, n2
+
+    def walk(self, centres, sums):
+        """-> (a int64 [N], dist [N], sums [K, C], counts [K], stats [2]); without ``sums`` the last three are None."""
+        N, C, K = self.rows.n, self.rows.dim, self.K
+        W, b = centres.to(torch.float64), self.bias(centres.to(torch.float64))
+        a, dist = torch.empty(N, dtype=torch.int64), torch.empty(N, dtype=torch.float64)
+        S, cnt = torch.zeros((K, C), dtype=torch.float64), torch.zeros(K, dtype=torch.float64)
+        stats = torch.zeros(2, dtype=torch.float64)
+        for g0, zg in self.rows.groups():
+            for r0 in range(0, int(zg.shape[0]), _HOST_BLOCK):
+                z = zg[r0:r0 + _HOST_BLOCK].to(torch.float64)
+                at = slice(g0 + r0, g0 + r0 + int(z.shape[0]))
+                a[at], dist[at], w, n2 = self.rows_of(z, W, b)
+                if sums:
+                    S.index_add_(0, a[at], z * w[:, None])
+                    cnt += torch.bincount(a[at], minlength=K).to(torch.float64)
+                    stats += torch.stack([dist[at].sum(), n2.sum()])
+        self.n_passes += 1
+        return (a, dist, S, cnt, stats) if sums else (a, dist, None, None, None)
+
+
+class _DeviceKMeans:
+    """The same walk on the device: every decode group goes through ``lla_kmeans_pass`` (csrc/kmeans.hip), which adds the
+    group's sums, counts and statistics to the running totals; scores never reach memory."""
+
+    def __init__(self, rows, K, cosine):
+        self.rows, self.K, self.cosine, self.n_passes = rows, int(K), bool(cosine), 0
+        L, dev, C, N = _lib.lib(), rows.device, rows.dim, rows.n
+        if C % 8 or not 8 <= C <= 1024:
+            raise ValueError(f"the device k-means needs a feature width that is a multiple of 8 in [8, 1024], got {C}")
+        nbytes = int(L.lla_kmeans_pass_workspace_bytes(C, self.K))
+        if nbytes == 0:
+            raise ValueError(f"lla_kmeans_pass refuses C = {C}, K = {K}")
+        self.ws = torch.empty(nbytes, dtype=torch.uint8, device=dev)
+        self.assign = torch.empty(N, dtype=torch.int32, device=dev)
+        self.dist = torch.empty(N, dtype=torch.float32, device=dev)
+        self.sum = torch.empty((self.K, C), dtype=torch.float32, device=dev)
+        self.count = torch.empty(self.K, dtype=torch.float64, device=dev)
+        self.stats = torch.empty(2, dtype=torch.float64, device=dev)
+
+    @staticmethod
+    def round(centres):
+        return centres.to(torch.float32).to(torch.float64)
+
+    def bias(self, W):
+        """b of the fp32 centres W: -1/2 |c_k|^2 in float64, rounded once (cosine: 0)."""
+        if self.cosine:
+            return torch.zeros(self.K, dtype=torch.float32, device=W.device)
+        return (-0.5 * (W.to(torch.float64) ** 2).sum(1)).to(torch.float32)
+
+    def run(self, z, W, b, assign, dist, sums, accumulate):
+        """One ``lla_kmeans_pass`` over the rows z [g, C] on the current stream."""
+        g, C, dev = int(z.shape[0]), int(W.shape[1]), W.device
+        zt = _lib.LLA_Z_F16 if z.dtype == torch.float16 else _lib.LLA_Z_F32
+        rc = _lib.lib().lla_kmeans_pass(
+            _lib.ptr(z), zt, int(z.stride(0)) if g > 1 else C, g, C, _lib.ptr(W), _lib.ptr(b), self.K, C,
+            1 if self.cosine else 0, _lib.ptr(assign), _lib.ptr(dist), _lib.ptr(self.sum if sums else None),
+            _lib.ptr(self.count if sums else None), _lib.ptr(self.stats if sums else None), accumulate, _lib.ptr(self.ws),
+            _lib.stream_ptr(dev))
+        _lib.check(rc, "lla_kmeans_pass")
+
+    def walk(self, centres, sums):
+        W = centres.to(torch.float32).contiguous()
+        b = self.bias(W)
+        with torch.cuda.device(W.device):
+            accumulate = 0
+            for g0, z in self.rows.groups():
+                g = int(z.shape[0])
+                self.run(z, W, b, self.assign[g0:g0 + g], self.dist[g0:g0 + g], sums, accumulate)
+                accumulate = 1
+        self.n_passes += 1
+        a, dist = self.assign.to(torch.int64), self.dist.to(torch.float64)
+        return (a, dist, self.sum.to(torch.float64), self.count.clone(), self.stats.clone()) if sums else \
+            (a, dist, None, None, None)
+
+
+def _kmeans_init(rows, K, cosine, init, seed, init_size):
+    """-> the initial centres, float64 [K, C] on the rows' device, drawn through the container's random access."""
+    N = rows.n
+    g = torch.Generator().manual_seed(int(seed))
+    perm = torch.randperm(N, generator=g)
+    if init == "random":
+        return _take_rows(rows, perm[:K])
+    S = min(N, max(4096, 32 * K)) if init_size is None else int(init_size)
+    S = max(min(S, N), K)
+    z = _take_rows(rows, perm[:S])
+    if cosine:
+        z = _unit_rows(z)
+    # k-means++ (Arthur & Vassilvitskii 2007): every next centre is drawn with probability proportional to D^2
+    u = torch.rand(K, generator=g, dtype=torch.float64)
+    n2 = (z * z).sum(1)
+    dist_to = lambda at: (n2 - 2.0 * (z @ z[at]) + n2[at]).clamp_min(0.0)                       # noqa: E731
+    chosen = [torch.tensor(min(int(float(u[0]) * S), S - 1), device=z.device)]
+    d = dist_to(chosen[0])
+    u = u.to(z.device)
+    for j in range(1, K):
+        cum = torch.cumsum(d, 0)
+        chosen.append(torch.searchsorted(cum, (u[j] * cum[-1])[None], right=True)[0].clamp(max=S - 1))
+        d = torch.minimum(d, dist_to(chosen[-1]))
+    return z[torch.stack(chosen)]
+
+
+def _relocate_empty(S, cnt, a, dist, rows, cosine):
+    """Empty clusters, in ascending index, each receive the row with the largest dist not already given away (the lowest
+    index on ties; a row that is its cluster's last is passed over), which leaves its own cluster -- scikit-learn's rule."""
+    empty = torch.nonzero(cnt == 0)[:, 0].tolist()
+    if not empty:
+        return S, cnt
+    K = int(cnt.numel())
+    order = torch.sort(dist, descending=True, stable=True)[1][:len(empty) + K]
+    left = cnt.tolist()
+    moves = []
+    for row, donor in zip(order.tolist(), a[order].tolist()):
+        if len(moves) == len(empty):
+            break
+        if left[donor] > 1:
+            left[donor] -= 1
+            moves.append((row, donor, empty[len(moves)]))
+    if not moves:
+        return S, cnt
+    z = _take_rows(rows, [m[0] for m in moves])
+    if cosine:
+        z = _unit_rows(z)
+    S, cnt = S.clone(), cnt.clone()
+    for j, (_, donor, k) in enumerate(moves):
+        S[donor] -= z[j]
+        cnt[donor] -= 1
+        S[k] = z[j]
+        cnt[k] = 1
+    return S, cnt
+
+
+def _lloyd(engine, rows, centres, cosine, max_iter, tol):
+    """Lloyd's iterations from ``centres`` with scikit-learn's stopping rules -> dict of the fitted state."""
+    N, C = rows.n, rows.dim
+    centres = engine.round(_unit_rows(centres) if cosine else centres)
+    prev, tol_abs, converged, curve, n_iter = None, None, False, [], 0
+    for _ in range(max_iter):
+        a, dist, S, cnt, stats = engine.walk(centres, True)
+        curve.append(float(stats[0]))
+        if tol_abs is None:                      # tol x the mean per-column variance, from the first pass's own totals
+            mean = S.sum(0) / N
+            second = 1.0 if cosine else float(stats[1]) / N
+            tol_abs = tol * max((second - float((mean * mean).sum())) / C, 0.0)
+        S, cnt = _relocate_empty(S, cnt, a, dist, rows, cosine)
+        new = torch.where(cnt[:, None] > 0, S / cnt.clamp_min(1.0)[:, None], centres)
+        new = engine.round(_unit_rows(new, centres) if cosine else new)
+        shift = float(((new - centres) ** 2).sum())
+        centres = new
+        n_iter += 1
+        if prev is not None and torch.equal(a, prev):
+            converged = True
+            break
+        if shift <= tol_abs:
+            converged = True
+            break
+        prev = a
+    a, dist, _, _, _ = engine.walk(centres, False)
+    return dict(centres=centres, labels=a, inertia=float(dist.sum()), n_iter=n_iter, curve=curve, converged=converged)
+
+
+def _contingency(labels, assigned):
+    """-> float64 [classes, clusters] counts of two integer labelings."""
+    y = labels.detach().cpu() if isinstance(labels, torch.Tensor) else torch.from_numpy(np.asarray(labels))
+    c = assigned.detach().cpu() if isinstance(assigned, torch.Tensor) else torch.from_numpy(np.asarray(assigned))
+    y, c = y.reshape(-1), c.reshape(-1)
+    if y.is_floating_point() or c.is_floating_point():
+        raise TypeError("labels must be integers")
+    if y.numel() != c.numel() or y.numel() == 0:
+        raise ValueError(f"{y.numel()} labels for {c.numel()} assignments")
+    yi, ci = torch.unique(y, return_inverse=True)[1], torch.unique(c, return_inverse=True)[1]
+    nb = int(ci.max()) + 1
+    return torch.bincount(yi * nb + ci, minlength=(int(yi.max()) + 1) * nb).reshape(-1, nb).to(torch.float64)
+
+
+class KMeansProbe:
+    """``KMeansProbe(n_clusters, metric="euclidean", init="k-means++", n_init=1, max_iter=100, tol=1e-4, seed=0,
+    init_size=None)``: Lloyd's k-means on the frozen representations -- the unsupervised protocol (cluster, then score the
+    clusters against the labels by NMI / ARI / purity: DeepCluster, SCAN) and the way to build codebooks or pseudo-labels
+    from a container that stays compressed.  ``metric="cosine"`` is spherical k-means: rows and centres on the unit sphere.
+
+    ``fit(data, rows_per_pass=65536, keep_rows=False)``
+        data    a ``CompressedLatents`` / ``HyperpriorLatents``, an ``[N, C]`` device tensor (fp32 or fp16) or CPU data.
+        Every Lloyd iteration is one walk of the rows, one decode group at a time, through ``lla_kmeans_pass``
+        (csrc/kmeans.hip): assignment, per-cluster sums and counts and the inertia in one pass whose scores never leave the
+        chip.  The centres are the sums over the counts in float64, rounded to fp32; an empty cluster receives the row
+        farthest from its centre (scikit-learn's rule, made deterministic: ascending cluster index, lowest row on ties).
+        Stops when no label changed, or when the squared centre shift is at most ``tol`` times the mean per-column variance
+        (scikit-learn's rule), or after ``max_iter`` iterations; one assign-only pass then makes ``labels_`` and ``inertia_``
+        those of ``cluster_centers_``.
+    ``init``    ``"k-means++"`` (D^2 sampling on a seeded subsample of ``init_size`` rows, default ``min(N, max(4096, 32 K))``),
+                ``"random"`` (K distinct rows) or an array ``[K, C]``; the rows are drawn with ``take``.  ``n_init`` restarts
+                run seeds ``seed, seed + 1, ...`` one after another and the lowest inertia is kept.
+
+    After ``fit``: ``cluster_centers_`` ``[K, C]`` (fp32 from the device, float64 from the CPU twin), ``labels_`` int64
+    ``[N]``, ``inertia_`` (sum of squared distances; cosine: of ``1 - cos``), ``n_iter_``, ``inertia_curve_`` (the inertia
+    each iteration's pass saw), ``converged_``, ``n_passes_``.  ``predict(data)`` -> labels; ``transform(data)`` -> distances
+    ``[N, K]`` (Euclidean, or ``1 - cos``) on ``lla_gemm_f32``; ``cluster_scores(labels, assigned=None)`` -> ``{"nmi", "ari",
+    "purity"}`` of ``assigned`` (default ``labels_``) against ``labels``, NMI with the arithmetic mean as ``sklearn.metrics``.
+
+    Deterministic: the same inputs, seed and ``rows_per_pass`` give the same bits, with ``keep_rows`` or without.  CPU data
+    (``device="cpu"`` latents, CPU tensors) run the float64 torch twin of the same algorithm."""
+
+    def __init__(self, n_clusters, metric="euclidean", init="k-means++", n_init=1, max_iter=100, tol=1e-4, seed=0,
+                 init_size=None):
+        if int(n_clusters) < 1 or int(n_init) < 1 or int(max_iter) < 1 or not tol >= 0:
+            raise ValueError("n_clusters, n_init and max_iter must be at least 1 and tol non-negative")
+        if metric not in ("euclidean", "cosine"):
+            raise ValueError(f"metric must be 'euclidean' or 'cosine', got {metric!r}")
+        if isinstance(init, str):
+            if init not in ("k-means++", "random"):
+                raise ValueError(f"init must be 'k-means++', 'random' or an array [K, C], got {init!r}")
+        else:
+            init = torch.as_tensor(np.asarray(init.detach().cpu() if isinstance(init, torch.Tensor) else init)).to(torch.float64)
+            if init.dim() != 2 or init.shape[0] != int(n_clusters):
+                raise ValueError(f"init must be [{int(n_clusters)}, C], got {tuple(init.shape)}")
+        if init_size is not None and int(init_size) < 1:
+            raise ValueError("init_size must be at least 1")
+        self.n_clusters, self.metric, self.init, self.n_init = int(n_clusters), metric, init, int(n_init)
+        self.max_iter, self.tol, self.seed, self.init_size = int(max_iter), float(tol), int(seed), init_size
+        self.cluster_centers_ = self.labels_ = None
+        self._packed = None
+
+    @property
+    def _cosine(self):
+        return self.metric == "cosine"
+
+    @staticmethod
+    def _engine(rows, K, cosine):
+        return (_DeviceKMeans if rows.device.type == "cuda" else _TwinKMeans)(rows, K, cosine)
+
+    # ------------------------------------------------------------------ fit
+    def fit(self, data, rows_per_pass=65536, keep_rows=False):
+        rows = _Rows(data, rows_per_pass, keep_rows)
+        K = self.n_clusters
+        if K > rows.n:
+            raise ValueError(f"n_clusters = {K} for {rows.n} rows")
+        if not isinstance(self.init, str) and self.init.shape[1] != rows.dim:
+            raise ValueError(f"init must be [{K}, {rows.dim}], got {tuple(self.init.shape)}")
+        best = None
+        try:
+            engine = self._engine(rows, K, self._cosine)
+            for r in range(self.n_init):
+                if isinstance(self.init, str):
+                    centres = _kmeans_init(rows, K, self._cosine, self.init, self.seed + r, self.init_size)
+                else:
+                    centres = self.init.to(rows.device)
+                run = _lloyd(engine, rows, centres, self._cosine, self.max_iter, self.tol)
+                if best is None or run["inertia"] < best["inertia"]:
+                    best = run
+        finally:
+            rows.close()
+        on_device = rows.device.type == "cuda"
+        self.cluster_centers_ = best["centres"].to(torch.float32) if on_device else best["centres"]
+        self.labels_, self.inertia_, self.n_iter_ = best["labels"], best["inertia"], best["n_iter"]
+        self.inertia_curve_, self.converged_, self.n_passes_ = best["curve"], best["converged"], engine.n_passes
+        self._packed = None
+        if not self.converged_:
+            warnings.warn(f"KMeansProbe stopped short of tol = {self.tol} after {self.max_iter} iterations", RuntimeWarning)
+        return self
+
+    # ------------------------------------------------------------------ predict / transform
+    def _rows_for(self, data, rows_per_pass):
+        if self.cluster_centers_ is None:
+            raise RuntimeError("fit first")
+        rows = _Rows(data, rows_per_pass, False)
+        rows.first_pass = _is_latents(data)
+        if rows.dim != self.cluster_centers_.shape[1]:
+            rows.close()
+            raise ValueError(f"data has {rows.dim} features, the probe was fitted on {self.cluster_centers_.shape[1]}")
+        return rows
+
+    def predict(self, data, rows_per_pass=65536):
+        rows = self._rows_for(data, rows_per_pass)
+        try:
+            if rows.n == 0:
+                return torch.zeros(0, dtype=torch.int64, device=rows.device)
+            engine = self._engine(rows, self.n_clusters, self._cosine)
+            return engine.walk(self.cluster_centers_.to(rows.device).to(torch.float64), False)[0]
+        finally:
+            rows.close()
+
+    def transform(self, data, rows_per_pass=65536):
+        """Distances to every centre, [N, K]: Euclidean (``sqrt(max(0, |z|^2 - 2 (z . c - 1/2 |c|^2)))``), or ``1 - cos``."""
+        rows = self._rows_for(data, rows_per_pass)
+        K, C = self.cluster_centers_.shape
+        cosine = self._cosine
+        try:
+            if rows.device.type != "cuda":
+                twin = _TwinKMeans(rows, K, cosine)
+                W = self.cluster_centers_.to(torch.float64)
+                b = twin.bias(W)
+                out = []
+                for _, z in rows.groups():
+                    z = z.to(torch.float64)
+                    n2 = (z * z).sum(1, keepdim=True)
+                    if cosine:
+                        out.append(1.0 - (z @ W.T) * torch.where(n2 > 0, 1.0 / torch.sqrt(n2), torch.zeros_like(n2)))
+                    else:
+                        out.append(torch.sqrt((n2 - 2.0 * (z @ W.T + b)).clamp_min(0.0)))
+                return torch.cat(out) if out else torch.zeros((0, K), dtype=torch.float64)
+            if C % 8:
+                raise ValueError("the device path needs a feature width that is a multiple of 8")
+            dev = rows.device
+            if self._packed is None or self._packed[0] != str(dev):
+                npad = -(-K // 8) * 8
+                w = torch.zeros((npad, C), dtype=torch.float32, device=dev)
+                w[:K] = self.cluster_centers_.to(dev)
+                b = torch.zeros(npad, dtype=torch.float32, device=dev)
+                if not cosine:
+                    b[:K] = (-0.5 * (w[:K].to(torch.float64) ** 2).sum(1)).to(torch.float32)
+                self._packed = (str(dev), w, b, npad)
+            _, w, b, npad = self._packed
+            out = torch.empty((rows.n, npad), dtype=torch.float32, device=dev)
+            L = _lib.lib()
+            with torch.cuda.device(dev):
+                for g0, z in rows.groups():
+                    z = z if z.dtype == torch.float32 else z.float()
+                    z = z if z.stride(1) == 1 and z.stride(0) % 4 == 0 else z.contiguous()
+                    g = int(z.shape[0])
+                    o = out[g0:g0 + g]
+                    rc = L.lla_gemm_f32(_lib.ptr(z), int(z.stride(0)) if g > 1 else C, _lib.ptr(w), C, _lib.ptr(b),
+                                        _lib.ptr(o), npad, g, npad, C, 0, _lib.stream_ptr(dev))
+                    _lib.check(rc, "lla_gemm_f32")
+                    n2 = (z * z).sum(1, keepdim=True)
+                    if cosine:
+                        o.copy_(1.0 - o * torch.where(n2 > 0, 1.0 / torch.sqrt(n2), torch.zeros_like(n2)))
+                    else:
+                        o.copy_(torch.sqrt((n2 - 2.0 * o).clamp_min(0.0)))
+            return out[:, :K].contiguous()
+        finally:
+            rows.close()
+
+    # ------------------------------------------------------------------ scores against labels
+    def cluster_scores(self, labels, assigned=None):
+        """``{"nmi", "ari", "purity"}`` of the clustering ``assigned`` (default: ``labels_``) against ``labels``, from their
+        contingency table in float64: NMI = MI / ((H(labels) + H(assigned)) / 2); ARI from the pair counts (Hubert & Arabie
+        1985); purity = the share of rows in their cluster's most frequent class."""
+        if assigned is None:
+            if self.labels_ is None:
+                raise RuntimeError("fit first")
+            assigned = self.labels_
+        n = _contingency(labels, assigned)
+        N = n.sum()
+        rows, cols = n.sum(1), n.sum(0)
+        entropy = lambda m: float(-(m[m > 0] / N * torch.log(m[m > 0] / N)).sum())              # noqa: E731
+        h_rows, h_cols = entropy(rows), entropy(cols)
+        if n.shape[0] == 1 and n.shape[1] == 1:
+            nmi = 1.0
+        else:
+            outer = rows[:, None] * cols[None, :]
+            on = n > 0
+            mi = float((n[on] / N * (torch.log(n[on]) + (torch.log(N) - torch.log(outer[on])))).sum())
+            nmi = max(mi, 0.0) / max((h_rows + h_cols) / 2.0, float(np.finfo(np.float64).eps))
+        squares = float((n * n).sum())
+        N = float(N)
+        c11 = squares - N
+        c01 = float((cols * cols).sum()) - squares
+        c10 = float((rows * rows).sum()) - squares
+        c00 = N * N - c01 - c10 - squares
+        ari = 1.0 if c01 == 0 and c10 == 0 else 2.0 * (c00 * c11 - c01 * c10) / ((c00 + c01) * (c01 + c11) + (c00 + c10) * (c10 + c11))
+        return {"nmi": nmi, "ari": ari, "purity": float(n.amax(0).sum()) / N}
