@@ -685,6 +685,41 @@ int lla_kmeans_pass(const void *z, int z_dtype, int ld_z, int B, int C, const fl
                     int metric, int32_t *out_assign, float *out_dist, float *out_sum, double *out_count, double *out_stats,
                     int accumulate, void *workspace, void *stream);
 
+/* The second moments of the rows in one pass (lossyless_amd/csrc/gram.hip): the sufficient statistics of a ridge probe on
+ * frozen features.  Stands in for `Z.T @ Z`, `Z.sum(0)` and `T.T @ Z` on the decompressed host array that scikit-learn's
+ * Ridge / RidgeClassifier would form from the reference's features (the reference itself fits only iterative predictors:
+ * LinearSVC in its README, the MLP of lossyless/predictors.py); they do not depend on the penalty and add over rows.
+ *   z [B][C] (pitch ld_z; LLA_Z_F32, or LLA_Z_F16 widened exactly); t [B][T] fp32 regression targets (pitch ld_t), or NULL
+ *   with T == 0.
+ *   out_gram [C][C] = sum_i z_i z_i^T (both triangles written, out_gram[c][d] and out_gram[d][c] from one value),
+ *   out_sum [C] = sum_i z_i;  with t: out_cross [T][C] = sum_i t_i z_i^T, out_tsum [T] = sum_i t_i, out_tsq [T] = sum_i t_i^2.
+ *   All outputs are double and contiguous.  accumulate = 1 adds this call's totals to them (a dataset walked in groups).
+ * Exact fp32 products, fp32 accumulation (v_mfma_f32_32x32x2_f32) along a walker's rows -- a chain is never longer than B --
+ * and every sum of chains, the column sums and the target sums in double.  No floating-point atomics: workgroups leave
+ * partial tiles in `workspace` (lla_gram_pass_workspace_bytes(C, T) bytes; 0 for a refused shape) and a last kernel adds
+ * them in walker order; the grid depends on (B, C, T) alone: the same inputs give the same bits.
+ * C % 8 == 0, 8 <= C <= 1024, ld_z >= C and a multiple of 4, z 16-byte (fp16: 8-byte) aligned; t != NULL: 1 <= T <= 4096,
+ * ld_t >= T (ANY pitch, not only multiples of 4 as for z: targets are read one by one, so that T == 1 takes a plain [B]
+ * vector), t 4-byte aligned.  The cap of 4096 targets bounds the grid and the workspace; the walkers per tile are
+ * 512 / (Gram tiles + cross tiles), so once the tiles exceed 512 (C = 1024: T > 1900) every tile has one walker, whose
+ * fp32 chain is as long as B and which has no row parallelism: many targets are better passed in several calls; out_gram, out_sum, workspace (with t: out_cross,
+ * out_tsum, out_tsq) not NULL and 16-byte aligned; anything else is LLA_EINVAL, decided before any device call.  B == 0:
+ * LLA_OK, no kernel is launched (the outputs are zeroed unless accumulate is set). */
+size_t lla_gram_pass_workspace_bytes(int C, int T);
+int lla_gram_pass(const void *z, int z_dtype, int ld_z, int B, int C, const float *t, int ld_t, int T, double *out_gram,
+                  double *out_sum, double *out_cross, double *out_tsum, double *out_tsq, int accumulate, void *workspace,
+                  void *stream);
+
+/* Column sums per run of rows (csrc/gram.hip): out [S][C] = sum of z_i over rows seg_offsets[s] <= i < seg_offsets[s + 1], in
+ * double.  Stands in for `onehot(Y).T @ Z` of a RidgeClassifier fit on rows sorted by class: the cross-moments of class
+ * labels without the one-hot matrix.  seg_offsets is HOST memory: S + 1 ascending offsets, [0] == 0, [S] == B; empty
+ * segments are allowed and give zeros.  Eight row lanes per segment add their rows (row = lane mod 8) in row order and are
+ * added in lane order: a function of the offsets alone.  z as for lla_gram_pass; S >= 1, out 16-byte aligned; anything else
+ * (offsets that descend or do not end at B included) is LLA_EINVAL before any device call.  B == 0: LLA_OK, no kernel
+ * (out is zeroed unless accumulate is set). */
+int lla_segment_sums(const void *z, int z_dtype, int ld_z, int B, int C, const int32_t *seg_offsets, int S, double *out,
+                     int accumulate, void *stream);
+
 /* ---- A training step of the reference's MLP predictor (csrc/mlp.hip): what lla_gemm_f32, the forward half of an fp32
  * Linear layer, lacks.  Everything is fp32, row-major, pitches in elements; v_mfma_f32_32x32x2_f32 (exact fp32 products,
  * fp32 accumulation), no floating-point atomics, the order of every sum fixed by the shape alone (the same inputs give the

@@ -105,6 +105,9 @@ _SIGNATURES = {
     "lla_knn_finish": (_i, [_i, _i, _i, _vp, _i, ctypes.c_float, _vp, _vp, _vp, _vp, _vp]),
     "lla_kmeans_pass_workspace_bytes": (_sz, [_i, _i]),
     "lla_kmeans_pass": (_i, [_vp, _i, _i, _i, _i, _vp, _vp, _i, _i, _i, _vp, _vp, _vp, _vp, _vp, _i, _vp, _vp]),
+    "lla_gram_pass_workspace_bytes": (_sz, [_i, _i]),
+    "lla_gram_pass": (_i, [_vp, _i, _i, _i, _i, _vp, _i, _i, _vp, _vp, _vp, _vp, _vp, _i, _vp, _vp]),
+    "lla_segment_sums": (_i, [_vp, _i, _i, _i, _i, _vp, _i, _vp, _i, _vp]),
     "lla_gemm_f32_nn": (_i, [_vp, _i, _vp, _i, _vp, _i, _vp, _i, _i, _i, _i, _vp]),
     "lla_gemm_f32_tn": (_i, [_vp, _i, _vp, _i, _vp, _i, _vp, _i, _i, _i, _vp]),
     "lla_softmax_xent_workspace_bytes": (_sz, [_i]),

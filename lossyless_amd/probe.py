@@ -28,7 +28,12 @@ joint Newton-CG), over the same walk of the rows and the same scoring path.
 
 :class:`KMeansProbe` is the unsupervised sibling: Lloyd's k-means over the same walk (``lla_kmeans_pass``, csrc/kmeans.hip:
 the argmax over the centres in the place of a residual), with the clusters scored against labels afterwards.
+
+:class:`RidgeProbe` / :class:`RidgeProbeCV` are the closed-form siblings: one walk accumulates the rows' second moments
+(``lla_gram_pass`` / ``lla_segment_sums``, csrc/gram.hip) and a float64 ``eigh`` gives every alpha and fold from them.
 """
+import contextlib
+import ctypes
 import warnings
 
 import numpy as np
@@ -48,11 +53,14 @@ def _is_latents(data):
 
 
 class _Rows:
-    """The rows of a fit / predict call, walked in file order in groups: ``groups()`` yields (first row, rows [g, C])."""
+    """The rows of a fit / predict call, walked in file order in groups: ``groups()`` yields (first row, rows [g, C]).
+    With ``order`` set (an int64 permutation [N] on the rows' device that keeps every row inside its group), position i of
+    the walk is row ``order[i]``: the ridge probes fetch each group sorted by (fold, class)."""
 
     def __init__(self, data, rows_per_pass, keep_rows):
         self.group = max(int(rows_per_pass), 1)
         self.kept = None
+        self.order = None
         self.first_pass = True
         if _is_latents(data):
             self.latents, self.rows = data, None
@@ -82,9 +90,9 @@ class _Rows:
         for g0 in range(0, self.n, self.group):
             g = min(self.group, self.n - g0)
             if self.rows is not None:
-                z = self.rows[g0:g0 + g]
+                z = self.rows[g0:g0 + g] if self.order is None else self.rows.index_select(0, self.order[g0:g0 + g])
             else:
-                idx = torch.arange(g0, g0 + g, device=self.device)
+                idx = torch.arange(g0, g0 + g, device=self.device) if self.order is None else self.order[g0:g0 + g]
                 if self.keep:
                     z = self.latents.take(idx, check=first)
                 else:
@@ -2582,3 +2590,441 @@ class KMeansProbe:
         c00 = N * N - c01 - c10 - squares
         ari = 1.0 if c01 == 0 and c10 == 0 else 2.0 * (c00 * c11 - c01 * c10) / ((c00 + c01) * (c01 + c11) + (c00 + c10) * (c10 + c11))
         return {"nmi": nmi, "ari": ari, "purity": float(n.amax(0).sum()) / N}
+
+
+# ---------------------------------------------------------------------- ridge regression from one Gram pass
+def _ridge_targets(data, labels, n):
+    """-> ("classify", class labels int64 [N]) or ("regress", targets float64 [N, T], whether they came as [N])."""
+    if labels is not None:
+        y = labels.detach().cpu() if isinstance(labels, torch.Tensor) else torch.from_numpy(np.asarray(labels))
+        if y.is_floating_point():
+            if y.dim() not in (1, 2) or y.shape[0] != n or (y.dim() == 2 and y.shape[1] < 1):
+                raise ValueError(f"targets of shape {tuple(y.shape)} for {n} rows: need [N] or [N, T]")
+            t = y.to(torch.float64).reshape(n, -1)
+            if not bool(torch.isfinite(t).all()):
+                raise ValueError("non-finite targets")
+            return "regress", t, y.dim() == 1
+    return "classify", _labels_of(data, labels, n), False
+
+
+def _kfolds_of(cv_arg, N):
+    """Folds of a regression: an int is scikit-learn's unshuffled ``KFold`` (contiguous in file order, the first ``N % cv``
+    folds one row longer); an int array [N] is taken as ``_folds_of`` takes it.  -> (fold id per row int64 [N], fold ids)."""
+    if isinstance(cv_arg, (int, np.integer)):
+        cv = int(cv_arg)
+        if cv < 2 or cv > N:
+            raise ValueError(f"cv must be at least 2 and at most the number of rows, got {cv} for {N} rows")
+        sizes = torch.full((cv,), N // cv, dtype=torch.int64)
+        sizes[:N % cv] += 1
+        return torch.repeat_interleave(torch.arange(cv), sizes), list(range(cv))
+    fold, ids, _ = _folds_of(cv_arg, torch.zeros(N, dtype=torch.int64), 1)      # (a fold that holds every row is refused there)
+    return fold, ids
+
+
+class _TwinMoments:
+    """The second moments of runs of rows in float64 torch -- the CPU path of the ridge probes and the oracle of the GPU
+    tests.  Bucket f holds ``gram`` [C, C], ``sum`` [C] and ``cross`` [K or T, C] (class sums, or sum t z^T) of the runs
+    added to it, and for regression ``tsum`` / ``tsq`` [T]."""
+
+    def __init__(self, rows, nb, n_cross, regress):
+        C = rows.dim
+        self.gram = torch.zeros((nb, C, C), dtype=torch.float64)
+        self.sum = torch.zeros((nb, C), dtype=torch.float64)
+        self.cross = torch.zeros((nb, n_cross, C), dtype=torch.float64)
+        self.tsum = torch.zeros((nb, n_cross), dtype=torch.float64)
+        self.tsq = torch.zeros((nb, n_cross), dtype=torch.float64)
+
+    def targets(self, t):
+        return t
+
+    def add(self, f, z, seg, t):
+        """Run z [r, C] into bucket f: ``seg`` int32 [K + 1] are the offsets of its class runs, or ``t`` [r, T] its targets."""
+        z = z.to(torch.float64)
+        self.gram[f] += z.T @ z
+        self.sum[f] += z.sum(0)
+        if seg is not None:
+            which = torch.repeat_interleave(torch.arange(len(seg) - 1), torch.diff(seg.to(torch.int64)))
+            self.cross[f].index_add_(0, which, z)
+        else:
+            self.cross[f] += t.T @ z
+            self.tsum[f] += t.sum(0)
+            self.tsq[f] += (t * t).sum(0)
+
+    def result(self):
+        return self.gram, self.sum, self.cross, self.tsum, self.tsq
+
+
+class _DeviceMoments:
+    """The same on the device: a run is one ``lla_gram_pass`` (csrc/gram.hip) accumulating into its bucket, plus one
+    ``lla_segment_sums`` for its class sums; regression targets go through the Gram pass, rounded to fp32."""
+
+    def __init__(self, rows, nb, n_cross, regress):
+        C, dev = rows.dim, rows.device
+        if C % 8 or not 8 <= C <= 1024:
+            raise ValueError(f"the device ridge needs a feature width that is a multiple of 8 in [8, 1024], got {C}")
+        self.T = n_cross if regress else 0
+        nbytes = int(_lib.lib().lla_gram_pass_workspace_bytes(C, self.T))
+        if nbytes == 0:
+            raise ValueError(f"lla_gram_pass refuses C = {C}, T = {self.T}")
+        self.dev, self.C = dev, C
+        self.ws = torch.empty(nbytes, dtype=torch.uint8, device=dev)
+        self.gram = torch.zeros((nb, C, C), dtype=torch.float64, device=dev)
+        self.sum = torch.zeros((nb, C), dtype=torch.float64, device=dev)
+        self.cross = torch.zeros((nb, n_cross, C), dtype=torch.float64, device=dev)
+        pad = -(-n_cross // 2) * 2                 # (every bucket's row 16-byte aligned)
+        self.tsum = torch.zeros((nb, pad), dtype=torch.float64, device=dev)
+        self.tsq = torch.zeros((nb, pad), dtype=torch.float64, device=dev)
+        self.n_cross = n_cross
+
+    def targets(self, t):
+        return t.to(torch.float32).to(self.dev).contiguous()
+
+    def add(self, f, z, seg, t):
+        L, C, r = _lib.lib(), self.C, int(z.shape[0])
+        zt = _lib.LLA_Z_F16 if z.dtype == torch.float16 else _lib.LLA_Z_F32
+        ld = int(z.stride(0)) if r > 1 else C
+        st = _lib.stream_ptr(self.dev)
+        with_t = seg is None
+        rc = L.lla_gram_pass(_lib.ptr(z), zt, ld, r, C, _lib.ptr(t) if with_t else None, self.T, self.T,
+                             _lib.ptr(self.gram[f]), _lib.ptr(self.sum[f]), _lib.ptr(self.cross[f]) if with_t else None,
+                             _lib.ptr(self.tsum[f]) if with_t else None, _lib.ptr(self.tsq[f]) if with_t else None, 1,
+                             _lib.ptr(self.ws), st)
+        _lib.check(rc, "lla_gram_pass")
+        if seg is not None:
+            rc = L.lla_segment_sums(_lib.ptr(z), zt, ld, r, C, ctypes.c_void_p(seg.data_ptr()), int(seg.numel()) - 1,
+                                    _lib.ptr(self.cross[f]), 1, st)
+            _lib.check(rc, "lla_segment_sums")
+
+    def result(self):
+        n = self.n_cross
+        return self.gram.cpu(), self.sum.cpu(), self.cross.cpu(), self.tsum[:, :n].cpu(), self.tsq[:, :n].cpu()
+
+
+class _RidgeWalk:
+    """What the ridge probes walk: the rows sorted inside every decode group by (bucket, class), so that a bucket -- a
+    held-out fold, or the rows no fold holds -- is one contiguous run of every group, and its classes are runs of that run.
+    ``runs(g0, g)`` yields (bucket, first, last + 1 within the group, class offsets int32 [K + 1] or None)."""
+
+    def __init__(self, rows, bucket, nb, cls, K):
+        self.nb, self.K = int(nb), int(K)
+        N, G = rows.n, rows.group
+        group = torch.arange(N, dtype=torch.int64) // G
+        key = bucket if cls is None else bucket * self.K + cls
+        self.sorted = cls is not None or nb > 1
+        self.order = torch.argsort(group * (self.nb * self.K) + key, stable=True) if self.sorted else None
+        self.key = key[self.order] if self.sorted else key
+        self.with_classes = cls is not None
+        if self.sorted:
+            rows.order = self.order.to(rows.device)
+
+    def take(self, x):
+        return x[self.order] if self.sorted else x
+
+    def runs(self, g0, g):
+        cnt = torch.bincount(self.key[g0:g0 + g], minlength=self.nb * self.K).reshape(self.nb, self.K)
+        first = 0
+        for f in range(self.nb):
+            r = int(cnt[f].sum())
+            if r:
+                seg = None
+                if self.with_classes:
+                    seg = torch.zeros(self.K + 1, dtype=torch.int32)
+                    seg[1:] = torch.cumsum(cnt[f], 0)
+                yield f, first, first + r, seg
+            first += r
+
+
+def _ridge_moments(rows, walk, t):
+    """One walk of the rows -> per bucket (gram [C, C], sum [C], cross [K or T, C], tsum [T], tsq [T]) float64 on the CPU."""
+    regress = t is not None
+    Engine = _DeviceMoments if rows.device.type == "cuda" else _TwinMoments
+    engine = Engine(rows, walk.nb, t.shape[1] if regress else walk.K, regress)
+    tp = engine.targets(walk.take(t)) if regress else None
+    with torch.cuda.device(rows.device) if rows.device.type == "cuda" else contextlib.nullcontext():
+        for g0, z in rows.groups():
+            for f, a, b, seg in walk.runs(g0, int(z.shape[0])):
+                engine.add(f, z[a:b], seg, tp[g0 + a:g0 + b] if regress else None)
+        return engine.result()
+
+
+def _signed_targets(n, s, class_sums, counts):
+    """The cross-moments of the +1 / -1 targets of ``RidgeClassifier`` from the class sums: ``Z^T Y`` with
+    ``Y = 2 onehot - 1`` is ``2 R_classsum - s``; two classes are the one column of ``classes_[1]``.
+    -> (R [K or 1, C], ts [K or 1])."""
+    R, ts = 2.0 * class_sums - s[None, :], 2.0 * counts - n
+    return (R[1:2], ts[1:2]) if R.shape[0] == 2 else (R, ts)
+
+
+def _ridge_solve(n, G, s, R, ts, alphas, fit_intercept=True):
+    """``min |T - Z W^T - b|^2 + alpha |W|^2`` (the intercept not penalised) for every alpha, from the moments of the rows
+    in float64: n, G = sum z z^T [C, C], s = sum z [C], R = sum t z^T [T, C], ts = sum t [T].  One ``eigh`` of the centred
+    Gram matrix serves all alphas: ``W = (Rc V) / (lam + alpha) V^T``, ``b = mt - W mu``.  -> (W [A, T, C], b [A, T])."""
+    G, s, R, ts = (x.to(torch.float64) for x in (G, s, R, ts))
+    n = float(n)
+    if fit_intercept:
+        mu, mt = s / n, ts / n
+        G = G - n * torch.outer(mu, mu)
+        R = R - n * torch.outer(mt, mu)
+    lam, V = torch.linalg.eigh((G + G.T) / 2)
+    lam = lam.clamp_min(0.0)
+    RV = R @ V
+    Ws, bs = [], []
+    for alpha in alphas:
+        d = lam + float(alpha)
+        W = (RV * torch.where(d > 0, 1.0 / d, torch.zeros_like(d))[None, :]) @ V.T
+        Ws.append(W)
+        bs.append(mt - W @ mu if fit_intercept else torch.zeros_like(ts))
+    return torch.stack(Ws), torch.stack(bs)
+
+
+def _check_alpha(alpha):
+    alpha = float(alpha)
+    if not alpha >= 0 or not np.isfinite(alpha):
+        raise ValueError(f"alpha must be finite and non-negative, got {alpha}")
+    return alpha
+
+
+class RidgeProbe(_Scores):
+    """``RidgeProbe(alpha=1.0, fit_intercept=True)``: scikit-learn's ``Ridge`` / ``RidgeClassifier`` on the frozen
+    representations, ``min |T - Z W^T - b|^2 + alpha |W|^2`` with the intercept not penalised, from ONE walk of the rows.
+    The walk accumulates the rows' second moments (``lla_gram_pass`` / ``lla_segment_sums``, csrc/gram.hip: fp32 MFMA chains
+    joined in double); the solve is one float64 ``eigh`` of the centred C x C Gram matrix on the host.
+
+    ``fit(data, labels=None, rows_per_pass=65536, keep_rows=False)`` takes what ``LinearProbe.fit`` takes.  Integer labels
+    mean classification: targets +1 / -1 per class, two classes solved as the one column of ``classes_[1]``, ``classes_``
+    set.  Floating labels ``[N]`` or ``[N, T]`` mean regression (on the device they are rounded to fp32).  CPU data run the
+    float64 twin of the same moments and the same solve.  Sample weights and ``class_weight`` are not built.
+
+    After ``fit``: ``coef_`` float64 ``[K, C]`` (``[1, C]`` for two classes, ``[T, C]`` for regression) and ``intercept_``
+    on the CPU, ``moments_`` (the float64 statistics: ``n``, ``gram``, ``sum``, ``cross`` -- class sums or ``sum t z^T`` --
+    ``tsum`` -- class counts or ``sum t`` -- and ``tsq``), ``n_passes_ = 1``.  ``path(alphas)`` returns fitted probes for
+    other alphas from ``moments_`` with no data pass.  ``decision_function`` / ``predict`` run on ``lla_gemm_f32`` (fp32) on
+    the device and in float64 on the CPU; ``score`` is the accuracy, or scikit-learn's R^2 (uniform average over targets)."""
+
+    def __init__(self, alpha=1.0, fit_intercept=True):
+        self.alpha, self.fit_intercept = _check_alpha(alpha), bool(fit_intercept)
+        self.coef_ = self.intercept_ = self.classes_ = self.moments_ = None
+
+    def fit(self, data, labels=None, rows_per_pass=65536, keep_rows=False):
+        rows = _Rows(data, rows_per_pass, keep_rows)
+        try:
+            self.moments_ = _fit_moments(rows, data, labels, None)[0]
+        finally:
+            rows.close()
+        return self._solve()
+
+    def _solve(self):
+        m = self.moments_
+        R, ts = _signed_targets(m["n"], m["sum"], m["cross"], m["tsum"]) if m["kind"] == "classify" else (m["cross"], m["tsum"])
+        W, b = _ridge_solve(m["n"], m["gram"], m["sum"], R, ts, [self.alpha], self.fit_intercept)
+        self.coef_, self.intercept_ = W[0], b[0]
+        self.classes_ = m["classes"]
+        self.n_passes_, self._packed = 1, None
+        return self
+
+    def path(self, alphas):
+        """Fitted probes for ``alphas`` from ``moments_``: no pass over the data."""
+        if self.moments_ is None:
+            raise RuntimeError("fit first")
+        out = []
+        for alpha in alphas:
+            probe = RidgeProbe(alpha, self.fit_intercept)
+            probe.moments_ = self.moments_
+            out.append(probe._solve())
+        return out
+
+    def decision_function(self, data, rows_per_pass=65536):
+        s = self._scores(data, rows_per_pass)
+        m = self.moments_
+        one = len(self.classes_) == 2 if m["kind"] == "classify" else m["squeeze"]
+        return s[:, 0].contiguous() if one else s.contiguous()
+
+    def predict(self, data, rows_per_pass=65536):
+        if self.coef_ is not None and self.moments_["kind"] == "regress":
+            return self.decision_function(data, rows_per_pass)
+        return super().predict(data, rows_per_pass)
+
+    def score(self, data, labels=None, rows_per_pass=65536):
+        if self.coef_ is None or self.moments_["kind"] == "classify":
+            return super().score(data, labels, rows_per_pass)
+        pred = self.predict(data, rows_per_pass).to(torch.float64)
+        pred = pred.reshape(pred.shape[0], -1)
+        kind, t, _ = _ridge_targets(data, labels, pred.shape[0])
+        if kind != "regress" or t.shape[1] != pred.shape[1]:
+            raise ValueError(f"a regression probe with {pred.shape[1]} targets needs floating targets of that shape")
+        t = t.to(pred.device)
+        res, tot = ((t - pred) ** 2).sum(0), ((t - t.mean(0)) ** 2).sum(0)
+        return float((1.0 - res / tot).mean())
+
+
+def _fit_moments(rows, data, labels, cv):
+    """The walk of a ridge fit: -> (total moments dict, per-fold held-out moments, walk, targets' bookkeeping).  ``cv`` None:
+    nothing is held out (one bucket)."""
+    if rows.n < 1:
+        raise ValueError("no rows")
+    kind, y, squeeze = _ridge_targets(data, labels, rows.n)
+    classes = cls = None
+    if kind == "classify":
+        classes = torch.unique(y)
+        if classes.numel() < 2:
+            raise ValueError("a ridge classifier needs at least two classes")
+        cls = torch.searchsorted(classes, y)
+    K = int(classes.numel()) if classes is not None else 1
+    if cv is None:
+        fold, ids = torch.full((rows.n,), -1, dtype=torch.int64), []
+    elif kind == "classify":
+        fold, ids, _ = _folds_of(cv, cls, K)
+    else:
+        fold, ids = _kfolds_of(cv, rows.n)
+    nf = len(ids)
+    bucket = torch.full((rows.n,), nf, dtype=torch.int64)             # rows no fold holds: the last bucket
+    for i, f in enumerate(ids):
+        bucket[fold == f] = i
+    walk = _RidgeWalk(rows, bucket, nf + 1, cls, K)
+    gram, s, cross, tsum, tsq = _ridge_moments(rows, walk, y if kind == "regress" else None)
+    n = torch.bincount(bucket, minlength=nf + 1).to(torch.float64)
+    if kind == "classify":                                           # class counts and sum y^2, exactly, from the labels
+        tsum = torch.bincount(bucket * K + cls, minlength=(nf + 1) * K).reshape(nf + 1, K).to(torch.float64)
+        tsq = n[:, None].expand(nf + 1, K).clone()
+    extra = dict(kind=kind, classes=classes.numpy() if classes is not None else None, squeeze=squeeze)
+    parts = [dict(n=float(n[f]), gram=gram[f], sum=s[f], cross=cross[f], tsum=tsum[f], tsq=tsq[f], **extra)
+             for f in range(nf + 1)]
+    total = dict(n=float(n.sum()), gram=gram.sum(0), sum=s.sum(0), cross=cross.sum(0), tsum=tsum.sum(0), tsq=tsq.sum(0), **extra)
+    return total, parts[:nf], walk, (fold, ids, cls)
+
+
+def _ridge_fold_fits(total, held, alphas, fit_intercept):
+    """Every (fold, alpha) of a search from the moments: fold f trains on ``total - held[f]``, one ``eigh`` per fold.
+    -> (W [folds, A, T, C], b [folds, A, T])."""
+    classify = total["kind"] == "classify"
+    Ws, bs = [], []
+    for h in held:
+        train = {k: total[k] - h[k] for k in ("n", "gram", "sum", "cross", "tsum")}
+        R, ts = _signed_targets(train["n"], train["sum"], train["cross"], train["tsum"]) if classify else \
+            (train["cross"], train["tsum"])
+        W, b = _ridge_solve(train["n"], train["gram"], train["sum"], R, ts, alphas, fit_intercept)
+        Ws.append(W)
+        bs.append(b)
+    return torch.stack(Ws), torch.stack(bs)
+
+
+def _ridge_held_out_mse(held, W, b):
+    """The held-out mean squared error of every (alpha, fold) from the fold's own moments, no data pass:
+    ``SSE_f = tt_f - 2 <W, R_f> - 2 b . ts_f + <W G_f, W> + 2 (W s_f) . b + n_f |b|^2``, over ``n_f T``.  -> [A, folds]."""
+    mse = torch.empty((W.shape[1], len(held)), dtype=torch.float64)
+    for f, h in enumerate(held):
+        Wf, bf = W[f], b[f]                                       # [A, T, C], [A, T]
+        sse = h["tsq"][None] - 2 * (Wf * h["cross"][None]).sum(2) - 2 * bf * h["tsum"][None] \
+            + ((Wf @ h["gram"]) * Wf).sum(2) + 2 * (Wf @ h["sum"]) * bf + h["n"] * bf * bf
+        mse[:, f] = sse.sum(1) / (h["n"] * Wf.shape[1])
+    return mse
+
+
+_SCORE_ELEMS = 1 << 25    # fp32 scores a scoring walk of RidgeProbeCV holds at a time: larger runs are scored in pieces
+
+
+class RidgeProbeCV:
+    """``RidgeProbeCV(alphas, cv=5, fit_intercept=True)``: the K-fold search over ``alpha`` of a :class:`RidgeProbe` from
+    the moments of ONE walk.  The moments add over rows, so the walk keeps them per fold, a fold's training moments are the
+    total minus its own, one ``eigh`` per fold serves every alpha, and ``best_estimator_`` is solved from the total.
+
+    Walks of the data: classification 2 (the moments, then one walk that scores every fold's rows against that fold's
+    ``len(alphas)`` classifiers on ``lla_gemm_f32``); regression 1 (the held-out squared error is a closed form of the
+    fold's own moments: ``SSE_f = tt_f - 2 <W, R_f> - 2 b . ts_f + <W G_f, W> + 2 (W s_f) . b + n_f |b|^2``).
+
+    cv      an int: stratified and unshuffled as ``LinearProbeCV`` for classification, scikit-learn's unshuffled ``KFold``
+            (contiguous in file order) for regression; or an int array ``[N]`` of fold ids (-1: always trains).
+    Inside every decode group the rows are fetched in (fold, class) order (``take`` / ``index_select``), so each fold is one
+    run per group: one ``lla_gram_pass`` and, for class labels, one ``lla_segment_sums``.
+
+    ``fit(data, labels=None, rows_per_pass=65536, keep_rows=False)``; afterwards ``cv_scores_`` float64
+    ``[len(alphas), folds]`` (accuracy, or negative mean squared error), ``mean_scores_``, ``best_index_`` (the LOWEST alpha
+    among the best means), ``best_params_``, ``best_estimator_`` (a fitted ``RidgeProbe``, no further pass), ``folds_``,
+    ``fold_coef_`` / ``fold_intercept_`` float64 ``[len(alphas), folds, K or T, C]``, ``fold_moments_`` (every fold's own
+    moments, as ``RidgeProbe.moments_``), ``classes_``, ``n_passes_``.  Sample weights and ``class_weight`` are not built."""
+
+    def __init__(self, alphas, cv=5, fit_intercept=True):
+        self.alphas = [_check_alpha(a) for a in alphas]
+        if not self.alphas:
+            raise ValueError("no alphas")
+        self.cv, self.fit_intercept = cv, bool(fit_intercept)
+        self.cv_scores_ = self.best_estimator_ = None
+
+    @staticmethod
+    def logspace(n, low, high):
+        """n alphas spaced evenly on a log scale from ``low`` to ``high``."""
+        if not 0 < low <= high or int(n) < 1:
+            raise ValueError("need 0 < low <= high and n >= 1")
+        return [float(a) for a in np.exp(np.linspace(np.log(low), np.log(high), int(n))).clip(low, high)]
+
+    def fit(self, data, labels=None, rows_per_pass=65536, keep_rows=False):
+        rows = _Rows(data, rows_per_pass, keep_rows)
+        A = len(self.alphas)
+        try:
+            total, held, walk, (fold, ids, cls) = _fit_moments(rows, data, labels, self.cv)
+            classify = total["kind"] == "classify"
+            W, b = _ridge_fold_fits(total, held, self.alphas, self.fit_intercept)
+            self.n_passes_ = 1
+            if classify:
+                right = self._score(rows, walk, W, b, walk.take(cls))
+                self.n_passes_ = 2
+                n_held = torch.tensor([h["n"] for h in held], dtype=torch.float64)
+                self.cv_scores_ = right.T.double() / n_held[None, :]
+            else:
+                self.cv_scores_ = -_ridge_held_out_mse(held, W, b)
+        finally:
+            rows.close()
+        self.mean_scores_ = self.cv_scores_.mean(1)
+        best = [i for i in range(A) if float(self.mean_scores_[i]) == float(self.mean_scores_.max())]
+        self.best_index_ = min(best, key=lambda i: self.alphas[i])                 # the lowest alpha on ties
+        self.best_params_ = {"alpha": self.alphas[self.best_index_]}
+        self.fold_coef_, self.fold_intercept_ = W.transpose(0, 1).contiguous(), b.transpose(0, 1).contiguous()
+        self.classes_, self.folds_, self.fold_moments_ = total["classes"], list(ids), held
+        probe = RidgeProbe(self.best_params_["alpha"], self.fit_intercept)
+        probe.moments_ = total
+        self.best_estimator_ = probe._solve()
+        return self
+
+    @staticmethod
+    def _score(rows, walk, W, b, cls):
+        """The scoring walk: the run of fold f in every group against fold f's classifiers (``lla_gemm_f32`` on the device,
+        float64 on the CPU) -> matches int64 [folds, A] on the CPU."""
+        nf, A, Kp, C = W.shape
+        dev = rows.device
+        right = torch.zeros((nf, A), dtype=torch.int64, device=dev)
+        cls = cls.to(dev)
+
+        def count(S, f, r0):
+            S = S.reshape(S.shape[0], A, Kp)
+            pred = (S[:, :, 0] > 0).to(torch.int64) if Kp == 1 else S.argmax(2)
+            right[f] += (pred == cls[r0:r0 + S.shape[0], None]).sum(0)
+
+        if dev.type == "cuda":
+            J = A * Kp
+            npad = -(-J // 8) * 8
+            w = torch.zeros((nf, npad, C), dtype=torch.float32, device=dev)
+            bp = torch.zeros((nf, npad), dtype=torch.float32, device=dev)
+            w[:, :J], bp[:, :J] = W.reshape(nf, J, C).to(dev), b.reshape(nf, J).to(dev)
+            piece = max(min(_SCORE_ELEMS // npad, rows.group), 1)
+            out = torch.empty((min(piece, rows.n), npad), dtype=torch.float32, device=dev)
+            L = _lib.lib()
+            with torch.cuda.device(dev):
+                for g0, z in rows.groups():
+                    z = z if z.dtype == torch.float32 else z.float()
+                    for f, a0, a1, _ in walk.runs(g0, int(z.shape[0])):
+                        if f >= nf:
+                            continue
+                        for r0 in range(a0, a1, piece):
+                            zz = z[r0:min(r0 + piece, a1)]
+                            n = int(zz.shape[0])
+                            rc = L.lla_gemm_f32(_lib.ptr(zz), int(zz.stride(0)) if n > 1 else C, _lib.ptr(w[f]), C,
+                                                _lib.ptr(bp[f]), _lib.ptr(out), npad, n, npad, C, 0, _lib.stream_ptr(dev))
+                            _lib.check(rc, "lla_gemm_f32")
+                            count(out[:n, :J], f, g0 + r0)
+        else:
+            for g0, z in rows.groups():
+                z = z.to(torch.float64)
+                for f, a0, a1, _ in walk.runs(g0, int(z.shape[0])):
+                    if f < nf:
+                        count(z[a0:a1] @ W[f].reshape(A * Kp, C).T + b[f].reshape(-1), f, g0 + a0)
+        return right.cpu()

@@ -88,6 +88,10 @@ def main():
                     help="also run the training-free protocol, lossyless_amd.KNNProbe (weighted k-NN: cosine, k = 20, T = 0.07), "
                          "on the device from the container kept compressed (adds knn_probe_accuracy, the leave-one-out "
                          "knn_probe_train_accuracy and knn_probe_s)")
+    ap.add_argument("--device-ridge", type=int, default=0, metavar="N",
+                    help="also run lossyless_amd.RidgeProbeCV (scikit-learn's RidgeClassifier objective, N values of alpha "
+                         "log-spaced in [1e-3, 1e3], 5 stratified folds, two walks of the container in all) on the device "
+                         "(adds ridge_probe_cv_best, _validation_accuracy, _accuracy and _fit_s)")
     args = ap.parse_args()
 
     weights = os.environ.get("LOSSYLESS_CLIP_WEIGHTS", "synthetic")
@@ -197,6 +201,14 @@ def main():
                     torch.cuda.synchronize()
                     probe.update(knn_probe_s=round(time.perf_counter() - t0, 3), knn_probe_accuracy=knn_accuracy,
                                  knn_probe_train_accuracy=knn_train)
+                if args.device_ridge:
+                    from lossyless_amd import RidgeProbeCV
+                    t0 = time.perf_counter()
+                    ridge = RidgeProbeCV(RidgeProbeCV.logspace(args.device_ridge, 1e-3, 1e3), cv=5).fit(comp.open_dataset(f), np.asarray(Y))
+                    torch.cuda.synchronize()
+                    probe.update(ridge_probe_cv_fit_s=round(time.perf_counter() - t0, 3), ridge_probe_cv_best=ridge.best_params_,
+                                 ridge_probe_cv_validation_accuracy=float(ridge.mean_scores_.max()),
+                                 ridge_probe_cv_accuracy=float(ridge.best_estimator_.score(comp.open_dataset(ft), np.asarray(Yt))))
         print(json.dumps(dict(rate_point=name, data=data, clip_weights=weights, images=n,
                               call=("Dataset(transform=RawRGB) -> compress_dataset(dataset, file, label_file, "
                                     f"dict(batch_size={args.batch}, num_workers={args.workers}))") if shaped
