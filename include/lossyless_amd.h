@@ -859,6 +859,19 @@ int lla_gemm_resid_layernorm768(const void *A, int lda, const void *W, const flo
                                 void *stream);
 /* qkv fp16 [B*50][2304] -> o fp16 [B*50][768]; 12 heads of 64, softmax(QK^T/8)V. */
 int lla_attention50(const void *qkv, void *o, int B, void *stream);
+/* lla_layernorm768 / lla_attention50 with the walk the tower uses on every second slice: rev 0 = first rows (images)
+ * first, 1 = last first; the same bits either way.  Any other rev is LLA_EINVAL. */
+int lla_layernorm768_ex(const float *x, size_t row_stride, const float *w, const float *b, void *y16, int rows, int rev,
+                        void *stream);
+int lla_attention50_ex(const void *qkv, void *o, int B, int rev, void *stream);
+/* The tower's token assembly as lla_vit_b32_forward launches it, over x fp32 [rows][768] whose rows r % 50 != 0 hold
+ * patch embedding + positional embedding (lla_patch_embed_f16):
+ *   x[r] = ln_pre(r % 50 == 0 ? cls + pos[0] : x[r]) (fp32, in place; the class rows of x are not read)
+ *   h16[r] (fp16) = ln_1 of block 0 of that x[r]  -- the bits lla_layernorm768 gives on the x written
+ * cls fp32 [768], pos fp32 [>= 768] (row 0 of the positional embedding), wpre / bpre / w1 / b1 fp32 [768], eps 1e-5.
+ * rows < 0, or a NULL pointer with rows > 0: LLA_EINVAL.  rows == 0: LLA_OK, nothing launched. */
+int lla_ln_pre_ln1_768(float *x, const float *cls, const float *pos, const float *wpre, const float *bpre, const float *w1,
+                       const float *b1, void *h16, int rows, void *stream);
 
 /* ------------------------------------------------------------------------- *
  * Device entry point: CLIP RN50 visual tower
@@ -888,6 +901,17 @@ size_t lla_rn50_workspace_bytes(int chunk);
  * slices (lla_rn50_workspace_bytes returns that size); joined back into `stream` before returning. */
 int lla_rn50_forward(const void *images_nhwc_f16, int B, const void *weights, void *workspace,
                      size_t workspace_bytes, int chunk, void *z_out, void *stream, void *tower);
+/* The tower's pooling kernels on their own, as lla_rn50_forward launches them (all fp16, fp32 arithmetic, one rounding):
+ * 2x2 average pool (clip/model.py Bottleneck.avgpool and the downsample's AvgPool2d): in NHWC [n][H][W][pitch] (first C
+ * channels) -> out [n][H/2][W/2][out_pitch] (first C channels; the others are not written).  H, W even; C, pitch, out_pitch
+ * multiples of 8, pitch >= C, out_pitch >= C; in and out 16-byte aligned and not NULL: anything else is LLA_EINVAL. */
+int lla_rn50_avgpool2_f16(const void *in, int n, int H, int W, int pitch, int C, void *out, int out_pitch, void *stream);
+/* AttentionPool2d's tokens: x [B][49][2048], pos fp32 [50][2048] -> tok [B][50][2048]:
+ * tok[b][0] = mean_j x[b][j] + pos[0], tok[b][1 + j] = x[b][j] + pos[1 + j]. */
+int lla_rn50_attnpool_tokens_f16(const void *x, const float *pos, void *tok, int B, void *stream);
+/* AttentionPool2d's single-query attention, 32 heads of 64: q [B][2048], kv [B * 50][4096] (k | v) -> o [B][2048] =
+ * softmax(q k^T / 8) v per head. */
+int lla_rn50_attnpool_attend_f16(const void *q, const void *kv, void *o, int B, void *stream);
 
 #ifdef __cplusplus
 }

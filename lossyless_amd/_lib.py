@@ -131,6 +131,12 @@ _SIGNATURES = {
     "lla_gemm_resid_layernorm768_workspace_bytes": (_sz, [_i]),
     "lla_gemm_resid_layernorm768": (_i, [_vp, _i, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _vp, _vp]),
     "lla_attention50": (_i, [_vp, _vp, _i, _vp]),
+    "lla_layernorm768_ex": (_i, [_vp, _sz, _vp, _vp, _vp, _i, _i, _vp]),
+    "lla_attention50_ex": (_i, [_vp, _vp, _i, _i, _vp]),
+    "lla_ln_pre_ln1_768": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _vp]),
+    "lla_rn50_avgpool2_f16": (_i, [_vp, _i, _i, _i, _i, _i, _vp, _i, _vp]),
+    "lla_rn50_attnpool_tokens_f16": (_i, [_vp, _vp, _vp, _i, _vp]),
+    "lla_rn50_attnpool_attend_f16": (_i, [_vp, _vp, _vp, _i, _vp]),
 }
 EXPORTS = tuple(sorted(_SIGNATURES))
 

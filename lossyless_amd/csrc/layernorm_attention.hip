@@ -445,6 +445,9 @@ int attention_impl(const void *qkv, void *o, int B, hipStream_t st, Profiler *pr
 
 int ln_pre_ln1_impl(float *x, const float *cls, const float *pos, const float *wpre, const float *bpre, const float *w1,
                     const float *b1, void *h16, int rows, hipStream_t st, Profiler *prof) {
+  if (rows < 0) return LLA_EINVAL;
+  if (rows == 0) return LLA_OK;
+  if (!x || !cls || !pos || !wpre || !bpre || !w1 || !b1 || !h16) return LLA_EINVAL;
   ProfScope scope(prof, st, LLA_PROF_LAYERNORM, (double)rows * kWidth * 10.0);
   ln_pre_ln1_kernel<<<(rows + 3) / 4, 256, 0, st>>>(x, cls, pos, wpre, bpre, w1, b1, reinterpret_cast<f16 *>(h16), rows);
   return check_launch();
@@ -470,6 +473,23 @@ int lla_layernorm768(const float *x, size_t row_stride, const float *w, const fl
 
 int lla_attention50(const void *qkv, void *o, int B, void *stream) {
   return attention_impl(qkv, o, B, as_stream(stream), nullptr);
+}
+
+// The same launches with the walk the tower uses on every second slice (rev = 1: last rows / images first).
+int lla_layernorm768_ex(const float *x, size_t row_stride, const float *w, const float *b, void *y16, int rows, int rev,
+                        void *stream) {
+  if (rev != 0 && rev != 1) return LLA_EINVAL;
+  return layernorm_impl(x, row_stride, w, b, y16, rows, as_stream(stream), nullptr, rev);
+}
+
+int lla_attention50_ex(const void *qkv, void *o, int B, int rev, void *stream) {
+  if (rev != 0 && rev != 1) return LLA_EINVAL;
+  return attention_impl(qkv, o, B, as_stream(stream), nullptr, rev);
+}
+
+int lla_ln_pre_ln1_768(float *x, const float *cls, const float *pos, const float *wpre, const float *bpre, const float *w1,
+                       const float *b1, void *h16, int rows, void *stream) {
+  return ln_pre_ln1_impl(x, cls, pos, wpre, bpre, w1, b1, h16, rows, as_stream(stream), nullptr);
 }
 
 }  // extern "C"

@@ -196,6 +196,23 @@ inline bool direct_conv() { return sw::rn50_direct_conv(); }
 
 inline int grid_for(size_t n) { size_t g = (n + 255) / 256; return (int)(g > 65535 * 16 ? 65535 * 16 : (g ? g : 1)); }
 
+// The pooling kernels' launches, stated once: lla_rn50_forward and the entry points of their own (below) both come through here.
+static int avgpool2_impl(const f16 *in, int n, int H, int W, int pitch, int C, f16 *out, int out_pitch, hipStream_t st) {
+  const size_t n_vec = (size_t)n * (H / 2) * (W / 2) * (C >> 3);
+  avgpool2_kernel<<<grid_for(n_vec), 256, 0, st>>>(in, H, W, pitch, C, out, out_pitch, n_vec);
+  return check_launch();
+}
+
+static int attnpool_tokens_impl(const f16 *x, const float *pos, f16 *tok, int n, hipStream_t st) {
+  attnpool_tokens_kernel<<<n, 256, 0, st>>>(x, pos, tok, n);
+  return check_launch();
+}
+
+static int attnpool_attend_impl(const f16 *q, const f16 *kv, f16 *o, int n, hipStream_t st) {
+  attnpool_attend_kernel<<<(n * kHeads + 3) / 4, 256, 0, st>>>(q, kv, o, n);
+  return check_launch();
+}
+
 // per-image workspace elements (halfs): three activation buffers + identity + im2col
 constexpr size_t kActElems = (size_t)112 * 112 * 128;   // largest activation (stem, pitch 128)
 constexpr size_t kColElems = (size_t)112 * 112 * 320;   // largest im2col matrix (stem conv2 / conv3)
@@ -321,9 +338,7 @@ static int rn50_slices(const void *images_nhwc_f16, int c_begin, int c_end, int 
     return lla_gemm_f16_ex(col, d.kpad, W16(d), B32(d), out, ldo, resid, ldr, (int)rows, d.npad, d.kpad, epi, stream);
   };
   auto pool = [&](const f16 *in, int n, int H, int Wd, int pitch, int C, f16 *out, int out_pitch) -> int {
-    const size_t n_vec = (size_t)n * (H / 2) * (Wd / 2) * (C >> 3);
-    avgpool2_kernel<<<grid_for(n_vec), 256, 0, st>>>(in, H, Wd, pitch, C, out, out_pitch, n_vec);
-    return check_launch();
+    return avgpool2_impl(in, n, H, Wd, pitch, C, out, out_pitch, st);
   };
 
   for (int c0 = c_begin; c0 < B; c0 += chunk) {
@@ -438,20 +453,44 @@ static int rn50_slices(const void *images_nhwc_f16, int c_begin, int c_end, int 
         pitch = c3.npad;
       }
     // attention pool over the 7x7 map (x: [n][49][2048])
-    attnpool_tokens_kernel<<<n, 256, 0, st>>>(x, reinterpret_cast<const float *>(wb + L.pos_off), tok, n);
-    LLA_TRY(check_launch());
+    LLA_TRY(attnpool_tokens_impl(x, reinterpret_cast<const float *>(wb + L.pos_off), tok, n, st));
     LLA_TRY(lla_gemm_f16_ex(tok, kEmbed, wb + L.kv_w, reinterpret_cast<const float *>(wb + L.kv_b), kvb, 2 * kEmbed,
                             nullptr, 0, n * kTokens, 2 * kEmbed, kEmbed, LLA_EPI_F16, stream));
     LLA_TRY(lla_gemm_f16_ex(tok, kTokens * kEmbed, wb + L.q_w, reinterpret_cast<const float *>(wb + L.q_b), qb, kEmbed,
                             nullptr, 0, n, kEmbed, kEmbed, LLA_EPI_F16, stream));
-    attnpool_attend_kernel<<<(n * kHeads + 3) / 4, 256, 0, st>>>(qb, kvb, ob, n);
-    LLA_TRY(check_launch());
+    LLA_TRY(attnpool_attend_impl(qb, kvb, ob, n, st));
     LLA_TRY(lla_gemm_f16_ex(ob, kEmbed, wb + L.c_w, reinterpret_cast<const float *>(wb + L.c_b),
                             reinterpret_cast<f16 *>(z_out) + (size_t)c0 * kOutDim, kOutDim, nullptr, 0, n, kOutDim, kEmbed,
                             LLA_EPI_F16, stream));
   }
 #undef LLA_TRY
   return LLA_OK;
+}
+
+// The tower's pooling kernels on their own: the launches lla_rn50_forward makes (avgpool2_impl, attnpool_*_impl above).
+int lla_rn50_avgpool2_f16(const void *in, int n, int H, int W, int pitch, int C, void *out, int out_pitch, void *stream) {
+  if (n < 0 || H < 0 || W < 0 || (H & 1) || (W & 1) || C <= 0 || (C & 7) || (pitch & 7) || (out_pitch & 7) || pitch < C ||
+      out_pitch < C)
+    return LLA_EINVAL;
+  if (n == 0 || H == 0 || W == 0) return LLA_OK;
+  if (!in || !out || ((uintptr_t)in & 15) || ((uintptr_t)out & 15)) return LLA_EINVAL;
+  return avgpool2_impl(reinterpret_cast<const f16 *>(in), n, H, W, pitch, C, reinterpret_cast<f16 *>(out), out_pitch,
+                       as_stream(stream));
+}
+
+int lla_rn50_attnpool_tokens_f16(const void *x, const float *pos, void *tok, int B, void *stream) {
+  if (B < 0) return LLA_EINVAL;
+  if (B == 0) return LLA_OK;
+  if (!x || !pos || !tok) return LLA_EINVAL;
+  return attnpool_tokens_impl(reinterpret_cast<const f16 *>(x), pos, reinterpret_cast<f16 *>(tok), B, as_stream(stream));
+}
+
+int lla_rn50_attnpool_attend_f16(const void *q, const void *kv, void *o, int B, void *stream) {
+  if (B < 0) return LLA_EINVAL;
+  if (B == 0) return LLA_OK;
+  if (!q || !kv || !o) return LLA_EINVAL;
+  return attnpool_attend_impl(reinterpret_cast<const f16 *>(q), reinterpret_cast<const f16 *>(kv), reinterpret_cast<f16 *>(o), B,
+                              as_stream(stream));
 }
 
 }  // extern "C"

@@ -15,13 +15,13 @@ import pytest
 import torch
 
 from lossyless_amd import _lib
+from tower_kernel_util import GUARD as _GUARD, guarded as _guarded, guards_intact as _guards_intact, worst as _worst
 
 pytestmark = pytest.mark.gpu
 
 _GK_TILE256, _GK_PERSIST1, _GK_PERSIST2, _GK_PP, _GK_Q4, _GK_W8 = 2, 3, 4, 5, 6, 7      # enum GemmKernel (csrc/gemm_plan.h)
 _EPI_LNX = 9
 _H_POISON = 0x7D5A          # an fp16 NaN: no LayerNorm output has these bits
-_GUARD = 4096               # elements in front of and behind every output
 _X_SENTINEL, _H_SENTINEL = -12345.0, -777.0
 
 
@@ -43,16 +43,6 @@ def _randn(g, *shape):
     return torch.randn(*shape, generator=g, device="cuda")
 
 
-def _guarded(n, dtype, sentinel):
-    """A flat buffer of n elements between two guard blocks: (whole buffer, the n elements)."""
-    buf = torch.full((n + 2 * _GUARD,), sentinel, dtype=dtype, device="cuda")
-    return buf, buf[_GUARD:_GUARD + n]
-
-
-def _guards_intact(buf, sentinel):
-    return bool((buf[:_GUARD] == sentinel).all()) and bool((buf[-_GUARD:] == sentinel).all())
-
-
 def _layernorm_f64(x, gamma, beta):
     """Two-pass LayerNorm over 768 in float64 (mean, then the mean of the squared deviations)."""
     xd = x.double()
@@ -67,16 +57,6 @@ def _layernorm_kernel(x, gamma, beta):
     _lib.check(_lib.lib().lla_layernorm768(_lib.ptr(x), 768, _lib.ptr(gamma), _lib.ptr(beta), _lib.ptr(y), rows,
                                            _lib.stream_ptr()), "lla_layernorm768")
     return y
-
-
-def _worst(err, bound, what):
-    """Largest err / bound, printed with the row and column it sits at."""
-    ratio = err / bound
-    flat = int(ratio.argmax())
-    r, c = divmod(flat, ratio.shape[1])
-    worst = float(ratio.reshape(-1)[flat])
-    print(f"{what}: max err/bound {worst:.3f} at row {r} col {c} (err {float(err[r, c]):.3e})")
-    return worst, r, c
 
 
 # ---------------------------------------------------------------------------------------------------------------------
