@@ -519,7 +519,8 @@ int lla_vit_b32_forward_profiled(const void *images, int layout, int B, const vo
  * N % 128 == 0, K % 64 == 0. */
 int lla_gemm_f16(const void *A, const void *W, const float *bias, void *C, int M, int N, int K,
                  int epilogue, void *stream);
-/* The same with explicit row strides (elements; lda % 8 == 0, ldc % 4 == 0; with the ReLU epilogues ldc < N,
+/* The same with explicit row strides (elements; lda % 8 == 0, ldc % 4 == 0 -- ldc % 8 == 0 for an fp16 output that the
+ * 256-column persistent kernels take, whose epilogues store 16 bytes per lane: LLA_EINVAL otherwise; with the ReLU epilogues ldc < N,
  * a multiple of 32, stores only the first ldc columns: narrow convolution outputs keep a narrow pitch) and, for
  * LLA_EPI_ADD_RELU_F16, an fp16 matrix R [M][ldr] added before the ReLU (the identity branch of a
  * ResNet bottleneck).  Used by the RN50-CLIP tower below, where 1x1 convolutions are GEMMs over NHWC

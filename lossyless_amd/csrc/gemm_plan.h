@@ -145,12 +145,20 @@ inline GemmPlan plan_gemm(GemmShape s, int cus, const GemmKnobs &k = GemmKnobs{}
   // the fp32 epilogues address C with 32-bit element offsets (registers are scarce there)
   if ((s.epi == EPI_RESID || s.epi == EPI_PATCH) && ((size_t)s.M + (size_t)s.M / kPatches + 2) * (size_t)s.ldc >= (1ull << 32)) return refuse;
 
+  // The 256-column persistent kernels finish fp16 outputs with ONE 16-byte store per lane at C + m ldc + 8 q (gemm_epilogue_staged,
+  // gemm_epilogue_swap: gemm_common.h): with ldc % 8 == 4 every other row would sit 8 bytes off that store's alignment.  Nothing
+  // here relies on what the memory pipeline does with such a store -- the towers pass multiples of 32 --, so the shape is refused
+  // (the one-tile kernels and the 128-column persistent kernel store 8 bytes per lane and keep taking ldc % 4 == 0).
+  const bool lines_ok = !(fp16_out || relu) || !(s.ldc & 7);
+
   auto one_tile = [&](GemmKernel kernel, int rows) { return GemmPlan{LLA_OK, kernel, rows, ceil_div(s.M, rows) * (s.N / 128)}; };
   auto ping_pong = [&] {
+    if (!lines_ok) return refuse;
     const int tiles_n = s.N / 256, rows = tall_tiles(s.M, tiles_n, cus, k.tall && !s.a_chunk_images) ? 320 : 256;
     return GemmPlan{LLA_OK, GK_PP, rows, balanced_grid(ceil_div(s.M, rows) * tiles_n, cus, k.balanced)};
   };
   auto lock_step = [&](int nj) {   // (N / (128 nj) column tiles; 320 rows exist for nj = 2, K-tiles of 64)
+    if (nj == 2 && !lines_ok) return refuse;
     const int tiles_n = s.N / (128 * nj), rows = tall_tiles(s.M, tiles_n, cus, k.tall && nj == 2 && k.kb == 64) ? 320 : 256;
     const int total = ceil_div(s.M, rows) * tiles_n;
     return GemmPlan{LLA_OK, nj == 2 ? GK_PERSIST2 : GK_PERSIST1, rows, k.persist ? balanced_grid(total, cus, false) : total};

@@ -645,9 +645,11 @@ def _expected_plan(epi, amode, M, N, K, lda, ldc, chunk, cus):
     if epi in (_RESID, _PATCH) and (M + M // 49 + 2) * ldc >= 2 ** 32:
         return refuse
     stored = ldc if ldc < N else N
+    # the 256-column persistent kernels store 16 bytes per lane into an fp16 row: its pitch must keep them aligned
+    lines = ldc % 8 == 0 or epi not in (_F16, _QGELU, _RELU, _ADDRELU)
     if epi in (_RELU, _ADDRELU):
         if amode == _PLAIN and M >= 9000 and N % 256 == 0 and stored == N:
-            return persistent(_GK["persist2"], N // 256, True, False)
+            return persistent(_GK["persist2"], N // 256, True, False) if lines else refuse
         if M > 128 or amode == _CONV3:
             return (0, _GK["tile256"], 256, cdiv(M, 256) * (N // 128))
         return (0, _GK["tile128"], 128, cdiv(M, 128) * (N // 128))
@@ -661,9 +663,9 @@ def _expected_plan(epi, amode, M, N, K, lda, ldc, chunk, cus):
     if epi == _RESID and ldc == N and four_wave:
         return persistent(_GK["q4"], N // 256, False, True)
     if wide3 and K >= 256:
-        return persistent(_GK["pp"], N // 256, not chunk, True)
+        return persistent(_GK["pp"], N // 256, not chunk, True) if lines else refuse
     if wide3:
-        return persistent(_GK["persist2"], N // 256, True, False)
+        return persistent(_GK["persist2"], N // 256, True, False) if lines else refuse
     return persistent(_GK["persist1"], N // 128, False, False)
 
 
@@ -715,6 +717,9 @@ def _plan_cases():
                 cases += [(e, _PLAIN, M, N, K, K, N, 0) for e in (_F16, _QGELU, _RESID, _RELU, _ADDRELU)]
                 cases += [(_PATCH, _NCHW, M, N, K, 0, N, 0), (_RELU, _CONV3, M, N, K, 64, N, 0), (_RELU, _PLAIN, M, N, K, K, 64, 0)]
     cases += [(_PATCH, _NHWC, 49 * B, 768, 3072, 0, 768, 256) for B in (256, 1024, 8704)]      # the image batch in pieces
+    # an output pitch that is a multiple of 4 and not of 8, below and above the persistent kernels' threshold
+    cases += [(e, _PLAIN, M, N, K, K, N + 4, 0) for M in (5000, 9001) for N in (256, 768) for K in (64, 256)
+              for e in (_F16, _QGELU, _RESID, _RELU, _ADDRELU)]
     return cases
 
 
@@ -780,6 +785,10 @@ def test_gemm_selection_refusals():
     assert plan(_F16, _PLAIN, 12800, 3328, 768, 768, 3328, 0)[1] == _GK["pp"]                   # N > 3072
     assert plan(_RESID, _PLAIN, 12837, 768, 768, 768, 768, 0)[1] == _GK["pp"]                   # ragged M
     assert plan(_F16, _PLAIN, 1_000_000, 768, 3072, 3072, 768, 0)[1] == _GK["pp"]               # M lda 2 >= 2^32
+    # fp16 rows of pitch 8 k + 4: not through the 16-byte stores of the 256-column persistent kernels' epilogues
+    assert plan(_ADDRELU, _PLAIN, 9001, 256, 64, 128, 324, 0)[0] == -1 and plan(_ADDRELU, _PLAIN, 9001, 256, 64, 128, 320, 0)[1] == _GK["persist2"]
+    assert plan(_F16, _PLAIN, 9001, 768, 256, 256, 772, 0)[0] == -1 and plan(_RESID, _PLAIN, 9001, 768, 256, 256, 772, 0)[1] == _GK["pp"]
+    assert plan(_ADDRELU, _PLAIN, 8999, 256, 64, 128, 324, 0)[1] == _GK["tile256"] and plan(_F16, _PLAIN, 9001, 256, 64, 64, 260, 0)[1] == _GK["persist1"]
     assert L.lla_gemm_plan(*ok, 0, None, None, None) == -1
 
 
@@ -798,6 +807,116 @@ def test_resid_layernorm_door_decides_from_the_arguments_alone():
     assert call(256, 256, 256, rev=2) == -1 and call(256, 256, 256, rev=-1) == -1
     assert call(256, 256, 256, x=ctypes.c_void_p((1 << 20) + 4)) == -1 and call(256, 256, 256, x=None) == -1
     assert call(256, 256, 256, ws=None) == -1 and call(256, 256, 256, ws=ctypes.c_void_p((1 << 20) + 8)) == -1
+
+
+def _rn50_forward_gemms(n, fuse_ds=True, fused_block=True, direct=True):
+    """(epilogue, operand mode, M, N, K, lda, ldc) of every GEMM that lla_rn50_forward launches for a slice of n images, in its
+    order, with the pitches it passes (rn50_slices, csrc/rn50.hip, restated; the three switches are LLA_RN50_FUSE_DS,
+    LLA_RN50_FUSED_BLOCK and LLA_RN50_DIRECT of the tools/ build, all on in the product).  The direct convolutions and the fused
+    bottleneck kernel are no GEMMs and do not appear."""
+    L, d = _lib.lib(), (ctypes.c_int64 * 8)()
+
+    def desc(fn, i):
+        assert fn(i, d) == 0
+        return [int(v) for v in d][:6]
+
+    convs = [desc(L.lla_rn50_conv_desc, i) for i in range(L.lla_rn50_conv_count())]      # cin, cout, ksize, stride, kpad, npad
+    fused = [desc(L.lla_rn50_fused_desc, s) for s in range(4)]                           # cin, cout, planes, inplanes, kpad, npad
+    opitch = lambda c: c[5] if c[1] % 128 == 0 else (c[1] + 31) // 32 * 32
+    out = []
+
+    def conv(c, H, pitch, epi):
+        cin, cout, ksize, stride, kpad, npad = c
+        ldo = opitch(c) if epi in (_RELU, _ADDRELU) else npad
+        if ksize == 1:
+            out.append((epi, _PLAIN, n * H * H, npad, kpad, pitch, ldo))
+        elif stride == 1 and direct and H % 8 == 0 and ((cin == 32 and cout in (32, 64)) or (cin == 64 and cout == 64)):
+            pass                                                                         # conv_direct.hip
+        elif stride == 1 and (cin % 64 == 0 or cin == 32):
+            out.append((_RELU, _CONV3, n * H * H, npad, kpad, pitch, ldo))               # implicit GEMM
+        elif not (direct and stride == 2 and cin == 3):
+            Ho = (H - 1) // stride + 1
+            out.append((epi, _PLAIN, n * Ho * Ho, npad, kpad, kpad, ldo))                # im2col matrix
+
+    ci = 3
+    conv(convs[0], 224, 3, _RELU)
+    conv(convs[1], 112, opitch(convs[0]), _RELU)
+    block0_fused = fused_block and fuse_ds and direct
+    fuse0 = fuse_ds and direct and not block0_fused
+    if not direct:
+        conv(convs[2], 112, opitch(convs[1]), _RELU)
+    H, pitch = 56, 128 if fuse0 else opitch(convs[2])
+    from lossyless_amd import clip_rn50
+    for s, nb in enumerate(clip_rn50.BLOCKS):
+        for b in range(nb):
+            stride = 2 if s > 0 and b == 0 else 1
+            c1, c2, c3 = convs[ci:ci + 3]
+            ci += 3
+            if s == 0 and b == 0 and block0_fused:
+                ci += 1
+                pitch = c3[5]
+                continue
+            if s == 0 and b > 0 and fused_block and pitch == c3[5]:
+                continue
+            conv(c1, H, pitch, _RELU)
+            Ho = H // stride
+            if b == 0 and fuse_ds and (s > 0 or fuse0):
+                ci += 1
+                if s > 0:
+                    conv(c2, H, opitch(c1), _RELU)
+                out.append((_RELU, _PLAIN, n * Ho * Ho, fused[s][5], fused[s][4], fused[s][0], c3[5]))
+                H, pitch = Ho, c3[5]
+                continue
+            conv(c2, H, opitch(c1), _RELU)
+            if b == 0:
+                conv(convs[ci], Ho, pitch, _F16)
+                ci += 1
+            conv(c3, Ho, opitch(c2), _ADDRELU)
+            H, pitch = Ho, c3[5]
+    assert ci == len(convs) and (H, pitch) == (7, 2048)
+    out += [(_F16, _PLAIN, 50 * n, 4096, 2048, 2048, 4096), (_F16, _PLAIN, n, 2048, 2048, 50 * 2048, 2048),      # K | V, query
+            (_F16, _PLAIN, n, 1024, 2048, 2048, 1024)]                                                          # output projection
+    return out
+
+
+def test_every_gemm_path_of_the_rn50_tower_has_a_kernel_level_case():
+    """Every (kernel, epilogue, tile rows) that the RN50 tower's GEMMs reach on 256 CUs at chunks of 4, 64 and 192 images -- the
+    product's calls and those of its A/B switches -- is one that a kernel-level float64 test runs: a case of
+    test_gpu_rn50_gemms.py (which asserts its kernel and tile rows itself) or of test_gpu_rn50.py's two GEMM tables.  A change of
+    the selection that sends the tower somewhere no such test goes fails here.  (No GEMM is launched.)"""
+    import test_gpu_rn50
+    import test_gpu_rn50_gemms as new
+    L = _lib.lib()
+    plan = lambda epi, amode, M, N, K, lda, ldc: _plan_answers(L, [(epi, amode, M, N, K, lda, ldc, 0)], (256,))[0]
+    covered = set()
+    for name, (M, N, K, lda, ldc, ldr, coff, epi, kernel, rows) in new.CASES.items():
+        assert plan(epi, _PLAIN, M, N, K, lda, ldc)[:3] == (0, kernel, rows), name
+        covered.add((kernel, epi, rows))
+    for test in (test_gpu_rn50.test_gemm_ex_strided_relu_and_add_relu, test_gpu_rn50.test_gemm_ex_narrow_output_pitch):
+        table = [m for m in test.pytestmark if m.name == "parametrize"]
+        assert len(table) == 1 and table[0].args[0] == "M,N,K,lda,ldc,epi"
+        for M, N, K, lda, ldc, epi in table[0].args[1]:
+            rc, kernel, rows, _ = plan(epi, _PLAIN, M, N, K, lda, ldc)
+            assert rc == 0
+            covered.add((kernel, epi, rows))
+    reached = {}
+    for n in (4, 64, 192):
+        for switches in ((True, True, True), (False, True, True), (True, False, True), (True, True, False), (False, False, False)):
+            calls = _rn50_forward_gemms(n, *switches)
+            if switches == (True, True, True):       # the 13 bottlenecks behind layer1: 3 GEMMs each; the attention pool's 3
+                assert len(calls) == 3 * 13 + 3
+            for epi, amode, M, N, K, lda, ldc in calls:
+                rc, kernel, rows, _ = plan(epi, amode, M, N, K, lda, ldc)
+                assert rc == 0, (n, switches, epi, amode, M, N, K, lda, ldc)
+                if amode == _CONV3:                  # (test_implicit_conv3x3_relu_against_float64: always this kernel)
+                    assert kernel == _GK["tile256"]
+                else:
+                    reached.setdefault((kernel, epi, rows), (n, switches, M, N, K, lda, ldc))
+    missing = {t: reached[t] for t in reached if t not in covered}
+    assert not missing, missing
+    # what the product itself adds to the one-tile kernels at these chunks
+    product = {plan(*c)[1:3] + (c[0],) for n in (4, 64, 192) for c in _rn50_forward_gemms(n) if c[1] == _PLAIN}
+    assert {(_GK["persist2"], 256, _RELU), (_GK["persist2"], 320, _ADDRELU), (_GK["pp"], 320, _F16)} <= product
 
 
 _PLAN_CHILD = r"""
