@@ -1,11 +1,14 @@
 """torch.hub entry points with the reference's factory names and return shape
 (reference hubconf.py:22-52): ``clip_compressor_b005``, ``clip_compressor_b001`` and
-``clip_compressor_b01``, each ``(device=..., **kwargs) -> (compressor, transform)``.
+``clip_compressor_b01``, each ``(device=..., **kwargs) -> (compressor, transform)``; ``clip_compressor(state_dict)`` and
+``clip_hyperprior_compressor(state_dict)`` take a rate point of the caller's.
 
 The reference fetches one state-dict per rate point from its GitHub release
 (hubconf.py:15,23-26).  Here the three state-dicts ship inside the package with their integer
 coding tables already frozen (``lossyless_amd/assets``), so nothing is
 fetched; the release URL is only a fallback for a missing asset.
+``clip_compressor(state_dict)`` takes any other factorized rate point: one trained here with
+``lossyless_amd.BottleneckFit`` on frozen features, or a ``main.py`` checkpoint's rate estimator.
 """
 dependencies = ["torch", "numpy"]
 
@@ -75,4 +78,20 @@ def clip_hyperprior_compressor(state_dict, device=_ON, **kwargs):
     the GPU (``is_cpu=True`` raises: the coding-table rows come from an MLP evaluated on the fp32 matrix cores).
     """
     model = _HyperpriorCompressor(pretrained_state_dict=state_dict, device=device, **kwargs)
+    return model, model.preprocess
+
+
+def clip_compressor(state_dict, device=_ON, **kwargs):
+    """CLIP ViT-B/32 + entropy bottleneck compressor at a rate point of the caller's: the factorized sibling of
+    ``clip_hyperprior_compressor``.
+
+    state_dict   : what the reference's ``HRateFactorizedPrior`` saves -- ``lossyless_amd.BottleneckFit(beta).fit(Z)
+                   .state_dict()``, or a ``main.py`` checkpoint's rate estimator -- as a dict or a path to it (the key set of
+                   the shipped ``lossyless_amd/assets/*_factorized_rate.pt``).
+    device, clip_weights, gpu_preprocess, other kwargs : as for ``clip_compressor_b005``; forwarded to
+                   ``lossyless_amd.ClipCompressor``
+
+    Returns ``(compressor, transform)`` with the surface of the three shipped rate points.
+    """
+    model = _Compressor(pretrained_state_dict=state_dict, device=device, **kwargs)
     return model, model.preprocess

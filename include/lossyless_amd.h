@@ -797,6 +797,50 @@ int lla_bn_relu_dropout_fwd(const float *a, int lda, const float *gamma, const f
 int lla_bn_bwd(const float *g, int ldg, const float *a, int lda, const float *gamma, const float *mean, const float *rstd,
                double p, float *dgamma, float *dbeta, float *da, int ldda, int B, int N, void *stream);
 
+/* ---- Training pass of the factorized rate estimator over frozen features (csrc/eb_train.hip): what autograd runs for
+ * HRateFactorizedPrior in training mode (lossyless/rates.py:534-554; compressai 1.1.5 EntropyBottleneck with filters (3, 3, 3, 3),
+ * uniform noise in place of rounding) and the lossy_Z distortion with p_norm 1 (lossyless/distortions.py:408-449), as
+ * lossyless/learnable_compressors.py:241-275 combines them.  Conventions of the blocks above: LLA_EINVAL before any device call,
+ * a zero-row call LLA_OK with no launch, no floating-point atomics, the order of every sum a function of (B, C) alone (the same
+ * inputs give the same bits).  fp32 arithmetic with expf / logf / log1pf / expm1f / tanhf (no fast variants), products and sums
+ * rounded separately; sums over rows in fp32 per walker (at most ceil(B / W) terms), over walkers and channels in double.
+ *
+ * `params` [58][C] fp32, params[k * C + c] for channel c, k in the order: _matrix0 (3: [j][0]), _matrix1, _matrix2, _matrix3 (9
+ * each, row-major [out j][in i]), _matrix4 (3: [0][i]), _bias0 .. _bias3 (3 each), _bias4 (1), _factor0 .. _factor3 (3 each).
+ * `scaling`, `biasing` [C].  With s = scaling[c], b = biasing[c], for row i and channel c:
+ *   y = (z_ic + b) exp(s);  v = y + u_ic;  L(x): x <- softplus(M_k) x + B_k, then x <- x + tanh(F_k) tanh(x) for k < 4
+ *   lower = L(v - .5), upper = L(v + .5), sgn = -sign(lower + upper) (a constant of the backward)
+ *   lik = max(|sigmoid(sgn upper) - sigmoid(sgn lower)|, 1e-9), the gradient passing through the bound (compressai's LowerBound
+ *   blocks only a gradient that would lower a value at the bound; d(-log lik)/d lik < 0)
+ *   rate_i = -sum_c log lik_ic (nats);  dist_i = sum_c |u_ic exp(-s) + 1e-6|  (= nn.PairwiseDistance(p=1) of z_hat = v / exp(s) - b
+ *   and z: z_hat - z = u exp(-s) in closed form, so d dist / d b = 0 and d dist / d s = -sign(.) u exp(-s))
+ * One formula each: softplus(m) = max(m, 0) + log1p(exp(-|m|)) (derivative sigmoid(m) = 1 / (1 + exp(-m)) evaluated from
+ * exp(-|m|)); the sigmoid difference, for a = sgn upper and b = sgn lower (a + b <= 0), is
+ * -exp(max(a, b)) expm1(-|a - b|) / ((1 + exp(a)) (1 + exp(b))) signed as a - b when both are <= 0 (two tail values do not cancel)
+ * and sigmoid(a) - sigmoid(b) otherwise; sigmoid'(t) = e / (1 + e)^2 with e = exp(-|t|); the rate term is -logf of the BOUNDED
+ * likelihood.
+ * Noise: Philox4x32-10 as lla_bn_relu_dropout_fwd, key (seed & 0xffffffff, seed >> 32), counter (e & 0xffffffff, e >> 32, step,
+ * 0x6e6f6973), e = (i C + c) / 4, output word c % 4: u = (float)(word >> 8) 2^-24 - 0.5f in [-0.5, 0.5): a function of
+ * (seed, step, i, c) alone.  C % 4 == 0.
+ * z [B][ldz] fp16 or fp32 (LLA_Z_F16 / LLA_Z_F32), ldz >= C in elements, aligned to its element; columns C .. ldz-1 are not read.
+ * grads [2][60 C] fp32: grads[0] the gradient of sum_i dist_i, grads[1] of sum_i rate_i, each in the layout of the main
+ * optimiser's buffer -- scaling [C], biasing [C], then the 58 C of `params` (so scaling, biasing and params may be three
+ * pieces of ONE buffer that lla_adamw_step updates); the caller forms (grads[0] + beta grads[1]) / B.  out_sums [2] doubles:
+ * sum_i dist_i, sum_i rate_i.  workspace: lla_eb_train_pass_workspace_bytes(B, C) bytes (0 for a refused shape), contents
+ * irrelevant.  params, scaling, biasing, grads, workspace 16-byte aligned, out_sums 8-byte. */
+size_t lla_eb_train_pass_workspace_bytes(int B, int C);
+int lla_eb_train_pass(const void *z, int z_dtype, size_t ldz, int B, int C, const float *params, const float *scaling,
+                      const float *biasing, uint64_t seed, uint32_t step, float *grads, double *out_sums, void *workspace,
+                      void *stream);
+/* The auxiliary loss of the same module (compressai EntropyBottleneck.loss(); lossyless/learnable_compressors.py:293-295) and
+ * its gradient with respect to the quantiles, the network held constant:
+ *   aux = sum_c sum_k |L_c(q_c[k]) - target[k]|;   grad_q[c][k] = sign(L_c(q_c[k]) - target[k]) dL_c/dx (q_c[k])
+ * with the device functions of the pass (dL/dx is the input derivative the pass needs for scaling and biasing).  params as
+ * above; quantiles, grad_q [C][3] fp32 (16-byte aligned), target [3] fp32; *out_loss a double, the channels' losses added in
+ * channel order (runs of 8 channels, then the runs).  C % 4 == 0. */
+int lla_eb_aux_grad(const float *params, const float *quantiles, const float *target, int C, float *grad_q, double *out_loss,
+                    void *stream);
+
 /* out[n][H][W][ldc] (first cout channels) = relu(conv3x3(in, stride 1, pad 1) + bias) as an IMPLICIT GEMM:
  * `in` is NHWC fp16 [n][H][W][pitch] (first cin channels used; cin % 64 == 0, or cin == 32), weights fp16
  * [cout][K] with K = 9 cin rounded up to a multiple of 64 (zero padded) in the order (kh, kw, c), bias fp32

@@ -116,6 +116,9 @@ _SIGNATURES = {
     "lla_bn_relu_dropout_fwd": (_i, [_vp, _i, _vp, _vp, _vp, _i, _vp, _vp, _vp, _vp, _i, _i] + [ctypes.c_double] * 3
                                 + [ctypes.c_uint64, ctypes.c_uint32, ctypes.c_uint32, _vp]),
     "lla_bn_bwd": (_i, [_vp, _i, _vp, _i, _vp, _vp, _vp, ctypes.c_double, _vp, _vp, _vp, _i, _i, _i, _vp]),
+    "lla_eb_train_pass_workspace_bytes": (_sz, [_i, _i]),
+    "lla_eb_train_pass": (_i, [_vp, _i, _sz, _i, _i, _vp, _vp, _vp, ctypes.c_uint64, ctypes.c_uint32, _vp, _vp, _vp, _vp]),
+    "lla_eb_aux_grad": (_i, [_vp, _vp, _vp, _i, _vp, _vp, _vp]),
     "lla_conv3x3_relu_f16": (_i, [_vp, _i, _i, _i, _i, _i, _vp, _vp, _vp, _i, _i, _vp]),
     "lla_conv3x3_direct_relu_f16": (_i, [_vp, _i, _i, _i, _i, _i, _vp, _i, _vp, _vp, _i, _i, _i, _vp]),
     "lla_conv3x3_rgb_s2_relu_f16": (_i, [_vp, _i, _i, _i, _vp, _i, _vp, _vp, _i, _vp]),

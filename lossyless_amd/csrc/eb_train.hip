@@ -1,0 +1,379 @@
+// Training pass of the factorized rate estimator (HRateFactorizedPrior with a frozen encoder), forward and backward, on gfx950.
+//
+// Stands in for what autograd runs for lossyless/rates.py:534-554 in training mode (compressai 1.1.5 EntropyBottleneck with
+// uniform noise in place of rounding, filters (3, 3, 3, 3)) plus the lossy_Z distortion with p_norm 1
+// (lossyless/distortions.py:408-449) over a matrix of frozen features.  include/lossyless_amd.h states the mathematics and
+// the buffer layouts; BottleneckFit (bottleneck_fit.py) drives the kernels and carries the float64 twin of every formula here.
+//
+//   lla_eb_train_pass   sum_i dist_i, sum_i rate_i and their gradients with respect to scaling, biasing and the 58 numbers of
+//                       each channel's cumulative network: eb_pass_kernel (forward + backward) then eb_pass_finish_kernel
+//   lla_eb_aux_grad     the auxiliary (quantile) loss and its gradient with respect to the quantiles: eb_aux_kernel
+//
+// Arrangement of the pass: a LANE owns a channel, a wave owns 64 adjacent channels (a row's load is one contiguous line of 256
+// or 128 bytes), one wave per workgroup.  Walker w of W walks the rows w, w + W, ...  The channel's parameters -- as the network
+// uses them: softplus(matrix), bias, tanh(factor) -- and the 63 accumulators (58 network gradients, d rate / d scaling,
+// d rate / d biasing, d dist / d scaling, the channel's dist and rate sums) stay in registers for the whole walk; nothing crosses
+// lanes.  The chain rule through softplus and tanh of the parameters is applied once, after the walk.  Each walker stores its
+// 63 partial sums; the finish kernel adds the walkers of every (quantity, channel) in walker order in double and rounds once, and
+// its last workgroup adds the channels' dist and rate sums in a fixed order in double.  W is a function of (B, C) alone
+// (eb_walkers), so the same inputs give the same bits.  No atomics, no LDS in the pass kernel.
+//
+// Resources (hipcc -Rpass-analysis=kernel-resource-usage, gfx950): DESIGN.md 5.19 records the register, scratch and occupancy
+// figures of the three kernels.
+#include "common.h"
+
+#include <cmath>
+
+namespace lla {
+namespace {
+
+constexpr int kNet = 58;                     // numbers of one channel's cumulative network: 33 matrix, 13 bias, 12 factor
+constexpr int kMat = 33, kBias = 13, kFac = 12;
+static_assert(kMat + kBias + kFac == kNet, "layout of one channel");
+constexpr int kMain = 60;                    // ... of the main optimiser's buffer per channel: scaling, biasing, the network
+constexpr int kPart = 63;                    // partial sums a walker stores per channel
+constexpr int kRowsPerWalker = 8;            // rows that amortise a walker's parameter set-up
+constexpr int kWaveSlots = 2048;             // 256 CUs x 4 SIMDs x 2 waves (the pass kernel's occupancy)
+constexpr uint32_t kNoiseTag = 0x6e6f6973u;  // fourth counter word of the noise stream ("nois")
+constexpr float kLikBound = 1e-9f;
+
+// Philox4x32-10 (Salmon et al., SC'11), as csrc/batchnorm.hip draws its dropout masks; word `pick` of the four.
+__device__ __forceinline__ uint32_t philox_word(uint32_t c0, uint32_t c1, uint32_t c2, uint32_t c3, uint32_t k0, uint32_t k1,
+                                                int pick) {
+#pragma unroll
+  for (int round = 0; round < 10; ++round) {
+    const uint64_t p0 = (uint64_t)0xD2511F53u * c0, p1 = (uint64_t)0xCD9E8D57u * c2;
+    const uint32_t n0 = (uint32_t)(p1 >> 32) ^ c1 ^ k0, n2 = (uint32_t)(p0 >> 32) ^ c3 ^ k1;
+    c1 = (uint32_t)p1, c3 = (uint32_t)p0, c0 = n0, c2 = n2;
+    k0 += 0x9E3779B9u, k1 += 0xBB67AE85u;
+  }
+  return pick == 0 ? c0 : pick == 1 ? c1 : pick == 2 ? c2 : c3;
+}
+
+// softplus(m) = max(m, 0) + log1p(exp(-|m|)) and its derivative sigmoid(m) = 1 / (1 + exp(-m)) from the same exponential
+__device__ __forceinline__ float softplus_f(float m) { return fmaxf(m, 0.f) + log1pf(expf(-fabsf(m))); }
+__device__ __forceinline__ float sigmoid_f(float t) {
+  const float e = expf(-fabsf(t));
+  return t <= 0.f ? e / (1.f + e) : 1.f / (1.f + e);
+}
+
+// One channel's cumulative network as its forward uses it.  Offsets into sp: layer 0 at 0 (3 x 1), layers 1..3 at 3 + 9 (k - 1)
+// (3 x 3, row-major [out][in]), layer 4 at 30 (1 x 3); into b: 3 k; into tf: 3 k.
+struct EbNet {
+  float sp[kMat], b[kBias], tf[kFac];
+};
+// What the backward needs of one evaluation: h[k] the output of layer k (the input of layer k + 1), t[k] = tanh of its
+// pre-activation, x the input.
+struct EbAct {
+  float x, h[4][3], t[4][3];
+};
+struct EbAcc {
+  float sp[kMat], b[kBias], tf[kFac];
+};
+
+// params[k * C + c], k = 0 .. 57 in the order of the header: the lanes of a wave read adjacent words
+__device__ __forceinline__ void eb_load(EbNet &n, const float *__restrict__ params, int C, int c) {
+#pragma unroll
+  for (int k = 0; k < kMat; ++k) n.sp[k] = softplus_f(params[(size_t)k * C + c]);
+#pragma unroll
+  for (int k = 0; k < kBias; ++k) n.b[k] = params[(size_t)(kMat + k) * C + c];
+#pragma unroll
+  for (int k = 0; k < kFac; ++k) n.tf[k] = tanhf(params[(size_t)(kMat + kBias + k) * C + c]);
+}
+
+// L(x): x <- softplus(M_k) x + B_k, then x <- x + tanh(F_k) tanh(x) for k < 4.  Every row sum is ((m0 h0 + m1 h1) + m2 h2) + b.
+__device__ __forceinline__ float eb_forward(const EbNet &n, float x, EbAct &a) {
+  a.x = x;
+#pragma unroll
+  for (int j = 0; j < 3; ++j) {
+    const float pre = n.sp[j] * x + n.b[j];
+    a.t[0][j] = tanhf(pre);
+    a.h[0][j] = pre + n.tf[j] * a.t[0][j];
+  }
+#pragma unroll
+  for (int k = 1; k < 4; ++k) {
+#pragma unroll
+    for (int j = 0; j < 3; ++j) {
+      const float *m = &n.sp[3 + 9 * (k - 1) + 3 * j];
+      const float pre = ((m[0] * a.h[k - 1][0] + m[1] * a.h[k - 1][1]) + m[2] * a.h[k - 1][2]) + n.b[3 * k + j];
+      a.t[k][j] = tanhf(pre);
+      a.h[k][j] = pre + n.tf[3 * k + j] * a.t[k][j];
+    }
+  }
+  return ((n.sp[30] * a.h[3][0] + n.sp[31] * a.h[3][1]) + n.sp[32] * a.h[3][2]) + n.b[12];
+}
+
+// Reverse pass of one evaluation seeded with g = d loss / d L(x): returns g dL/dx and, with ACC, adds g times the derivatives
+// with respect to softplus(matrix), bias and tanh(factor) to `acc`.
+template <bool ACC>
+__device__ __forceinline__ float eb_backward(const EbNet &n, const EbAct &a, float g, EbAcc &acc) {
+  float dh[3];
+#pragma unroll
+  for (int i = 0; i < 3; ++i) {
+    dh[i] = g * n.sp[30 + i];
+    if (ACC) acc.sp[30 + i] += g * a.h[3][i];
+  }
+  if (ACC) acc.b[12] += g;
+#pragma unroll
+  for (int k = 3; k >= 1; --k) {
+    float da[3];
+#pragma unroll
+    for (int j = 0; j < 3; ++j) {
+      const float t = a.t[k][j];
+      da[j] = dh[j] * (1.f + n.tf[3 * k + j] * (1.f - t * t));
+      if (ACC) {
+        acc.tf[3 * k + j] += dh[j] * t;
+        acc.b[3 * k + j] += da[j];
+#pragma unroll
+        for (int i = 0; i < 3; ++i) acc.sp[3 + 9 * (k - 1) + 3 * j + i] += da[j] * a.h[k - 1][i];
+      }
+    }
+#pragma unroll
+    for (int i = 0; i < 3; ++i) {
+      const float *m = &n.sp[3 + 9 * (k - 1)];
+      dh[i] = (m[i] * da[0] + m[3 + i] * da[1]) + m[6 + i] * da[2];
+    }
+  }
+  float dx = 0.f;
+#pragma unroll
+  for (int j = 0; j < 3; ++j) {
+    const float t = a.t[0][j];
+    const float da = dh[j] * (1.f + n.tf[j] * (1.f - t * t));
+    if (ACC) {
+      acc.tf[j] += dh[j] * t;
+      acc.b[j] += da;
+      acc.sp[j] += da * a.x;
+    }
+    dx += n.sp[j] * da;
+  }
+  return dx;
+}
+
+// lik = |sigmoid(a) - sigmoid(b)| for a = sgn upper, b = sgn lower (a + b <= 0: at most one is positive), signed as the
+// difference.  Both in the lower tail: (exp(a) - exp(b)) / ((1 + exp(a)) (1 + exp(b))) with the numerator as
+// -exp(max) expm1(-|a - b|) -- no cancellation between two nearly equal tail values; otherwise the plain difference.
+__device__ __forceinline__ float sigmoid_diff(float a, float b) {
+  const float ea = expf(-fabsf(a)), eb = expf(-fabsf(b));
+  if (a <= 0.f && b <= 0.f) {
+    const float d = a - b;
+    const float num = d >= 0.f ? -(ea * expm1f(-d)) : eb * expm1f(d);   // expm1 of a non-positive number: no overflow
+    return num / ((1.f + ea) * (1.f + eb));
+  }
+  const float sa = a <= 0.f ? ea / (1.f + ea) : 1.f / (1.f + ea), sb = b <= 0.f ? eb / (1.f + eb) : 1.f / (1.f + eb);
+  return sa - sb;
+}
+// sigmoid'(t) = e / (1 + e)^2, e = exp(-|t|)
+__device__ __forceinline__ float sigmoid_slope(float t) {
+  const float e = expf(-fabsf(t));
+  return e / ((1.f + e) * (1.f + e));
+}
+__device__ __forceinline__ float sign_f(float x) { return x > 0.f ? 1.f : x < 0.f ? -1.f : 0.f; }
+
+template <typename T>
+__device__ __forceinline__ float load_z(const void *z, size_t at) {
+  return (float)reinterpret_cast<const T *>(z)[at];
+}
+
+struct EbPass {
+  uint32_t k0, k1, step;
+  int B, C, W;
+};
+
+template <typename T>
+__global__ __launch_bounds__(64) void eb_pass_kernel(const void *__restrict__ z, size_t ldz, const float *__restrict__ params,
+                                                     const float *__restrict__ scaling, const float *__restrict__ biasing,
+                                                     float *__restrict__ part, EbPass f) {
+  const int c = blockIdx.x * kWave + threadIdx.x, w = blockIdx.y;
+  if (c >= f.C) return;                      // (nothing crosses lanes: a lane beyond C has no part in the walk)
+  EbNet n;
+  eb_load(n, params, f.C, c);
+  const float s = scaling[c], bz = biasing[c];
+  const float es = expf(s), ems = expf(-s);
+  EbAcc acc;
+#pragma unroll
+  for (int k = 0; k < kMat; ++k) acc.sp[k] = 0.f;
+#pragma unroll
+  for (int k = 0; k < kBias; ++k) acc.b[k] = 0.f;
+#pragma unroll
+  for (int k = 0; k < kFac; ++k) acc.tf[k] = 0.f;
+  float g_rate_s = 0.f, g_rate_b = 0.f, g_dist_s = 0.f, sum_dist = 0.f, sum_rate = 0.f;
+  float zn = w < f.B ? load_z<T>(z, (size_t)w * ldz + c) : 0.f;
+  for (int i = w; i < f.B; i += f.W) {
+    const float zi = zn;
+    if (i + f.W < f.B) zn = load_z<T>(z, (size_t)(i + f.W) * ldz + c);   // the next row's load flies over this row's arithmetic
+    const uint64_t e = ((uint64_t)i * (uint64_t)f.C + (uint64_t)c) >> 2;
+    const uint32_t word = philox_word((uint32_t)e, (uint32_t)(e >> 32), f.step, kNoiseTag, f.k0, f.k1, c & 3);
+    const float u = (float)(word >> 8) * 0x1p-24f - 0.5f;
+    const float y = (zi + bz) * es;
+    const float v = y + u;
+    EbAct lo, up;
+    const float lower = eb_forward(n, v - 0.5f, lo), upper = eb_forward(n, v + 0.5f, up);
+    const float sgn = -sign_f(lower + upper);
+    const float a = sgn * upper, b = sgn * lower;
+    const float diff = sigmoid_diff(a, b);
+    const float lik = fmaxf(fabsf(diff), kLikBound);
+    sum_rate += -logf(lik);
+    // d(-log lik) / d lik = -1 / lik through the bound (header); |.| and the constant sign give the seeds of the two evaluations
+    const float gl = -1.f / lik * sign_f(diff) * sgn;
+    const float dv = eb_backward<true>(n, up, gl * sigmoid_slope(a), acc) + eb_backward<true>(n, lo, -gl * sigmoid_slope(b), acc);
+    g_rate_s += dv * y;
+    g_rate_b += dv * es;
+    // dist: z_hat - z = u exp(-s) (closed form of the header), + the 1e-6 of nn.PairwiseDistance
+    const float r = u * ems, d = r + 1e-6f;
+    sum_dist += fabsf(d);
+    g_dist_s += -sign_f(d) * r;
+  }
+  // chain rule through the parameters' own images: d softplus(m) = sigmoid(m), d tanh(f) = 1 - tanh(f)^2
+  float *out = part + (size_t)w * kPart * f.C + c;
+  out[0] = g_dist_s;
+  out[(size_t)1 * f.C] = g_rate_s;
+  out[(size_t)2 * f.C] = g_rate_b;
+#pragma unroll
+  for (int k = 0; k < kMat; ++k) out[(size_t)(3 + k) * f.C] = acc.sp[k] * sigmoid_f(params[(size_t)k * f.C + c]);
+#pragma unroll
+  for (int k = 0; k < kBias; ++k) out[(size_t)(3 + kMat + k) * f.C] = acc.b[k];
+#pragma unroll
+  for (int k = 0; k < kFac; ++k) out[(size_t)(3 + kMat + kBias + k) * f.C] = acc.tf[k] * (1.f - n.tf[k] * n.tf[k]);
+  out[(size_t)61 * f.C] = sum_dist;
+  out[(size_t)62 * f.C] = sum_rate;
+}
+
+// grads[0][..] (dist) and grads[1][..] (rate), each 60 C: every element the sum of its W partials in walker order, in double,
+// rounded once (the dist half is zero outside scaling).  The LAST workgroup adds the channels' dist and rate sums instead:
+// thread t adds the channels t, t + 256, ... (each the double sum of its walkers, in walker order) in ascending order, and
+// thread 0 adds the 256 thread sums in thread order.
+__global__ __launch_bounds__(256) void eb_pass_finish_kernel(const float *__restrict__ part, float *__restrict__ grads,
+                                                             double *__restrict__ out_sums, int C, int W) {
+  __shared__ double red[2][256];
+  const size_t slab = (size_t)kPart * C;
+  if (blockIdx.x + 1 == gridDim.x) {
+    double tot[2] = {0.0, 0.0};
+    for (int c = threadIdx.x; c < C; c += 256) {
+#pragma unroll
+      for (int q = 0; q < 2; ++q) {
+        double col = 0.0;
+        for (int w = 0; w < W; ++w) col += (double)part[w * slab + (size_t)(61 + q) * C + c];
+        tot[q] += col;
+      }
+    }
+    red[0][threadIdx.x] = tot[0], red[1][threadIdx.x] = tot[1];
+    __syncthreads();
+    if (threadIdx.x < 2) {
+      double sum = 0.0;
+      for (int t = 0; t < 256; ++t) sum += red[threadIdx.x][t];
+      out_sums[threadIdx.x] = sum;
+    }
+    return;
+  }
+  const size_t at = (size_t)blockIdx.x * 256 + threadIdx.x;      // element of the main layout: [60][C]
+  if (at >= (size_t)kMain * C) return;
+  const int k = (int)(at / C), c = (int)(at % C);
+  // main layout row k: 0 scaling, 1 biasing, 2 + j network -> partial rows: rate (1, 2, 3 + j), dist (0 for scaling)
+  const int rate_row = k == 0 ? 1 : k == 1 ? 2 : k + 1;
+  double rate = 0.0, dist = 0.0;
+  for (int w = 0; w < W; ++w) rate += (double)part[w * slab + (size_t)rate_row * C + c];
+  if (k == 0)
+    for (int w = 0; w < W; ++w) dist += (double)part[w * slab + c];
+  grads[at] = (float)dist;
+  grads[(size_t)kMain * C + at] = (float)rate;
+}
+
+// aux = sum_c sum_k |L_c(q_c[k]) - target[k]| and d aux / d q_c[k] = sign(.) dL_c/dx (q_c[k]), the network held constant.
+// ONE workgroup of 512 threads; a thread owns the channels t, t + 512, ...  The channels' losses are added in channel
+// order in double: runs of 8 adjacent channels by the lanes of the first wave, then the 64 runs in order by lane 0, chunk
+// of 512 channels after chunk.
+__global__ __launch_bounds__(512) void eb_aux_kernel(const float *__restrict__ params, const float *__restrict__ quantiles,
+                                                      const float *__restrict__ target, float *__restrict__ grad_q,
+                                                      double *__restrict__ out_loss, int C) {
+  __shared__ double loss[512];
+  __shared__ double runs[64];
+  double total = 0.0;
+  const float tg[3] = {target[0], target[1], target[2]};
+  for (int c0 = 0; c0 < C; c0 += 512) {
+    const int c = c0 + threadIdx.x;
+    double mine = 0.0;
+    if (c < C) {
+      EbNet n;
+      eb_load(n, params, C, c);
+      EbAcc none;
+#pragma unroll
+      for (int k = 0; k < 3; ++k) {
+        EbAct a;
+        const float r = eb_forward(n, quantiles[(size_t)3 * c + k], a) - tg[k];
+        const float sg = sign_f(r);
+        grad_q[(size_t)3 * c + k] = sg == 0.f ? 0.f : sg * eb_backward<false>(n, a, 1.f, none);
+        mine += (double)fabsf(r);
+      }
+    }
+    loss[threadIdx.x] = mine;
+    __syncthreads();
+    if (threadIdx.x < 64) {
+      double run = 0.0;
+      for (int j = 0; j < 8; ++j) run += loss[8 * threadIdx.x + j];
+      runs[threadIdx.x] = run;
+    }
+    __syncthreads();
+    if (threadIdx.x == 0)
+      for (int j = 0; j < 64; ++j) total += runs[j];
+    __syncthreads();
+  }
+  if (threadIdx.x == 0) *out_loss = total;
+}
+
+bool aligned16(const void *q) { return ((uintptr_t)q & 15) == 0; }
+
+// walkers of a pass: enough rows each to amortise the parameter set-up, no more waves than the chip holds at once
+int eb_walkers(int B, int C) {
+  const int groups = (C + kWave - 1) / kWave;
+  const int most = kWaveSlots / groups > 1 ? kWaveSlots / groups : 1;
+  const int want = (B + kRowsPerWalker - 1) / kRowsPerWalker;
+  return want < 1 ? 1 : want < most ? want : most;
+}
+
+bool eb_shape_ok(int B, int C) { return B >= 0 && C > 0 && !(C & 3) && C <= (1 << 20); }
+
+}  // namespace
+}  // namespace lla
+
+using namespace lla;
+
+extern "C" size_t lla_eb_train_pass_workspace_bytes(int B, int C) {
+  if (!eb_shape_ok(B, C) || B == 0) return 0;
+  return (size_t)eb_walkers(B, C) * kPart * (size_t)C * sizeof(float);
+}
+
+extern "C" int lla_eb_train_pass(const void *z, int z_dtype, size_t ldz, int B, int C, const float *params,
+                                 const float *scaling, const float *biasing, uint64_t seed, uint32_t step, float *grads,
+                                 double *out_sums, void *workspace, void *stream) {
+  if (!eb_shape_ok(B, C) || (z_dtype != LLA_Z_F16 && z_dtype != LLA_Z_F32) || ldz < (size_t)C) return LLA_EINVAL;
+  if (B == 0) return LLA_OK;
+  if (!z || !params || !scaling || !biasing || !grads || !out_sums || !workspace) return LLA_EINVAL;
+  const size_t zb = z_dtype == LLA_Z_F16 ? 2 : 4;
+  if (((uintptr_t)z & (zb - 1)) || !aligned16(params) || !aligned16(scaling) || !aligned16(biasing) || !aligned16(grads) ||
+      !aligned16(workspace) || ((uintptr_t)out_sums & 7))
+    return LLA_EINVAL;
+  const int W = eb_walkers(B, C);
+  const EbPass f = {(uint32_t)seed, (uint32_t)(seed >> 32), step, B, C, W};
+  const dim3 grid((C + kWave - 1) / kWave, W);
+  hipStream_t st = as_stream(stream);
+  float *part = static_cast<float *>(workspace);
+  if (z_dtype == LLA_Z_F16)
+    eb_pass_kernel<_Float16><<<grid, kWave, 0, st>>>(z, ldz, params, scaling, biasing, part, f);
+  else
+    eb_pass_kernel<float><<<grid, kWave, 0, st>>>(z, ldz, params, scaling, biasing, part, f);
+  int rc = check_launch();
+  if (rc != LLA_OK) return rc;
+  const int blocks = (int)(((size_t)kMain * C + 255) / 256) + 1;
+  eb_pass_finish_kernel<<<blocks, 256, 0, st>>>(part, grads, out_sums, C, W);
+  return check_launch();
+}
+
+extern "C" int lla_eb_aux_grad(const float *params, const float *quantiles, const float *target, int C, float *grad_q,
+                               double *out_loss, void *stream) {
+  if (!eb_shape_ok(0, C)) return LLA_EINVAL;
+  if (!params || !quantiles || !target || !grad_q || !out_loss) return LLA_EINVAL;
+  if (!aligned16(params) || !aligned16(quantiles) || !aligned16(grad_q) || ((uintptr_t)target & 3) || ((uintptr_t)out_loss & 7))
+    return LLA_EINVAL;
+  eb_aux_kernel<<<1, 512, 0, as_stream(stream)>>>(params, quantiles, target, grad_q, out_loss, C);
+  return check_launch();
+}

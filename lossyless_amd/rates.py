@@ -7,8 +7,8 @@ Mirror of the inference-time surface of ``lossyless/rates.py`` that the referenc
 ``update``, ``prepare_compressor_``), ``HRateEstimator`` :398-506 (``scaling/biasing``, ``process_z_in/out``
 :434-438, the CDF-buffer-aware load hook :440-473, ``is_coder_updated / is_coder_present /
 is_compute_real_rate`` :482-506), ``HRateFactorizedPrior`` :509-564 and ``HRateHyperprior`` :572-756 -- so that
-``LearnableCompressor`` can evaluate and code representations with the HIP kernels.  Training-mode noise and the
-auxiliary losses stay in the reference (out of scope).
+``LearnableCompressor`` can evaluate and code representations with the HIP kernels.  Training ``HRateFactorizedPrior`` on
+frozen features (noise, the auxiliary loss, both optimisers) is ``lossyless_amd.BottleneckFit`` (bottleneck_fit.py).
 """
 import math
 

@@ -14,7 +14,8 @@ The two `-shaped` modes run the REFERENCE CALL -- a torchvision-style `Dataset(t
 compressor built with `gpu_preprocess=True` -- on generated stand-ins of the real datasets' shapes
 (tools/workloads.py: the real files cannot be fetched offline), and say so in `data`.
 Without real weights the output says so too: these runs exercise the path at the datasets' scale and shapes,
-not the reference's numbers.  Prints one JSON line per rate point.
+not the reference's numbers.  Prints one JSON line per rate point; `--device-bottleneck-fit BETA` adds a rate point trained
+in the run (lossyless_amd.BottleneckFit on the tower's features of the training images) and its line.
 """
 import argparse
 import json
@@ -49,6 +50,44 @@ def _represent(comp, data, idx, batch):
             x = [data[int(k)][0] for k in j]          # raw uint8 [H,W,3] tensors of any size
         out.append(comp(x).cpu())
     return torch.cat(out).numpy()
+
+
+def _features(comp, data, batch):
+    """The tower's features (fp16 [N, 512] on the device) of a tensor or a dataset of raw images: what the rate model codes."""
+    out = []
+    with torch.no_grad():
+        for i in range(0, len(data), batch):
+            if isinstance(data, torch.Tensor):
+                x = data[i:i + batch].cuda()
+            else:
+                x = [data[k][0] for k in range(i, min(i + batch, len(data)))]
+            out.append(comp._embed(x))
+    return torch.cat(out)
+
+
+def _bottleneck_fit_leg(args, comp, train, data, weights, shaped, loader):
+    """Train a rate point on the run's features, code the run's images with it, print its line."""
+    from lossyless_amd import BottleneckFit
+    n = len(train)
+    feats = _features(comp, train, args.batch)
+    torch.cuda.synchronize()
+    t0 = time.perf_counter()
+    fit = BottleneckFit(args.device_bottleneck_fit, epochs=args.bottleneck_fit_epochs, batch_size=min(1024, n)).fit(feats)
+    torch.cuda.synchronize()
+    fit_s = time.perf_counter() - t0
+    fitted, _ = hubconf.clip_compressor(fit.state_dict(), device="cuda", clip_weights=weights, gpu_preprocess=shaped)
+    with tempfile.TemporaryDirectory() as d:
+        f = os.path.join(d, "Z.bin")
+        enc = _compress(fitted, train, f, None, loader)
+        bits = 8 * os.path.getsize(f) / n
+        Z = fitted.decompress_dataset(f, is_info=False)
+        idx = np.arange(n) if (not shaped or n <= args.check) else np.linspace(0, n - 1, args.check).astype(np.int64)
+        assert np.array_equal(Z[idx], _represent(fitted, train, idx, args.batch))
+    print(json.dumps(dict(rate_point=f"BottleneckFit(beta={args.device_bottleneck_fit:g})", data=data, clip_weights=weights, images=n,
+                          bits_per_img=round(bits, 2), encode_img_per_sec=round(n / enc, 1), round_trip="exact",
+                          round_trip_samples=int(len(idx)), bottleneck_fit_s=round(fit_s, 3),
+                          bottleneck_fit_epochs=fit.epochs, bottleneck_fit_rate_curve_bits=[round(r, 2) for r in fit.rate_curve_],
+                          bottleneck_fit_distortion_curve=[round(r, 5) for r in fit.distortion_curve_])), flush=True)
 
 
 def main():
@@ -92,6 +131,11 @@ def main():
                     help="also run lossyless_amd.RidgeProbeCV (scikit-learn's RidgeClassifier objective, N values of alpha "
                          "log-spaced in [1e-3, 1e3], 5 stratified folds, two walks of the container in all) on the device "
                          "(adds ridge_probe_cv_best, _validation_accuracy, _accuracy and _fit_s)")
+    ap.add_argument("--device-bottleneck-fit", type=float, default=0.0, metavar="BETA",
+                    help="also train a rate point of its own with lossyless_amd.BottleneckFit(BETA) on the device, on the tower's "
+                         "features of the run's training images, load its state_dict() through hubconf.clip_compressor and "
+                         "code the same images with it (one more JSON line: bits_per_img, the fit's time and curves)")
+    ap.add_argument("--bottleneck-fit-epochs", type=int, default=10)
     args = ap.parse_args()
 
     weights = os.environ.get("LOSSYLESS_CLIP_WEIGHTS", "synthetic")
@@ -216,6 +260,8 @@ def main():
                               bits_per_img=round(bits, 2), encode_img_per_sec=round(n / enc, 1),
                               decode_img_per_sec=round(n / dec, 1), round_trip="exact",
                               round_trip_samples=int(len(idx)), linear_svc_accuracy=acc, **probe)), flush=True)
+    if args.device_bottleneck_fit > 0:
+        _bottleneck_fit_leg(args, comp, train, data, weights, shaped, loader)
 
 
 if __name__ == "__main__":
