@@ -69,7 +69,8 @@ def clip_hyperprior_compressor(state_dict, device=_ON, **kwargs):
     """CLIP ViT-B/32 + scale-hyperprior compressor (the model behind the reference's headline table), MI355X kernels.
 
     state_dict   : what the reference's ``HRateHyperprior`` saves (``main.py`` training), as a dict or a path to it.  No
-                   hyperprior checkpoint ships with the reference, so there is nothing to fetch.
+                   hyperprior checkpoint ships with the reference, so there is nothing to fetch:
+                   ``lossyless_amd.HyperpriorFit(beta).fit(Z).state_dict()`` trains one on frozen features.
     device, clip_weights, gpu_preprocess, other kwargs : as for ``clip_compressor_b005``; forwarded to
                    ``lossyless_amd.HyperpriorClipCompressor``
 

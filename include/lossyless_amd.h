@@ -841,6 +841,65 @@ int lla_eb_train_pass(const void *z, int z_dtype, size_t ldz, int B, int C, cons
 int lla_eb_aux_grad(const float *params, const float *quantiles, const float *target, int C, float *grad_q, double *out_loss,
                     void *stream);
 
+/* ---- Training passes of the scale-hyperprior rate estimator over frozen features (csrc/hyperprior_train.hip): what autograd
+ * runs for HRateHyperprior in training mode (lossyless/rates.py:631-678, :428-438; lossyless/learnable_compressors.py:241-303;
+ * compressai 1.1.5 EntropyBottleneck and GaussianConditional with uniform noise in place of rounding) around its two MLPs,
+ * which run on lla_gemm_f32 / lla_gemm_f32_tn / lla_gemm_f32_nn.  For a minibatch z [B][C], S = side_z_dim:
+ *   y = (z + biasing) exp(scaling);  x = side_encoder(y);  s_hat = x + u_s;  lik_s as lla_eb_train_pass's lik (no affine)
+ *   gp = z_encoder(s_hat): scales = gp[:, 0..C-1], means = gp[:, C..2C-1];  v = y + u_z;  t = |v - means|;  sc = max(scales, bound)
+ *   lik_z = max(Phi((.5 - t) / sc) - Phi((-.5 - t) / sc), 1e-9),  Phi(a) = 0.5 erfc(-a / sqrt 2)
+ *   rate_i = -sum log lik_s - sum log lik_z (nats);  dist_i = sum_c |u_z exp(-scaling) + 1e-6|  (the closed form of the block above)
+ *   loss = mean_i dist_i + beta_t mean_i rate_i
+ * Both LowerBounds follow compressai: a gradient passes where the value is at or above the bound, or where the gradient is
+ * negative.  d(-log lik) / d lik < 0 always passes; the scale's bound blocks.  sign(0) = 0 for |.| at v == means.
+ * Conventions of the block above: LLA_EINVAL before any device call, a zero-row call LLA_OK with no launch, no floating-point
+ * atomics, the order of every sum a function of the shape alone, fp32 arithmetic with expf / logf / erfcf / tanhf / log1pf /
+ * expm1f (no fast variants), products and sums rounded separately; sums over rows in fp32 per walker, over walkers and channels in
+ * double.  `scale` is the caller's beta_t / B: the passes multiply the rate's gradients by it (per element in fp32 for the
+ * activations' gradients; once, in double, on the summed parameter gradients).
+ * Noise: element f = i cols + c of a [rows][cols] matrix draws Philox4x32-10 with key (seed & 0xffffffff, seed >> 32) and counter
+ * (f / 4 & 0xffffffff, f / 4 >> 32, step, tag), output word f % 4, u = (float)(word >> 8) 2^-24 - 0.5f; tag 0x6e6f6973 for u_z
+ * (cols = C: for C % 4 == 0 the stream of lla_eb_train_pass to the bit), 0x73696465 for u_s (cols = S). */
+
+/* The side information's bottleneck, forward and backward, for ANY S >= 1.  x [B][ldx] fp32 (the side encoder's output; columns
+ * S .. ldx-1 are not read), params [58][S] in the order of lla_eb_train_pass.  Writes
+ *   s_hat [B][lds] = x + u_s (columns S .. lds-1: 0 -- the next GEMM reads them);  dx [B][ldd] = scale d(sum_i rate_s) / dx
+ *   (columns S .. ldd-1: 0);  grads [58 S] = scale d(sum_i rate_s) / d params;  *out_sum (double) = sum_i rate_s.
+ * workspace: lla_eb_side_pass_workspace_bytes(B, S) bytes (0 for a refused shape).  ldx, lds, ldd >= S; x, s_hat, dx 4-byte,
+ * params, grads, workspace 16-byte, out_sum 8-byte aligned. */
+size_t lla_eb_side_pass_workspace_bytes(int B, int S);
+int lla_eb_side_pass(const float *x, int ldx, int B, int S, const float *params, uint64_t seed, uint32_t step, float scale,
+                     float *s_hat, int lds, float *dx, int ldd, float *grads, double *out_sum, void *workspace, void *stream);
+/* lla_eb_aux_grad for any S >= 1 (the same kernel: the same bits where both accept the shape). */
+int lla_eb_aux_grad_any(const float *params, const float *quantiles, const float *target, int S, float *grad_q,
+                        double *out_loss, void *stream);
+/* The affine, the Gaussian conditional likelihood and the distortion, forward and backward.  z [B][ldz] fp16 or fp32 as
+ * lla_eb_train_pass reads it; gp [B][ldg] fp32, ldg >= 2C; scale_bound > 0 (compressai: 0.11).  Writes
+ *   y [B][ldy] fp32 = (z + biasing) exp(scaling), the side encoder's input (columns C .. ldy-1: 0)
+ *   dgp [B][ldg] = scale d(sum_i rate_z) / d(scales | means), the scale half through the bound rule (columns 2C .. ldg-1: 0)
+ *   dy [B][ldy] = scale d(sum_i rate_z) / dy (columns C .. ldy-1: 0)
+ *   g_dist [C] = d(sum_i dist_i) / d scaling, NOT scaled;  out_sums [2] doubles: sum_i dist_i, sum_i rate_z.
+ * With a_u = (.5 - t) / sc, a_l = (-.5 - t) / sc and phi(a) = exp(-a^2 / 2) / sqrt(2 pi), evaluated as
+ * expf(-0.5f (a a)) 0.39894228f:  d lik / dt = -(phi(a_u) - phi(a_l)) / sc,  d lik / d sc = -(a_u phi(a_u) - a_l phi(a_l)) / sc,
+ * dt / dv = -dt / d means = sign(v - means); Phi as 0.5f erfcf(-0.70710678f a); the rate term is -logf of the BOUNDED likelihood
+ * and its seed -1 / lik.  gp == NULL is the prologue: y alone is written (its pad columns included) and dgp, dy, g_dist,
+ * out_sums, workspace are not touched -- y has to exist before the side encoder runs, gp only after the z encoder has.
+ * workspace: lla_gaussian_train_pass_workspace_bytes(B, C) bytes.  z aligned to its element; gp, dgp, y, dy 4-byte; scaling,
+ * biasing, g_dist, workspace 16-byte; out_sums 8-byte. */
+size_t lla_gaussian_train_pass_workspace_bytes(int B, int C);
+int lla_gaussian_train_pass(const void *z, int z_dtype, size_t ldz, int B, int C, const float *scaling, const float *biasing,
+                            const float *gp, int ldg, float scale_bound, uint64_t seed, uint32_t step, float scale, float *dgp,
+                            float *y, int ldy, float *dy, float *g_dist, double *out_sums, void *workspace, void *stream);
+/* The affine's gradient from dy_total [B][ld] = d loss / dy (the Gaussian pass's dy plus the side encoder's input gradient)
+ * and y [B][ldy]:
+ *   g_scaling[c] = sum_i dy_total_ic y_ic (+ add_scale add_scaling[c] when add_scaling != NULL: the distortion's share,
+ *   g_dist / B, added in double before the one rounding);   g_biasing[c] = exp(scaling[c]) sum_i dy_total_ic
+ * (dy / d scaling = y, dy / d biasing = exp(scaling)).  Walker partials in fp32, added in double in walker order.
+ * workspace: lla_affine_grad_workspace_bytes(B, C) bytes.  dy_total, y 4-byte; the [C] vectors and workspace 16-byte aligned. */
+size_t lla_affine_grad_workspace_bytes(int B, int C);
+int lla_affine_grad(const float *dy_total, int ld, const float *y, int ldy, const float *scaling, int B, int C,
+                    const float *add_scaling, float add_scale, float *g_scaling, float *g_biasing, void *workspace, void *stream);
+
 /* out[n][H][W][ldc] (first cout channels) = relu(conv3x3(in, stride 1, pad 1) + bias) as an IMPLICIT GEMM:
  * `in` is NHWC fp16 [n][H][W][pitch] (first cin channels used; cin % 64 == 0, or cin == 32), weights fp16
  * [cout][K] with K = 9 cin rounded up to a multiple of 64 (zero padded) in the order (kh, kw, c), bias fp32

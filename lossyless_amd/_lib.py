@@ -119,6 +119,15 @@ _SIGNATURES = {
     "lla_eb_train_pass_workspace_bytes": (_sz, [_i, _i]),
     "lla_eb_train_pass": (_i, [_vp, _i, _sz, _i, _i, _vp, _vp, _vp, ctypes.c_uint64, ctypes.c_uint32, _vp, _vp, _vp, _vp]),
     "lla_eb_aux_grad": (_i, [_vp, _vp, _vp, _i, _vp, _vp, _vp]),
+    "lla_eb_side_pass_workspace_bytes": (_sz, [_i, _i]),
+    "lla_eb_side_pass": (_i, [_vp, _i, _i, _i, _vp, ctypes.c_uint64, ctypes.c_uint32, ctypes.c_float, _vp, _i, _vp, _i, _vp, _vp,
+                              _vp, _vp]),
+    "lla_eb_aux_grad_any": (_i, [_vp, _vp, _vp, _i, _vp, _vp, _vp]),
+    "lla_gaussian_train_pass_workspace_bytes": (_sz, [_i, _i]),
+    "lla_gaussian_train_pass": (_i, [_vp, _i, _sz, _i, _i, _vp, _vp, _vp, _i, ctypes.c_float, ctypes.c_uint64, ctypes.c_uint32,
+                                     ctypes.c_float, _vp, _vp, _i, _vp, _vp, _vp, _vp, _vp]),
+    "lla_affine_grad_workspace_bytes": (_sz, [_i, _i]),
+    "lla_affine_grad": (_i, [_vp, _i, _vp, _i, _vp, _i, _i, _vp, ctypes.c_float, _vp, _vp, _vp, _vp]),
     "lla_conv3x3_relu_f16": (_i, [_vp, _i, _i, _i, _i, _i, _vp, _vp, _vp, _i, _i, _vp]),
     "lla_conv3x3_direct_relu_f16": (_i, [_vp, _i, _i, _i, _i, _i, _vp, _i, _vp, _vp, _i, _i, _i, _vp]),
     "lla_conv3x3_rgb_s2_relu_f16": (_i, [_vp, _i, _i, _i, _vp, _i, _vp, _vp, _i, _vp]),

@@ -13,8 +13,8 @@ CPU data runs the float64 twin below instead, as every probe of this package doe
 torch (NO autograd: the backward is the kernel's, line for line), the same noise, the same step order.  The tests hold the
 twin to torch autograd and the kernels to the twin.
 
-Not built: the hyperprior's training, the encoder's, the other distortions, ``HRateEstimator.reset_parameters``'
-``weights_init`` (the module's own initialisation is kept), lightning's logging.
+Not built: the encoder's training, the other distortions, ``HRateEstimator.reset_parameters``' ``weights_init`` (the
+module's own initialisation is kept), lightning's logging.  The hyperprior's training is hyperprior_fit.py.
 """
 import math
 

@@ -15,7 +15,8 @@ compressor built with `gpu_preprocess=True` -- on generated stand-ins of the rea
 (tools/workloads.py: the real files cannot be fetched offline), and say so in `data`.
 Without real weights the output says so too: these runs exercise the path at the datasets' scale and shapes,
 not the reference's numbers.  Prints one JSON line per rate point; `--device-bottleneck-fit BETA` adds a rate point trained
-in the run (lossyless_amd.BottleneckFit on the tower's features of the training images) and its line.
+in the run (lossyless_amd.BottleneckFit on the tower's features of the training images) and its line,
+`--device-hyperprior-fit BETA` the same with lossyless_amd.HyperpriorFit.
 """
 import argparse
 import json
@@ -65,17 +66,24 @@ def _features(comp, data, batch):
     return torch.cat(out)
 
 
-def _bottleneck_fit_leg(args, comp, train, data, weights, shaped, loader):
-    """Train a rate point on the run's features, code the run's images with it, print its line."""
-    from lossyless_amd import BottleneckFit
+def _fit_leg(args, comp, train, data, weights, shaped, loader, hyperprior=False):
+    """Train a rate point on the run's features -- BottleneckFit, or HyperpriorFit with ``hyperprior`` -- code the run's images
+    with it, print its line."""
+    from lossyless_amd import BottleneckFit, HyperpriorFit
     n = len(train)
     feats = _features(comp, train, args.batch)
     torch.cuda.synchronize()
     t0 = time.perf_counter()
-    fit = BottleneckFit(args.device_bottleneck_fit, epochs=args.bottleneck_fit_epochs, batch_size=min(1024, n)).fit(feats)
+    if hyperprior:
+        name, beta, epochs, key = "HyperpriorFit", args.device_hyperprior_fit, args.hyperprior_fit_epochs, "hyperprior_fit"
+        fit = HyperpriorFit(beta, epochs=epochs, batch_size=min(1024, n)).fit(feats)
+    else:
+        name, beta, epochs, key = "BottleneckFit", args.device_bottleneck_fit, args.bottleneck_fit_epochs, "bottleneck_fit"
+        fit = BottleneckFit(beta, epochs=epochs, batch_size=min(1024, n)).fit(feats)
     torch.cuda.synchronize()
     fit_s = time.perf_counter() - t0
-    fitted, _ = hubconf.clip_compressor(fit.state_dict(), device="cuda", clip_weights=weights, gpu_preprocess=shaped)
+    hub = hubconf.clip_hyperprior_compressor if hyperprior else hubconf.clip_compressor
+    fitted, _ = hub(fit.state_dict(), device="cuda", clip_weights=weights, gpu_preprocess=shaped)
     with tempfile.TemporaryDirectory() as d:
         f = os.path.join(d, "Z.bin")
         enc = _compress(fitted, train, f, None, loader)
@@ -83,11 +91,14 @@ def _bottleneck_fit_leg(args, comp, train, data, weights, shaped, loader):
         Z = fitted.decompress_dataset(f, is_info=False)
         idx = np.arange(n) if (not shaped or n <= args.check) else np.linspace(0, n - 1, args.check).astype(np.int64)
         assert np.array_equal(Z[idx], _represent(fitted, train, idx, args.batch))
-    print(json.dumps(dict(rate_point=f"BottleneckFit(beta={args.device_bottleneck_fit:g})", data=data, clip_weights=weights, images=n,
-                          bits_per_img=round(bits, 2), encode_img_per_sec=round(n / enc, 1), round_trip="exact",
-                          round_trip_samples=int(len(idx)), bottleneck_fit_s=round(fit_s, 3),
-                          bottleneck_fit_epochs=fit.epochs, bottleneck_fit_rate_curve_bits=[round(r, 2) for r in fit.rate_curve_],
-                          bottleneck_fit_distortion_curve=[round(r, 5) for r in fit.distortion_curve_])), flush=True)
+    line = {"rate_point": f"{name}(beta={beta:g})", "data": data, "clip_weights": weights, "images": n,
+            "bits_per_img": round(bits, 2), "encode_img_per_sec": round(n / enc, 1), "round_trip": "exact",
+            "round_trip_samples": int(len(idx)), f"{key}_s": round(fit_s, 3), f"{key}_epochs": fit.epochs,
+            f"{key}_rate_curve_bits": [round(r, 2) for r in fit.rate_curve_],
+            f"{key}_distortion_curve": [round(r, 5) for r in fit.distortion_curve_]}
+    if hyperprior:
+        line[f"{key}_side_rate_curve_bits"] = [round(r, 2) for r in fit.side_rate_curve_]
+    print(json.dumps(line), flush=True)
 
 
 def main():
@@ -136,6 +147,11 @@ def main():
                          "features of the run's training images, load its state_dict() through hubconf.clip_compressor and "
                          "code the same images with it (one more JSON line: bits_per_img, the fit's time and curves)")
     ap.add_argument("--bottleneck-fit-epochs", type=int, default=10)
+    ap.add_argument("--device-hyperprior-fit", type=float, default=0.0, metavar="BETA",
+                    help="the same with lossyless_amd.HyperpriorFit(BETA): the scale-hyperprior rate model trained on the device, "
+                         "loaded through hubconf.clip_hyperprior_compressor (one more JSON line, with the side information's "
+                         "share of the rate)")
+    ap.add_argument("--hyperprior-fit-epochs", type=int, default=10)
     args = ap.parse_args()
 
     weights = os.environ.get("LOSSYLESS_CLIP_WEIGHTS", "synthetic")
@@ -261,7 +277,9 @@ def main():
                               decode_img_per_sec=round(n / dec, 1), round_trip="exact",
                               round_trip_samples=int(len(idx)), linear_svc_accuracy=acc, **probe)), flush=True)
     if args.device_bottleneck_fit > 0:
-        _bottleneck_fit_leg(args, comp, train, data, weights, shaped, loader)
+        _fit_leg(args, comp, train, data, weights, shaped, loader)
+    if args.device_hyperprior_fit > 0:
+        _fit_leg(args, comp, train, data, weights, shaped, loader, hyperprior=True)
 
 
 if __name__ == "__main__":
