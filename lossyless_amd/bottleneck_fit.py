@@ -22,7 +22,7 @@ import numpy as np
 import torch
 
 from . import _lib
-from .probe import _Adam, _adamw, lr_schedule, philox4x32_10
+from .probe import _Adam, _adamw, _adamw_step, lr_schedule, philox4x32_10
 from .rates import BASE_LOG, HRateFactorizedPrior
 
 FILTERS = (3, 3, 3, 3)
@@ -34,19 +34,28 @@ LIK_BOUND = 1e-9
 _NET_NAMES = [f"_matrix{i}" for i in range(5)] + [f"_bias{i}" for i in range(5)] + [f"_factor{i}" for i in range(4)]
 
 
+def hyperprior_noise(seed, step, rows, cols, tag=NOISE_TAG):
+    """The noise of ``lla_eb_train_pass`` and ``lla_gaussian_train_pass`` (``tag`` 0x6e6f6973) and of ``lla_eb_side_pass``
+    (``hyperprior_fit.SIDE_TAG``) -> fp32 tensor [rows, cols] on the CPU, any ``cols``: element f = i cols + c is word f % 4 of
+    Philox4x32-10 with key (seed_lo, seed_hi) and counter (f / 4 lo, f / 4 hi, step, tag), as
+    ``u = float32(word >> 8) 2^-24 - 0.5`` in [-0.5, 0.5).  The ONE implementation of the stream the kernels are held to."""
+    seed, n = int(seed) & 0xFFFFFFFFFFFFFFFF, int(rows) * int(cols)
+    e = np.arange(-(-n // 4), dtype=np.uint64)
+    counter = np.stack([e & np.uint64(0xFFFFFFFF), e >> np.uint64(32), np.full_like(e, int(step) & 0xFFFFFFFF),
+                        np.full_like(e, int(tag) & 0xFFFFFFFF)], -1)
+    words = philox4x32_10(counter, np.array([seed & 0xFFFFFFFF, seed >> 32], dtype=np.uint64)).reshape(-1)[:n]
+    u = (words >> np.uint32(8)).astype(np.float32) * np.float32(2.0 ** -24) - np.float32(0.5)
+    return torch.from_numpy(u.reshape(int(rows), int(cols)))
+
+
 def bottleneck_noise(seed, step, rows, cols):
     """The noise of ``lla_eb_train_pass`` -> fp32 tensor [rows, cols] on the CPU (``cols % 4 == 0``): element (i, c) is word
     ``c % 4`` of Philox4x32-10 with key (seed_lo, seed_hi) and counter (e_lo, e_hi, step, 0x6e6f6973), e = (i cols + c) / 4,
-    as ``u = float32(word >> 8) 2^-24 - 0.5`` in [-0.5, 0.5).  The definition the kernel is held to."""
+    as ``u = float32(word >> 8) 2^-24 - 0.5`` in [-0.5, 0.5).  The definition the kernel is held to; :func:`hyperprior_noise`
+    restricted to the widths ``lla_eb_train_pass`` takes."""
     if cols % 4:
         raise ValueError("cols must be a multiple of 4")
-    seed = int(seed) & 0xFFFFFFFFFFFFFFFF
-    e = np.arange(rows * cols // 4, dtype=np.uint64)
-    counter = np.stack([e & np.uint64(0xFFFFFFFF), e >> np.uint64(32), np.full_like(e, int(step) & 0xFFFFFFFF),
-                        np.full_like(e, NOISE_TAG)], -1)
-    words = philox4x32_10(counter, np.array([seed & 0xFFFFFFFF, seed >> 32], dtype=np.uint64))
-    u = (words >> np.uint32(8)).astype(np.float32) * np.float32(2.0 ** -24) - np.float32(0.5)
-    return torch.from_numpy(u.reshape(rows, cols))
+    return hyperprior_noise(seed, step, rows, cols)
 
 
 def beta_schedule(beta, total_steps, mode="linear"):
@@ -143,16 +152,11 @@ def _sigmoid_slope(t):
     return e / ((1 + e) * (1 + e))
 
 
-def twin_pass(z, main, u):
-    """``lla_eb_train_pass`` in the dtype of ``main`` [60, C] (rows: scaling, biasing, the 58 of the network) on rows z [B, C]
-    and noise u [B, C] -> (grads [2, 60, C]: of sum dist, of sum rate; sum dist; sum rate).  Backward by hand."""
-    dt = main.dtype
-    z, u = z.to(dt), u.to(dt)
-    s, bz, net = main[0], main[1], main[2:]
+def twin_likelihood(net, v):
+    """eb_lik_step and eb_store_grads of csrc/eb_net.h in the dtype of ``net`` [58, C] at v [B, C] (noise already added) ->
+    (d rate / dv [B, C], d rate / d net [58, C], rate = sum -log lik).  Backward by hand; the likelihood of ``twin_pass`` and
+    of ``hyperprior_fit.twin_side_pass``."""
     sp, b, tf = _twin_net(net)
-    es, ems = torch.exp(s), torch.exp(-s)
-    y = (z + bz) * es
-    v = y + u
     lower, act_lo = _twin_forward(sp, b, tf, v - 0.5)
     upper, act_up = _twin_forward(sp, b, tf, v + 0.5)
     sgn = -torch.sign(lower + upper)
@@ -162,18 +166,29 @@ def twin_pass(z, main, u):
     gl = -1 / lik * torch.sign(diff) * sgn
     acc = (torch.zeros_like(sp), torch.zeros_like(b), torch.zeros_like(tf))
     dv = _twin_backward(sp, tf, act_up, gl * _sigmoid_slope(a), acc) + _twin_backward(sp, tf, act_lo, -gl * _sigmoid_slope(bb), acc)
+    M = net[:N_MAT]
+    e = torch.exp(-M.abs())                 # the chain rule through softplus (its derivative: the sigmoid) and tanh
+    grads = torch.cat([acc[0] * torch.where(M <= 0, e / (1 + e), 1 / (1 + e)), acc[1], acc[2] * (1 - tf * tf)], 0)
+    return dv, grads, -torch.log(lik).sum()
+
+
+def twin_pass(z, main, u):
+    """``lla_eb_train_pass`` in the dtype of ``main`` [60, C] (rows: scaling, biasing, the 58 of the network) on rows z [B, C]
+    and noise u [B, C] -> (grads [2, 60, C]: of sum dist, of sum rate; sum dist; sum rate).  Backward by hand."""
+    dt = main.dtype
+    z, u = z.to(dt), u.to(dt)
+    s, bz = main[0], main[1]
+    es, ems = torch.exp(s), torch.exp(-s)
+    y = (z + bz) * es
+    dv, g_net, rate = twin_likelihood(main[2:], y + u)
     r = u * ems
     d = r + 1e-6
     grads = torch.zeros((2,) + tuple(main.shape), dtype=dt)
     grads[0, 0] = (-torch.sign(d) * r).sum(0)
     grads[1, 0] = (dv * y).sum(0)
     grads[1, 1] = (dv * es).sum(0)
-    M = net[:N_MAT]
-    e = torch.exp(-M.abs())
-    grads[1, 2:2 + N_MAT] = acc[0] * torch.where(M <= 0, e / (1 + e), 1 / (1 + e))
-    grads[1, 2 + N_MAT:2 + N_MAT + N_BIAS] = acc[1]
-    grads[1, 2 + N_MAT + N_BIAS:] = acc[2] * (1 - tf * tf)
-    return grads, d.abs().sum(), -torch.log(lik).sum()
+    grads[1, 2:] = g_net
+    return grads, d.abs().sum(), rate
 
 
 def twin_aux(net, q, target):
@@ -185,16 +200,48 @@ def twin_aux(net, q, target):
     return (torch.sign(r) * dx).t().contiguous(), r.abs().sum()
 
 
-class _TwinEngine:
-    """One training step in float64 on the host: the CPU path of ``BottleneckFit`` and the oracle of its GPU tests."""
+class _Engine:
+    """What the four engines of this module and of hyperprior_fit.py share: the two optimisers and the step count, the log of
+    an epoch's steps (``width`` doubles a step) and, on a device, the slots the kernels write those sums to (read once per
+    epoch: one synchronisation) and the rows of a minibatch as the library reads them."""
+
+    def __init__(self, width, adam, adam_coder, seed, device=None, max_batch=0, steps_per_epoch=0):
+        self.adam, self.adam_coder, self.seed, self.t = adam, adam_coder, int(seed), 0
+        self.width, self.log, self.n_log, self.sums = width, [], 0, None
+        if device is not None:
+            self.L, self.dev, self.rows = _lib.lib(), torch.device(device), max(int(max_batch), 1)
+            self.sums = torch.zeros((max(int(steps_per_epoch), 1), width), dtype=torch.float64, device=self.dev)
+
+    def _minibatch(self, z, C):
+        """-> (z in fp16 or fp32 with a unit column stride, its ``LLA_Z_*`` code, its pitch), for the epoch's next slot."""
+        B = z.shape[0]
+        if B > self.rows or self.n_log >= self.sums.shape[0]:
+            raise ValueError("a minibatch larger, or an epoch longer, than the engine was sized for")
+        if z.dtype not in (torch.float16, torch.float32):
+            z = z.float()
+        if z.stride(1) != 1 or (B > 1 and z.stride(0) < C):
+            z = z.contiguous()
+        return z, _lib.LLA_Z_F16 if z.dtype == torch.float16 else _lib.LLA_Z_F32, z.stride(0) if B > 1 else C
+
+    def epoch_log(self):
+        """-> [steps, width] doubles, the sums of the steps since the last call."""
+        if self.sums is None:
+            out, self.log = np.asarray(self.log, dtype=np.float64).reshape(-1, self.width), []
+        else:
+            out, self.n_log = self.sums[:self.n_log].cpu().numpy().copy(), 0
+        return out
+
+
+class _TwinEngine(_Engine):
+    """One training step in float64 on the host: the CPU path of ``BottleneckFit`` and the oracle of its GPU tests.  A step's
+    log: sum dist, sum rate, aux."""
 
     def __init__(self, main, q, target, adam, adam_coder, seed):
+        super().__init__(3, adam, adam_coder, seed)
         self.main, self.q, self.target = main.double().clone(), q.double().clone(), target.double()
         self.C = self.main.shape[1]
-        self.adam, self.adam_coder, self.seed, self.t = adam, adam_coder, int(seed), 0
         self.mom = [(torch.zeros_like(self.main), torch.zeros_like(self.main))]
         self.mom_q = [(torch.zeros_like(self.q), torch.zeros_like(self.q))]
-        self.log = []
 
     def step(self, z, step, beta_t):
         B = z.shape[0]
@@ -205,73 +252,47 @@ class _TwinEngine:
         _adamw([self.q], [gq], self.mom_q, self.adam_coder, self.t)
         self.log.append((float(dist), float(rate), float(aux)))
 
-    def epoch_log(self):
-        """-> [steps, 3] doubles (sum dist, sum rate, aux) of the steps since the last call."""
-        out, self.log = np.asarray(self.log, dtype=np.float64).reshape(-1, 3), []
-        return out
-
     def state(self):
         return self.main.clone(), self.q.clone()
 
 
-class _DeviceEngine:
-    """The same step on the GPU: fp32 flat buffers, ``lla_eb_train_pass`` + ``lla_eb_aux_grad`` + 2 x ``lla_adamw_step``;
-    the sums of a step stay on the device until ``epoch_log`` reads them (one synchronisation per epoch)."""
+class _DeviceEngine(_Engine):
+    """The same step on the GPU: fp32 flat buffers, ``lla_eb_train_pass`` + ``lla_eb_aux_grad`` + 2 x ``lla_adamw_step``."""
 
     def __init__(self, main, q, target, adam, adam_coder, seed, device, max_batch, steps_per_epoch):
-        self.L, self.dev = _lib.lib(), torch.device(device)
+        super().__init__(3, adam, adam_coder, seed, device, max_batch, steps_per_epoch)
         f = lambda t: t.to(self.dev, torch.float32).contiguous()
         self.main, self.q, self.target = f(main), f(q), f(target)
         self.C = self.main.shape[1]
         if self.C % 4:
             raise ValueError("the device engine needs a channel count that is a multiple of 4")
-        self.adam, self.adam_coder, self.seed, self.t = adam, adam_coder, int(seed), 0
         z = lambda t: torch.zeros_like(t)
         self.g, self.m, self.v = z(self.main), z(self.main), z(self.main)
         self.gq, self.mq, self.vq = z(self.q), z(self.q), z(self.q)
         self.raw = torch.zeros((2,) + tuple(self.main.shape), dtype=torch.float32, device=self.dev)
-        self.max_batch = int(max_batch)
-        self.ws = torch.empty(max(int(self.L.lla_eb_train_pass_workspace_bytes(self.max_batch, self.C)), 16), dtype=torch.uint8,
+        self.ws = torch.empty(max(int(self.L.lla_eb_train_pass_workspace_bytes(self.rows, self.C)), 16), dtype=torch.uint8,
                               device=self.dev)
-        self.sums = torch.zeros((max(int(steps_per_epoch), 1), 3), dtype=torch.float64, device=self.dev)
-        self.n_log = 0
-
-    def _adamw(self, p, g, m, v, a):
-        bc1, bc2 = a.corrections(self.t)
-        rc = self.L.lla_adamw_step(_lib.ptr(p), _lib.ptr(g), _lib.ptr(m), _lib.ptr(v), p.numel(), a.lr, a.b1, a.b2, a.eps, a.wd,
-                                   bc1, bc2, _lib.stream_ptr(self.dev))
-        _lib.check(rc, "lla_adamw_step")
 
     def step(self, z, step, beta_t):
         B, C, L = z.shape[0], self.C, self.L
-        if B > self.max_batch or self.n_log >= self.sums.shape[0]:
-            raise ValueError("a minibatch larger, or an epoch longer, than the engine was sized for")
-        if z.dtype not in (torch.float16, torch.float32):
-            z = z.float()
-        if z.stride(1) != 1 or (B > 1 and z.stride(0) < C):
-            z = z.contiguous()
+        z, code, ldz = self._minibatch(z, C)
         _lib.require_cuda(self.main, "parameters")
         slot = self.sums[self.n_log]
         with torch.cuda.device(self.dev):
             st = _lib.stream_ptr(self.dev)
-            rc = L.lla_eb_train_pass(_lib.ptr(z), _lib.LLA_Z_F16 if z.dtype == torch.float16 else _lib.LLA_Z_F32,
-                                     z.stride(0) if B > 1 else C, B, C, _lib.ptr(self.main[2:]), _lib.ptr(self.main[0]),
+            rc = L.lla_eb_train_pass(_lib.ptr(z), code, ldz, B, C, _lib.ptr(self.main[2:]), _lib.ptr(self.main[0]),
                                      _lib.ptr(self.main[1]), self.seed & 0xFFFFFFFFFFFFFFFF, int(step) & 0xFFFFFFFF,
                                      _lib.ptr(self.raw), _lib.ptr(slot), _lib.ptr(self.ws), st)
             _lib.check(rc, "lla_eb_train_pass")
             torch.add(self.raw[0], self.raw[1], alpha=float(beta_t), out=self.g)      # (g_dist + beta_t g_rate) / B
             self.g.div_(float(B))
             self.t += 1
-            self._adamw(self.main, self.g, self.m, self.v, self.adam)
+            _adamw_step(L, self.main, self.g, self.m, self.v, self.adam, *self.adam.corrections(self.t), st)
             rc = L.lla_eb_aux_grad(_lib.ptr(self.main[2:]), _lib.ptr(self.q), _lib.ptr(self.target), C, _lib.ptr(self.gq),
                                    _lib.ptr(slot[2:]), st)
             _lib.check(rc, "lla_eb_aux_grad")
-            self._adamw(self.q, self.gq, self.mq, self.vq, self.adam_coder)
+            _adamw_step(L, self.q, self.gq, self.mq, self.vq, self.adam_coder, *self.adam_coder.corrections(self.t), st)
         self.n_log += 1
-
-    def epoch_log(self):
-        out, self.n_log = self.sums[:self.n_log].cpu().numpy().copy(), 0
-        return out
 
     def state(self):
         return self.main.detach().cpu().clone(), self.q.detach().cpu().clone()
@@ -313,17 +334,48 @@ class BottleneckFit:
         self.lr_curve_ = lr_schedule(scheduler, lr, self.epochs, decay_factor=decay_factor)      # (ValueError: unknown scheduler)
         self._lr_coder_curve = lr_schedule(scheduler, lr_coder, self.epochs, decay_factor=decay_factor)
 
+    def _draw_biases(self, eb, g):
+        """The ``_bias*`` values of an ``EntropyBottleneck``, uniform in +-0.5 from the seeded generator: its first draws."""
+        with torch.no_grad():
+            for i in range(5):
+                b = getattr(eb, f"_bias{i}")
+                b.copy_(torch.empty(b.shape).uniform_(-0.5, 0.5, generator=g))
+
     def initial_estimator(self, z_dim, generator=None):
         """The untrained module: ``EntropyBottleneck.__init__`` (``scaling`` = 1, ``biasing`` = 0, lossyless/rates.py:423-424)
         with the ``_bias`` values drawn from the seeded generator."""
         g = generator if generator is not None else torch.Generator().manual_seed(self.seed)
         with torch.random.fork_rng(devices=[]):
             m = HRateFactorizedPrior(int(z_dim), kwargs_ent_bottleneck=dict(init_scale=self.init_scale, filters=FILTERS))
-        with torch.no_grad():
-            for i in range(5):
-                b = getattr(m.entropy_bottleneck, f"_bias{i}")
-                b.copy_(torch.empty(b.shape).uniform_(-0.5, 0.5, generator=g))
+        self._draw_biases(m.entropy_bottleneck, g)
         return m
+
+    # ---- the three hooks of ``fit``, which HyperpriorFit replaces
+    def _engine(self, m, adam, adam_coder, dev, max_batch, steps_per_epoch):
+        """The freshly initialised module -> its engine: the device's for ``dev`` a GPU, else the twin."""
+        eb = m.entropy_bottleneck
+        main = torch.cat([m.scaling.detach().double()[None], m.biasing.detach().double()[None], pack_network(eb)], 0)
+        q = eb.quantiles.detach().double().reshape(-1, 3)
+        if dev.type == "cuda":
+            return _DeviceEngine(main, q, eb.target, adam, adam_coder, self.seed, dev, max_batch, steps_per_epoch)
+        return _TwinEngine(main, q, eb.target, adam, adam_coder, self.seed)
+
+    def _curve_entries(self, log, N):
+        """One epoch's ``epoch_log()`` -> {curve: the epoch's entry}."""
+        return self._rate_entries(log[:, 0], log[:, 1], log[:, 2], N)
+
+    def _rate_entries(self, dist, rate, aux, N):
+        return dict(rate=float(rate.sum() / N / math.log(BASE_LOG)), distortion=float(dist.sum() / N),
+                    loss=float((dist + self.beta * rate).sum() / N), aux=float(aux.mean()))
+
+    def _store(self, m, state):
+        """The engine's ``state()`` back into the module."""
+        main, q = state
+        with torch.no_grad():
+            m.scaling.copy_(main[0].float())
+            m.biasing.copy_(main[1].float())
+            unpack_network_(m.entropy_bottleneck, main[2:].float())
+            m.entropy_bottleneck.quantiles.copy_(q.float().reshape(-1, 1, 3))
 
     def _batches(self, Z, g):
         """One epoch of minibatches of Z in an order drawn from g."""
@@ -346,40 +398,22 @@ class BottleneckFit:
             N, C, dev = int(Z.shape[0]), int(Z.shape[1]), Z.device
         g = torch.Generator().manual_seed(self.seed)
         m = self.initial_estimator(C, g)
-        eb = m.entropy_bottleneck
-        main = torch.cat([m.scaling.detach().double()[None], m.biasing.detach().double()[None], pack_network(eb)], 0)
-        q = eb.quantiles.detach().double().reshape(C, 3)
         steps_per_epoch = -(-N // self.batch_size)
         betas = beta_schedule(self.beta, self.epochs * steps_per_epoch, self.beta_anneal)
         adam = _Adam(self.lr, self.weight_decay, (0.9, 0.999), 1e-8)
         adam_coder = _Adam(self.lr_coder, self.weight_decay_coder, (0.9, 0.999), 1e-8)
-        if dev.type == "cuda":
-            eng = _DeviceEngine(main, q, eb.target, adam, adam_coder, self.seed, dev, min(self.batch_size, N), steps_per_epoch)
-        else:
-            eng = _TwinEngine(main, q, eb.target, adam, adam_coder, self.seed)
-        curves = {k: [] for k in ("rate", "distortion", "loss", "aux", "beta")}
-        step = 0
+        eng = self._engine(m, adam, adam_coder, dev, min(self.batch_size, N), steps_per_epoch)
+        curves, step = {}, 0
         for epoch in range(self.epochs):
             adam.lr, adam_coder.lr = self.lr_curve_[epoch], self._lr_coder_curve[epoch]
-            first = step
             for zb in self._batches(Z, g):
                 eng.step(zb, step, betas[step])
                 step += 1
-            log = eng.epoch_log()
-            bt = np.asarray(betas[first:step])
-            curves["rate"].append(float(log[:, 1].sum() / N / math.log(BASE_LOG)))
-            curves["distortion"].append(float(log[:, 0].sum() / N))
-            curves["loss"].append(float((log[:, 0] + self.beta * log[:, 1]).sum() / N))
-            curves["aux"].append(float(log[:, 2].mean()))
-            curves["beta"].append(float(bt[-1]))
+            for k, v in dict(self._curve_entries(eng.epoch_log(), N), beta=float(betas[step - 1])).items():
+                curves.setdefault(k, []).append(v)
         for k, v in curves.items():
             setattr(self, f"{k}_curve_", v)
-        main, q = eng.state()
-        with torch.no_grad():
-            m.scaling.copy_(main[0].float())
-            m.biasing.copy_(main[1].float())
-            unpack_network_(eb, main[2:].float())
-            eb.quantiles.copy_(q.float().reshape(C, 1, 3))
+        self._store(m, eng.state())
         m.eval()
         m.update(force=True)
         self.engine_ = "device" if dev.type == "cuda" else "twin"
@@ -387,6 +421,8 @@ class BottleneckFit:
         return self
 
     def state_dict(self):
-        """What the reference's module saves, with the key set of the shipped ``assets/*_factorized_rate.pt``: loads into
-        ``ClipCompressor(pretrained_state_dict=...)`` and into the reference's ``HRateFactorizedPrior``."""
+        """What the reference's module saves: for ``BottleneckFit`` the key set of the shipped ``assets/*_factorized_rate.pt``
+        (loads into ``ClipCompressor(pretrained_state_dict=...)`` and the reference's ``HRateFactorizedPrior``), for
+        ``HyperpriorFit`` that of ``synthetic_hyperprior_state_dict`` (loads into ``hubconf.clip_hyperprior_compressor`` and,
+        ``strict=True``, into ``HRateHyperprior(z_dim)``)."""
         return {k: v.detach().cpu().clone() for k, v in self.rate_estimator_.state_dict().items()}

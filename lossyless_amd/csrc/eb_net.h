@@ -1,7 +1,8 @@
 // Device functions of one channel's cumulative network (compressai 1.1.5 EntropyBottleneck, filters (3, 3, 3, 3)) and the
 // Philox noise stream, shared by the training passes of the factorized model (eb_train.hip) and of the scale hyperprior
-// (hyperprior_train.hip).  include/lossyless_amd.h states the mathematics; every formula here has ONE form, which the float64
-// twins of bottleneck_fit.py / hyperprior_fit.py repeat line for line.
+// (hyperprior_train.hip), with the per-element likelihood step of their two walks and the sums of their finish kernels.
+// include/lossyless_amd.h states the mathematics; every formula here has ONE form, which the float64 twin of bottleneck_fit.py
+// (twin_likelihood and what it calls) repeats line for line.
 #pragma once
 #include "common.h"
 
@@ -18,6 +19,7 @@ constexpr int kWaveSlots = 2048;             // 256 CUs x 4 SIMDs x 2 waves (the
 constexpr uint32_t kNoiseTag = 0x6e6f6973u;  // fourth counter word of the noise stream of z ("nois")
 constexpr uint32_t kSideTag = 0x73696465u;   // ... of the side information's stream ("side")
 constexpr float kLikBound = 1e-9f;
+constexpr int kMaxWidth = 1 << 20;           // widest matrix (channels) a pass accepts
 
 // Philox4x32-10 (Salmon et al., SC'11), as csrc/batchnorm.hip draws its dropout masks; word `pick` of the four.
 __device__ __forceinline__ uint32_t philox_word(uint32_t c0, uint32_t c1, uint32_t c2, uint32_t c3, uint32_t k0, uint32_t k1,
@@ -33,7 +35,8 @@ __device__ __forceinline__ uint32_t philox_word(uint32_t c0, uint32_t c1, uint32
 }
 
 // The noise of element f = i cols + c of a [rows][cols] matrix, ANY cols: counter (f / 4 lo, f / 4 hi, step, tag), word f % 4,
-// u = float(word >> 8) 2^-24 - 0.5 in [-0.5, 0.5).  For cols % 4 == 0 and tag kNoiseTag this is eb_pass_kernel's stream.
+// u = float(word >> 8) 2^-24 - 0.5 in [-0.5, 0.5).  Every pass draws from it; eb_pass_kernel's cols are multiples of 4, where
+// the word is c % 4 (the definition of bottleneck_noise).
 __device__ __forceinline__ float noise_at(uint64_t f, uint32_t step, uint32_t tag, uint32_t k0, uint32_t k1) {
   const uint64_t e = f >> 2;
   const uint32_t word = philox_word((uint32_t)e, (uint32_t)(e >> 32), step, tag, k0, k1, (int)(f & 3));
@@ -159,6 +162,73 @@ __device__ __forceinline__ float sigmoid_slope(float t) {
 }
 __device__ __forceinline__ float sign_f(float x) { return x > 0.f ? 1.f : x < 0.f ? -1.f : 0.f; }
 
+// ---- what eb_pass_kernel and side_pass_kernel share of a walk: the accumulators' start, one element, the walker's 58 stores
+__device__ __forceinline__ void eb_acc_zero(EbAcc &acc) {
+#pragma unroll
+  for (int k = 0; k < kMat; ++k) acc.sp[k] = 0.f;
+#pragma unroll
+  for (int k = 0; k < kBias; ++k) acc.b[k] = 0.f;
+#pragma unroll
+  for (int k = 0; k < kFac; ++k) acc.tf[k] = 0.f;
+}
+
+// One element of the bounded likelihood at v (noise already added): adds -log lik to sum_rate and the element's share of the
+// network's gradients to acc, returns d(-log lik) / dv.
+__device__ __forceinline__ float eb_lik_step(const EbNet &n, float v, EbAcc &acc, float &sum_rate) {
+  EbAct lo, up;
+  const float lower = eb_forward(n, v - 0.5f, lo), upper = eb_forward(n, v + 0.5f, up);
+  const float sgn = -sign_f(lower + upper);
+  const float a = sgn * upper, b = sgn * lower;
+  const float diff = sigmoid_diff(a, b);
+  const float lik = fmaxf(fabsf(diff), kLikBound);
+  sum_rate += -logf(lik);
+  // d(-log lik) / d lik = -1 / lik through the bound (header); |.| and the constant sign give the seeds of the two evaluations
+  const float gl = -1.f / lik * sign_f(diff) * sgn;
+  return eb_backward<true>(n, up, gl * sigmoid_slope(a), acc) + eb_backward<true>(n, lo, -gl * sigmoid_slope(b), acc);
+}
+
+// The lane's 58 network gradients to rows row0 .. row0 + 57 of `out` ([.][C], already at the lane's channel c), through the
+// chain rule of the parameters' own images: d softplus(m) = sigmoid(m), d tanh(f) = 1 - tanh(f)^2.
+__device__ __forceinline__ void eb_store_grads(const EbNet &n, const EbAcc &acc, const float *params, int C, int c, float *out,
+                                               int row0) {
+#pragma unroll
+  for (int k = 0; k < kMat; ++k) out[(size_t)(row0 + k) * C] = acc.sp[k] * sigmoid_f(params[(size_t)k * C + c]);
+#pragma unroll
+  for (int k = 0; k < kBias; ++k) out[(size_t)(row0 + kMat + k) * C] = acc.b[k];
+#pragma unroll
+  for (int k = 0; k < kFac; ++k) out[(size_t)(row0 + kMat + kBias + k) * C] = acc.tf[k] * (1.f - n.tf[k] * n.tf[k]);
+}
+
+// ---- what the finish kernels share.  The sum of element `at` over the W walkers' slabs, in walker order, in double.
+__device__ __forceinline__ double walker_sum(const float *__restrict__ part, size_t slab, size_t at, int W) {
+  double sum = 0.0;
+  for (int w = 0; w < W; ++w) sum += (double)part[w * slab + at];
+  return sum;
+}
+
+// The scalar sums of a pass, by the LAST workgroup (256 threads) of its finish kernel: for q < Q, out[q] = the sum over the
+// channels of the walker_sum of partial row first + q; thread t adds the channels t, t + 256, ... in ascending order and
+// thread 0 .. Q-1 adds the 256 thread sums of its q in thread order.
+template <int Q>
+__device__ __forceinline__ void channel_totals(const float *__restrict__ part, size_t slab, int first, int C, int W,
+                                               double *__restrict__ out, double (*red)[256]) {
+  double tot[Q];
+#pragma unroll
+  for (int q = 0; q < Q; ++q) tot[q] = 0.0;
+  for (int c = threadIdx.x; c < C; c += 256) {
+#pragma unroll
+    for (int q = 0; q < Q; ++q) tot[q] += walker_sum(part, slab, (size_t)(first + q) * C + c, W);
+  }
+#pragma unroll
+  for (int q = 0; q < Q; ++q) red[q][threadIdx.x] = tot[q];
+  __syncthreads();
+  if (threadIdx.x < Q) {
+    double sum = 0.0;
+    for (int t = 0; t < 256; ++t) sum += red[threadIdx.x][t];
+    out[threadIdx.x] = sum;
+  }
+}
+
 template <typename T>
 __device__ __forceinline__ float load_z(const void *z, size_t at) {
   return (float)reinterpret_cast<const T *>(z)[at];
@@ -175,10 +245,4 @@ inline int eb_walkers(int B, int C) {
 }
 
 }  // namespace
-
-// eb_aux_kernel lives in eb_train.hip alone; lla_eb_aux_grad and lla_eb_aux_grad_any both launch it through this (any C >= 1,
-// arguments already checked).
-int launch_eb_aux(const float *params, const float *quantiles, const float *target, int C, float *grad_q, double *out_loss,
-                  hipStream_t stream);
-
 }  // namespace lla

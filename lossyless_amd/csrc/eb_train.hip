@@ -8,6 +8,7 @@
 //   lla_eb_train_pass   sum_i dist_i, sum_i rate_i and their gradients with respect to scaling, biasing and the 58 numbers of
 //                       each channel's cumulative network: eb_pass_kernel (forward + backward) then eb_pass_finish_kernel
 //   lla_eb_aux_grad     the auxiliary (quantile) loss and its gradient with respect to the quantiles: eb_aux_kernel
+//   lla_eb_aux_grad_any the same for any channel count (the hyperprior's side bottleneck); one checked function, eb_aux_grad
 //
 // Arrangement of the pass: a LANE owns a channel, a wave owns 64 adjacent channels (a row's load is one contiguous line of 256
 // or 128 bytes), one wave per workgroup.  Walker w of W walks the rows w, w + W, ...  The channel's parameters -- as the network
@@ -19,8 +20,9 @@
 // (eb_walkers), so the same inputs give the same bits.  No atomics, no LDS in the pass kernel.
 //
 // Resources (hipcc -Rpass-analysis=kernel-resource-usage, gfx950): DESIGN.md 5.19 records the register, scratch and occupancy
-// figures of the three kernels.  The channel network's device functions and the noise stream live in eb_net.h, which
-// hyperprior_train.hip shares; eb_aux_kernel stays here and serves both through launch_eb_aux.
+// figures of the three kernels.  The channel network's device functions, the noise stream (noise_at), the walk's shared parts
+// (eb_acc_zero, eb_lik_step, eb_store_grads) and the finish kernels' sums (walker_sum, channel_totals) live in eb_net.h, which
+// hyperprior_train.hip shares; eb_aux_kernel and both of its entry points are here.
 #include "eb_net.h"
 
 namespace lla {
@@ -45,32 +47,15 @@ __global__ __launch_bounds__(64) void eb_pass_kernel(const void *__restrict__ z,
   const float s = scaling[c], bz = biasing[c];
   const float es = expf(s), ems = expf(-s);
   EbAcc acc;
-#pragma unroll
-  for (int k = 0; k < kMat; ++k) acc.sp[k] = 0.f;
-#pragma unroll
-  for (int k = 0; k < kBias; ++k) acc.b[k] = 0.f;
-#pragma unroll
-  for (int k = 0; k < kFac; ++k) acc.tf[k] = 0.f;
+  eb_acc_zero(acc);
   float g_rate_s = 0.f, g_rate_b = 0.f, g_dist_s = 0.f, sum_dist = 0.f, sum_rate = 0.f;
   float zn = w < f.B ? load_z<T>(z, (size_t)w * ldz + c) : 0.f;
   for (int i = w; i < f.B; i += f.W) {
     const float zi = zn;
     if (i + f.W < f.B) zn = load_z<T>(z, (size_t)(i + f.W) * ldz + c);   // the next row's load flies over this row's arithmetic
-    const uint64_t e = ((uint64_t)i * (uint64_t)f.C + (uint64_t)c) >> 2;
-    const uint32_t word = philox_word((uint32_t)e, (uint32_t)(e >> 32), f.step, kNoiseTag, f.k0, f.k1, c & 3);
-    const float u = (float)(word >> 8) * 0x1p-24f - 0.5f;
+    const float u = noise_at((uint64_t)i * (uint64_t)f.C + (uint64_t)c, f.step, kNoiseTag, f.k0, f.k1);
     const float y = (zi + bz) * es;
-    const float v = y + u;
-    EbAct lo, up;
-    const float lower = eb_forward(n, v - 0.5f, lo), upper = eb_forward(n, v + 0.5f, up);
-    const float sgn = -sign_f(lower + upper);
-    const float a = sgn * upper, b = sgn * lower;
-    const float diff = sigmoid_diff(a, b);
-    const float lik = fmaxf(fabsf(diff), kLikBound);
-    sum_rate += -logf(lik);
-    // d(-log lik) / d lik = -1 / lik through the bound (header); |.| and the constant sign give the seeds of the two evaluations
-    const float gl = -1.f / lik * sign_f(diff) * sgn;
-    const float dv = eb_backward<true>(n, up, gl * sigmoid_slope(a), acc) + eb_backward<true>(n, lo, -gl * sigmoid_slope(b), acc);
+    const float dv = eb_lik_step(n, y + u, acc, sum_rate);
     g_rate_s += dv * y;
     g_rate_b += dv * es;
     // dist: z_hat - z = u exp(-s) (closed form of the header), + the 1e-6 of nn.PairwiseDistance
@@ -78,46 +63,24 @@ __global__ __launch_bounds__(64) void eb_pass_kernel(const void *__restrict__ z,
     sum_dist += fabsf(d);
     g_dist_s += -sign_f(d) * r;
   }
-  // chain rule through the parameters' own images: d softplus(m) = sigmoid(m), d tanh(f) = 1 - tanh(f)^2
   float *out = part + (size_t)w * kPart * f.C + c;
   out[0] = g_dist_s;
   out[(size_t)1 * f.C] = g_rate_s;
   out[(size_t)2 * f.C] = g_rate_b;
-#pragma unroll
-  for (int k = 0; k < kMat; ++k) out[(size_t)(3 + k) * f.C] = acc.sp[k] * sigmoid_f(params[(size_t)k * f.C + c]);
-#pragma unroll
-  for (int k = 0; k < kBias; ++k) out[(size_t)(3 + kMat + k) * f.C] = acc.b[k];
-#pragma unroll
-  for (int k = 0; k < kFac; ++k) out[(size_t)(3 + kMat + kBias + k) * f.C] = acc.tf[k] * (1.f - n.tf[k] * n.tf[k]);
+  eb_store_grads(n, acc, params, f.C, c, out, 3);
   out[(size_t)61 * f.C] = sum_dist;
   out[(size_t)62 * f.C] = sum_rate;
 }
 
 // grads[0][..] (dist) and grads[1][..] (rate), each 60 C: every element the sum of its W partials in walker order, in double,
-// rounded once (the dist half is zero outside scaling).  The LAST workgroup adds the channels' dist and rate sums instead:
-// thread t adds the channels t, t + 256, ... (each the double sum of its walkers, in walker order) in ascending order, and
-// thread 0 adds the 256 thread sums in thread order.
+// rounded once (the dist half is zero outside scaling).  The LAST workgroup adds the channels' dist and rate sums instead
+// (channel_totals, eb_net.h).
 __global__ __launch_bounds__(256) void eb_pass_finish_kernel(const float *__restrict__ part, float *__restrict__ grads,
                                                              double *__restrict__ out_sums, int C, int W) {
   __shared__ double red[2][256];
   const size_t slab = (size_t)kPart * C;
   if (blockIdx.x + 1 == gridDim.x) {
-    double tot[2] = {0.0, 0.0};
-    for (int c = threadIdx.x; c < C; c += 256) {
-#pragma unroll
-      for (int q = 0; q < 2; ++q) {
-        double col = 0.0;
-        for (int w = 0; w < W; ++w) col += (double)part[w * slab + (size_t)(61 + q) * C + c];
-        tot[q] += col;
-      }
-    }
-    red[0][threadIdx.x] = tot[0], red[1][threadIdx.x] = tot[1];
-    __syncthreads();
-    if (threadIdx.x < 2) {
-      double sum = 0.0;
-      for (int t = 0; t < 256; ++t) sum += red[threadIdx.x][t];
-      out_sums[threadIdx.x] = sum;
-    }
+    channel_totals<2>(part, slab, 61, C, W, out_sums, red);
     return;
   }
   const size_t at = (size_t)blockIdx.x * 256 + threadIdx.x;      // element of the main layout: [60][C]
@@ -125,12 +88,8 @@ __global__ __launch_bounds__(256) void eb_pass_finish_kernel(const float *__rest
   const int k = (int)(at / C), c = (int)(at % C);
   // main layout row k: 0 scaling, 1 biasing, 2 + j network -> partial rows: rate (1, 2, 3 + j), dist (0 for scaling)
   const int rate_row = k == 0 ? 1 : k == 1 ? 2 : k + 1;
-  double rate = 0.0, dist = 0.0;
-  for (int w = 0; w < W; ++w) rate += (double)part[w * slab + (size_t)rate_row * C + c];
-  if (k == 0)
-    for (int w = 0; w < W; ++w) dist += (double)part[w * slab + c];
-  grads[at] = (float)dist;
-  grads[(size_t)kMain * C + at] = (float)rate;
+  grads[at] = k == 0 ? (float)walker_sum(part, slab, c, W) : 0.f;
+  grads[(size_t)kMain * C + at] = (float)walker_sum(part, slab, (size_t)rate_row * C + c, W);
 }
 
 // aux = sum_c sum_k |L_c(q_c[k]) - target[k]| and d aux / d q_c[k] = sign(.) dL_c/dx (q_c[k]), the network held constant.
@@ -175,16 +134,20 @@ __global__ __launch_bounds__(512) void eb_aux_kernel(const float *__restrict__ p
   if (threadIdx.x == 0) *out_loss = total;
 }
 
-bool eb_shape_ok(int B, int C) { return B >= 0 && C > 0 && !(C & 3) && C <= (1 << 20); }
+bool eb_shape_ok(int B, int C) { return B >= 0 && C > 0 && !(C & 3) && C <= kMaxWidth; }
 
-}  // namespace
-
-int launch_eb_aux(const float *params, const float *quantiles, const float *target, int C, float *grad_q, double *out_loss,
-                  hipStream_t stream) {
-  eb_aux_kernel<<<1, 512, 0, stream>>>(params, quantiles, target, grad_q, out_loss, C);
+// what lla_eb_aux_grad and lla_eb_aux_grad_any share: every refusal but the first's C % 4, and the launch
+int eb_aux_grad(const float *params, const float *quantiles, const float *target, int C, float *grad_q, double *out_loss,
+                void *stream) {
+  if (C <= 0 || C > kMaxWidth) return LLA_EINVAL;
+  if (!params || !quantiles || !target || !grad_q || !out_loss) return LLA_EINVAL;
+  if (!aligned16(params) || !aligned16(quantiles) || !aligned16(grad_q) || ((uintptr_t)target & 3) || ((uintptr_t)out_loss & 7))
+    return LLA_EINVAL;
+  eb_aux_kernel<<<1, 512, 0, as_stream(stream)>>>(params, quantiles, target, grad_q, out_loss, C);
   return check_launch();
 }
 
+}  // namespace
 }  // namespace lla
 
 using namespace lla;
@@ -222,9 +185,11 @@ extern "C" int lla_eb_train_pass(const void *z, int z_dtype, size_t ldz, int B, 
 
 extern "C" int lla_eb_aux_grad(const float *params, const float *quantiles, const float *target, int C, float *grad_q,
                                double *out_loss, void *stream) {
-  if (!eb_shape_ok(0, C)) return LLA_EINVAL;
-  if (!params || !quantiles || !target || !grad_q || !out_loss) return LLA_EINVAL;
-  if (!aligned16(params) || !aligned16(quantiles) || !aligned16(grad_q) || ((uintptr_t)target & 3) || ((uintptr_t)out_loss & 7))
-    return LLA_EINVAL;
-  return launch_eb_aux(params, quantiles, target, C, grad_q, out_loss, as_stream(stream));
+  if (C & 3) return LLA_EINVAL;
+  return eb_aux_grad(params, quantiles, target, C, grad_q, out_loss, stream);
+}
+
+extern "C" int lla_eb_aux_grad_any(const float *params, const float *quantiles, const float *target, int S, float *grad_q,
+                                   double *out_loss, void *stream) {
+  return eb_aux_grad(params, quantiles, target, S, grad_q, out_loss, stream);
 }

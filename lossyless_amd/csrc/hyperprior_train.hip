@@ -8,7 +8,7 @@
 //
 //   lla_eb_side_pass          s_hat = x + u, sum rate_s, scale d rate_s / dx and scale d rate_s / d(the 58 S numbers):
 //                             side_pass_kernel (forward + backward) then side_finish_kernel
-//   lla_eb_aux_grad_any       eb_aux_kernel (eb_train.hip, through launch_eb_aux) for any channel count
+//   (lla_eb_aux_grad_any, the side bottleneck's auxiliary loss, is in eb_train.hip next to eb_aux_kernel)
 //   lla_gaussian_train_pass   y, sum dist, sum rate_z, scale d rate_z / d(scales | means | y), d dist / d scaling:
 //                             gaussian_pass_kernel then gaussian_finish_kernel; with gp == NULL the prologue alone (y)
 //   lla_affine_grad           the gradients of scaling and biasing from d loss / d y: affine_pass_kernel, affine_finish_kernel
@@ -51,12 +51,7 @@ __global__ __launch_bounds__(64) void side_pass_kernel(const float *__restrict__
   EbNet n;
   eb_load(n, params, f.C, c);
   EbAcc acc;
-#pragma unroll
-  for (int k = 0; k < kMat; ++k) acc.sp[k] = 0.f;
-#pragma unroll
-  for (int k = 0; k < kBias; ++k) acc.b[k] = 0.f;
-#pragma unroll
-  for (int k = 0; k < kFac; ++k) acc.tf[k] = 0.f;
+  eb_acc_zero(acc);
   float sum_rate = 0.f;
   float xn = w < f.B ? x[(size_t)w * ldx + c] : 0.f;
   for (int i = w; i < f.B; i += f.W) {
@@ -65,55 +60,15 @@ __global__ __launch_bounds__(64) void side_pass_kernel(const float *__restrict__
     const float u = noise_at((uint64_t)i * (uint64_t)f.C + (uint64_t)c, f.step, kSideTag, f.k0, f.k1);
     const float v = xi + u;
     s_hat[(size_t)i * lds + c] = v;
-    EbAct lo, up;
-    const float lower = eb_forward(n, v - 0.5f, lo), upper = eb_forward(n, v + 0.5f, up);
-    const float sgn = -sign_f(lower + upper);
-    const float a = sgn * upper, b = sgn * lower;
-    const float diff = sigmoid_diff(a, b);
-    const float lik = fmaxf(fabsf(diff), kLikBound);
-    sum_rate += -logf(lik);
-    const float gl = -1.f / lik * sign_f(diff) * sgn;
-    const float dv = eb_backward<true>(n, up, gl * sigmoid_slope(a), acc) + eb_backward<true>(n, lo, -gl * sigmoid_slope(b), acc);
-    dx[(size_t)i * ldd + c] = f.scale * dv;
+    dx[(size_t)i * ldd + c] = f.scale * eb_lik_step(n, v, acc, sum_rate);
   }
   float *out = part + (size_t)w * kSidePart * f.C + c;
-#pragma unroll
-  for (int k = 0; k < kMat; ++k) out[(size_t)k * f.C] = acc.sp[k] * sigmoid_f(params[(size_t)k * f.C + c]);
-#pragma unroll
-  for (int k = 0; k < kBias; ++k) out[(size_t)(kMat + k) * f.C] = acc.b[k];
-#pragma unroll
-  for (int k = 0; k < kFac; ++k) out[(size_t)(kMat + kBias + k) * f.C] = acc.tf[k] * (1.f - n.tf[k] * n.tf[k]);
+  eb_store_grads(n, acc, params, f.C, c, out, 0);
   out[(size_t)kNet * f.C] = sum_rate;
 }
 
-// The scalar sums of a pass, by the LAST workgroup (256 threads) of its finish kernel: for q < Q, out[q] = the sum over the
-// channels of (the double sum over the walkers, in walker order, of partial row first + q); thread t adds the channels t,
-// t + 256, ... in ascending order and thread 0 .. Q-1 adds the 256 thread sums of its q in thread order.
-template <int Q>
-__device__ __forceinline__ void channel_totals(const float *__restrict__ part, size_t slab, int first, int C, int W,
-                                               double *__restrict__ out, double (*red)[256]) {
-  double tot[Q];
-#pragma unroll
-  for (int q = 0; q < Q; ++q) tot[q] = 0.0;
-  for (int c = threadIdx.x; c < C; c += 256) {
-#pragma unroll
-    for (int q = 0; q < Q; ++q) {
-      double col = 0.0;
-      for (int w = 0; w < W; ++w) col += (double)part[w * slab + (size_t)(first + q) * C + c];
-      tot[q] += col;
-    }
-  }
-#pragma unroll
-  for (int q = 0; q < Q; ++q) red[q][threadIdx.x] = tot[q];
-  __syncthreads();
-  if (threadIdx.x < Q) {
-    double sum = 0.0;
-    for (int t = 0; t < 256; ++t) sum += red[threadIdx.x][t];
-    out[threadIdx.x] = sum;
-  }
-}
-
-// grads [58 S]: scale times the double sum of the element's W partials, rounded once.  The last workgroup: sum rate.
+// grads [58 S]: scale times the double sum of the element's W partials, rounded once.  The last workgroup: sum rate
+// (channel_totals and walker_sum: eb_net.h).
 __global__ __launch_bounds__(256) void side_finish_kernel(const float *__restrict__ part, float *__restrict__ grads,
                                                           double *__restrict__ out_sum, int C, int W, float scale) {
   __shared__ double red[1][256];
@@ -124,9 +79,7 @@ __global__ __launch_bounds__(256) void side_finish_kernel(const float *__restric
   }
   const size_t at = (size_t)blockIdx.x * 256 + threadIdx.x;      // element of [58][S]: the partial rows have the same order
   if (at >= (size_t)kNet * C) return;
-  double sum = 0.0;
-  for (int w = 0; w < W; ++w) sum += (double)part[w * slab + at];
-  grads[at] = (float)((double)scale * sum);
+  grads[at] = (float)((double)scale * walker_sum(part, slab, at, W));
 }
 
 // --------------------------------------------------------------------------------------------------------- Gaussian pass
@@ -202,9 +155,7 @@ __global__ __launch_bounds__(256) void gaussian_finish_kernel(const float *__res
   }
   const int c = blockIdx.x * 256 + threadIdx.x;
   if (c >= C) return;
-  double sum = 0.0;
-  for (int w = 0; w < W; ++w) sum += (double)part[w * slab + c];
-  g_dist[c] = (float)sum;
+  g_dist[c] = (float)walker_sum(part, slab, c, W);
 }
 
 // ----------------------------------------------------------------------------------------------------------- affine grad
@@ -228,6 +179,7 @@ __global__ __launch_bounds__(256) void affine_finish_kernel(const float *__restr
                                                             int W) {
   const int c = blockIdx.x * 256 + threadIdx.x;
   if (c >= C) return;
+  // walker_sum's loop, for two sums in ONE walk: a walk waits for each walker's load in turn, and two walks would wait twice
   double gs = 0.0, gb = 0.0;
   for (int w = 0; w < W; ++w) {
     gs += (double)part[(size_t)w * 2 * C + c];
@@ -238,7 +190,6 @@ __global__ __launch_bounds__(256) void affine_finish_kernel(const float *__restr
   g_biasing[c] = (float)((double)expf(scaling[c]) * gb);
 }
 
-constexpr int kMaxWidth = 1 << 20;
 bool width_ok(int B, int C) { return B >= 0 && C > 0 && C <= kMaxWidth; }
 bool pitch_ok(int ld, int C) { return ld >= C && ld <= 2 * kMaxWidth; }
 
@@ -272,15 +223,6 @@ extern "C" int lla_eb_side_pass(const float *x, int ldx, int B, int S, const flo
   const int blocks = (int)(((size_t)kNet * S + 255) / 256) + 1;
   side_finish_kernel<<<blocks, 256, 0, st>>>(part, grads, out_sum, S, W, scale);
   return check_launch();
-}
-
-extern "C" int lla_eb_aux_grad_any(const float *params, const float *quantiles, const float *target, int S, float *grad_q,
-                                   double *out_loss, void *stream) {
-  if (!width_ok(0, S)) return LLA_EINVAL;
-  if (!params || !quantiles || !target || !grad_q || !out_loss) return LLA_EINVAL;
-  if (!aligned16(params) || !aligned16(quantiles) || !aligned16(grad_q) || ((uintptr_t)target & 3) || ((uintptr_t)out_loss & 7))
-    return LLA_EINVAL;
-  return launch_eb_aux(params, quantiles, target, S, grad_q, out_loss, as_stream(stream));
 }
 
 extern "C" size_t lla_gaussian_train_pass_workspace_bytes(int B, int C) {

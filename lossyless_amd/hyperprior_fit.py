@@ -29,49 +29,22 @@ import numpy as np
 import torch
 
 from . import _lib
-from .bottleneck_fit import (FILTERS, LIK_BOUND, N_BIAS, N_MAT, N_NET, NOISE_TAG, BottleneckFit, _sigmoid_diff, _sigmoid_slope,
-                             _twin_backward, _twin_forward, _twin_net, beta_schedule, pack_network, twin_aux, unpack_network_)
-from .probe import _Adam, _adamw, philox4x32_10
+from .bottleneck_fit import (FILTERS, LIK_BOUND, N_NET, NOISE_TAG, BottleneckFit, _Engine, hyperprior_noise, pack_network, twin_aux,
+                             twin_likelihood, unpack_network_)
+from .probe import _adamw, _adamw_step, _mlp_backward, _mlp_forward
 from .rates import BASE_LOG, HRateHyperprior
 
-SIDE_TAG = 0x73696465
+SIDE_TAG = 0x73696465                   # fourth counter word of the side information's noise (``hyperprior_noise(..., tag)``)
 _INV_SQRT2, _INV_SQRT2PI = 2.0 ** -0.5, 1.0 / math.sqrt(2.0 * math.pi)
-
-
-def hyperprior_noise(seed, step, rows, cols, tag=NOISE_TAG):
-    """The noise of ``lla_gaussian_train_pass`` (``tag`` 0x6e6f6973) and ``lla_eb_side_pass`` (``SIDE_TAG``) -> fp32 tensor
-    [rows, cols] on the CPU, any ``cols``: element f = i cols + c is word f % 4 of Philox4x32-10 with key (seed_lo, seed_hi) and
-    counter (f / 4 lo, f / 4 hi, step, tag), as ``u = float32(word >> 8) 2^-24 - 0.5``.  For ``cols % 4 == 0`` and the first tag
-    this is :func:`bottleneck_noise`."""
-    seed, n = int(seed) & 0xFFFFFFFFFFFFFFFF, int(rows) * int(cols)
-    e = np.arange(-(-n // 4), dtype=np.uint64)
-    counter = np.stack([e & np.uint64(0xFFFFFFFF), e >> np.uint64(32), np.full_like(e, int(step) & 0xFFFFFFFF),
-                        np.full_like(e, int(tag) & 0xFFFFFFFF)], -1)
-    words = philox4x32_10(counter, np.array([seed & 0xFFFFFFFF, seed >> 32], dtype=np.uint64)).reshape(-1)[:n]
-    u = (words >> np.uint32(8)).astype(np.float32) * np.float32(2.0 ** -24) - np.float32(0.5)
-    return torch.from_numpy(u.reshape(int(rows), int(cols)))
 
 
 # ------------------------------------------------------------------------------------------ the float64 twin of the kernels
 def twin_side_pass(x, net, u, scale=1.0):
     """``lla_eb_side_pass`` in the dtype of ``net`` [58, S] on x [B, S] and noise u -> (s_hat, dx = scale d rate / dx,
-    grads [58, S] = scale d rate / d net, sum rate).  Backward by hand."""
-    dt = net.dtype
-    sp, b, tf = _twin_net(net)
-    v = x.to(dt) + u.to(dt)
-    lower, act_lo = _twin_forward(sp, b, tf, v - 0.5)
-    upper, act_up = _twin_forward(sp, b, tf, v + 0.5)
-    sgn = -torch.sign(lower + upper)
-    a, bb = sgn * upper, sgn * lower
-    diff = _sigmoid_diff(a, bb)
-    lik = diff.abs().clamp(min=LIK_BOUND)
-    gl = -1 / lik * torch.sign(diff) * sgn
-    acc = (torch.zeros_like(sp), torch.zeros_like(b), torch.zeros_like(tf))
-    dv = _twin_backward(sp, tf, act_up, gl * _sigmoid_slope(a), acc) + _twin_backward(sp, tf, act_lo, -gl * _sigmoid_slope(bb), acc)
-    M = net[:N_MAT]
-    e = torch.exp(-M.abs())
-    grads = torch.cat([acc[0] * torch.where(M <= 0, e / (1 + e), 1 / (1 + e)), acc[1], acc[2] * (1 - tf * tf)], 0)
-    return v, scale * dv, scale * grads, -torch.log(lik).sum()
+    grads [58, S] = scale d rate / d net, sum rate).  Backward by hand (``bottleneck_fit.twin_likelihood``)."""
+    v = x.to(net.dtype) + u.to(net.dtype)
+    dv, grads, rate = twin_likelihood(net, v)
+    return v, scale * dv, scale * grads, rate
 
 
 def twin_gaussian_pass(z, scaling, biasing, gp, u, bound, scale=1.0):
@@ -109,26 +82,6 @@ def twin_affine_grad(dy_total, y, scaling, g_dist=None, add_scale=0.0):
     return gs, torch.exp(scaling) * dy_total.sum(0)
 
 
-def _mlp_forward(Ws, bs, x):
-    """-> (output, [x, h_1, h_2]): h = relu(h W^T + b) (``lla_gemm_f32``, relu = 1), then the last Linear."""
-    hs = [x]
-    for W, b in zip(Ws[:-1], bs[:-1]):
-        a = hs[-1] @ W.T + b
-        hs.append(torch.where(a > 0, a, torch.zeros((), dtype=a.dtype)))
-    return hs[-1] @ Ws[-1].T + bs[-1], hs
-
-
-def _mlp_backward(Ws, hs, delta):
-    """The output's gradient -> (dW per layer, db per layer, the input's gradient): ``lla_gemm_f32_tn`` / ``_nn``."""
-    gW, gb = [None] * len(Ws), [None] * len(Ws)
-    for l in range(len(Ws) - 1, -1, -1):
-        gW[l], gb[l] = delta.T @ hs[l], delta.sum(0)
-        delta = delta @ Ws[l]
-        if l > 0:
-            delta = torch.where(hs[l] > 0, delta, torch.zeros((), dtype=delta.dtype))
-    return gW, gb, delta
-
-
 def twin_step_gradients(P, z, u_s, u_z, bound, beta_t):
     """The main optimiser's gradients of ``mean dist + beta_t mean rate`` for the parameters P (dict: scaling, biasing, net,
     side_W, side_b, z_W, z_b) in the order of a device step -> (dict of gradients, (sum dist, sum rate_z, sum rate_s))."""
@@ -139,8 +92,8 @@ def twin_step_gradients(P, z, u_s, u_z, bound, beta_t):
     s_hat, dx, g_net, rate_s = twin_side_pass(x, P["net"], u_s, scale)
     gp, hs_z = _mlp_forward(P["z_W"], P["z_b"], s_hat)
     _, dgp, dy, g_dist, dist, rate_z = twin_gaussian_pass(z, P["scaling"], P["biasing"], gp, u_z, bound, scale)
-    gW_z, gb_z, ds = _mlp_backward(P["z_W"], hs_z, dgp)
-    gW_s, gb_s, dy_enc = _mlp_backward(P["side_W"], hs_s, dx + ds)
+    gW_z, gb_z, ds = _mlp_backward(P["z_W"], hs_z, dgp, below=True)
+    gW_s, gb_s, dy_enc = _mlp_backward(P["side_W"], hs_s, dx + ds, below=True)
     g_s, g_b = twin_affine_grad(dy + dy_enc, y, P["scaling"], g_dist, float(np.float32(1.0 / B)))
     return dict(scaling=g_s, biasing=g_b, net=g_net, side_W=gW_s, side_b=gb_s, z_W=gW_z, z_b=gb_z), (dist, rate_z, rate_s)
 
@@ -154,17 +107,17 @@ def _flatten(P):
     return out
 
 
-class _TwinEngine:
-    """One training step in float64 on the host: the CPU path of ``HyperpriorFit`` and the oracle of its GPU tests."""
+class _TwinEngine(_Engine):
+    """One training step in float64 on the host: the CPU path of ``HyperpriorFit`` and the oracle of its GPU tests.  A step's
+    log: sum dist, sum rate_z, sum rate_s, aux."""
 
     def __init__(self, P, q, target, bound, adam, adam_coder, seed):
+        super().__init__(4, adam, adam_coder, seed)
         cp = lambda v: [t.double().clone() for t in v] if isinstance(v, (list, tuple)) else v.double().clone()
         self.P, self.q, self.target, self.bound = {k: cp(v) for k, v in P.items()}, q.double().clone(), target.double(), float(bound)
         self.C, self.S = self.P["scaling"].shape[0], self.P["net"].shape[1]
-        self.adam, self.adam_coder, self.seed, self.t = adam, adam_coder, int(seed), 0
         self.mom = [(torch.zeros_like(p), torch.zeros_like(p)) for p in _flatten(self.P)]
         self.mom_q = [(torch.zeros_like(self.q), torch.zeros_like(self.q))]
-        self.log = []
 
     def step(self, z, step, beta_t):
         B = z.shape[0]
@@ -177,11 +130,6 @@ class _TwinEngine:
         _adamw([self.q], [gq], self.mom_q, self.adam_coder, self.t)
         self.log.append((float(dist), float(rate_z), float(rate_s), float(aux)))
 
-    def epoch_log(self):
-        """-> [steps, 4] doubles (sum dist, sum rate_z, sum rate_s, aux) of the steps since the last call."""
-        out, self.log = np.asarray(self.log, dtype=np.float64).reshape(-1, 4), []
-        return out
-
     def state(self):
         cp = lambda v: [t.clone() for t in v] if isinstance(v, list) else v.clone()
         return {k: cp(v) for k, v in self.P.items()}, self.q.clone()
@@ -191,15 +139,17 @@ def _pad(n, k):
     return -(-int(n) // k) * k
 
 
-class _DeviceEngine:
+class _DeviceEngine(_Engine):
     """The same step on the GPU.  Parameters, gradients and the two moments of the main optimiser each live in ONE flat fp32
     buffer -- scaling [C], biasing [C], the network [58][S], then per Linear layer the weight [out_p][in_p] and the bias [out_p],
     every piece starting on a multiple of 4 elements and every layer width padded to a multiple of 8 as ``_DeviceMLP`` pads
     (zero weights and zero biases, whose gradients are zero: AdamW leaves them zero) -- so one ``lla_adamw_step`` updates
-    everything.  The sums of a step stay on the device until ``epoch_log`` reads them (one synchronisation per epoch)."""
+    everything.  ``_forward`` and ``_backward`` stay apart from ``probe._DeviceMLP`` on purpose: EVERY width is padded here
+    and only the class width there, and the batchnorm blocks and the cross-entropy slot exist only there; one class for both
+    would be switches for all of that."""
 
     def __init__(self, P, q, target, bound, adam, adam_coder, seed, device, max_batch, steps_per_epoch):
-        self.L, self.dev = _lib.lib(), torch.device(device)
+        super().__init__(4, adam, adam_coder, seed, device, max_batch, steps_per_epoch)
         f32 = dict(dtype=torch.float32, device=self.dev)
         self.C, self.S = int(P["scaling"].shape[0]), int(P["net"].shape[1])
         C, S = self.C, self.S
@@ -225,8 +175,7 @@ class _DeviceEngine:
                     dst[:src.shape[0]].copy_(src)
         self.q, self.target = q.to(**f32).contiguous(), target.to(**f32).contiguous()
         self.gq, self.mq, self.vq = (torch.zeros_like(self.q) for _ in range(3))
-        self.bound, self.adam, self.adam_coder, self.seed, self.t = float(bound), adam, adam_coder, int(seed), 0
-        self.rows = R = max(int(max_batch), 1)
+        self.bound, R = float(bound), self.rows
         buf = lambda n: torch.zeros((R, n), **f32)
         self.y, self.dy, self.dy_enc = buf(self.Cp), buf(self.Cp), buf(self.Cp)
         self.s_hat, self.dx, self.ds = buf(self.Sp), buf(self.Sp), buf(self.Sp)
@@ -237,8 +186,6 @@ class _DeviceEngine:
         nws = max(int(self.L.lla_eb_side_pass_workspace_bytes(R, S)), int(self.L.lla_gaussian_train_pass_workspace_bytes(R, C)),
                   int(self.L.lla_affine_grad_workspace_bytes(R, C)), 16)
         self.ws = torch.empty(nws, dtype=torch.uint8, device=self.dev)
-        self.sums = torch.zeros((max(int(steps_per_epoch), 1), 4), dtype=torch.float64, device=self.dev)
-        self.n_log = 0
 
     def _views(self, flat):
         at = iter(zip(self.offsets, self.sizes))
@@ -252,11 +199,10 @@ class _DeviceEngine:
         return v
 
     # every launch is a method of its own; ``step`` is their sequence
-    def _gaussian(self, z, B, step, scale, st, full):
+    def _gaussian(self, z, code, ldz, B, step, scale, st, full):
         P, L = _lib.ptr, self.L
         slot = self.sums[self.n_log]
-        rc = L.lla_gaussian_train_pass(P(z), _lib.LLA_Z_F16 if z.dtype == torch.float16 else _lib.LLA_Z_F32,
-                                       z.stride(0) if B > 1 else self.C, B, self.C, P(self.p["scaling"]), P(self.p["biasing"]),
+        rc = L.lla_gaussian_train_pass(P(z), code, ldz, B, self.C, P(self.p["scaling"]), P(self.p["biasing"]),
                                        P(self.acts_z[2]) if full else None, self.Gp, self.bound, self.seed & 0xFFFFFFFFFFFFFFFF,
                                        int(step) & 0xFFFFFFFF, scale, P(self.dgp), P(self.y), self.Cp, P(self.dy), P(self.g_dist),
                                        P(slot), P(self.ws), st)
@@ -283,31 +229,21 @@ class _DeviceEngine:
             _lib.check(rc, "lla_gemm_f32_nn")
             delta = out
 
-    def _adamw(self, p, g, m, v, n, a, st):
-        bc1, bc2 = a.corrections(self.t)
-        rc = self.L.lla_adamw_step(_lib.ptr(p), _lib.ptr(g), _lib.ptr(m), _lib.ptr(v), n, a.lr, a.b1, a.b2, a.eps, a.wd, bc1, bc2, st)
-        _lib.check(rc, "lla_adamw_step")
-
     def step(self, z, step, beta_t):
         B, C, S, L, P = int(z.shape[0]), self.C, self.S, self.L, _lib.ptr
-        if B > self.rows or self.n_log >= self.sums.shape[0]:
-            raise ValueError("a minibatch larger, or an epoch longer, than the engine was sized for")
-        if z.dtype not in (torch.float16, torch.float32):
-            z = z.float()
-        if z.stride(1) != 1 or (B > 1 and z.stride(0) < C):
-            z = z.contiguous()
+        z, code, ldz = self._minibatch(z, C)
         _lib.require_cuda(self.flat[0], "parameters")
         scale, slot, p, g = float(beta_t) / B, self.sums[self.n_log], self.p, self.g
         with torch.cuda.device(self.dev):
             st = _lib.stream_ptr(self.dev)
-            self._gaussian(z, B, step, scale, st, full=False)                                   # y
+            self._gaussian(z, code, ldz, B, step, scale, st, full=False)                        # y
             self._forward(p["side_W"], p["side_b"], self.dims_s, self.y, self.acts_s, B, st)
             rc = L.lla_eb_side_pass(P(self.acts_s[2]), self.Sp, B, S, P(p["net"]), self.seed & 0xFFFFFFFFFFFFFFFF,
                                     int(step) & 0xFFFFFFFF, scale, P(self.s_hat), self.Sp, P(self.dx), self.Sp, P(g["net"]),
                                     P(slot[2:]), P(self.ws), st)
             _lib.check(rc, "lla_eb_side_pass")
             self._forward(p["z_W"], p["z_b"], self.dims_z, self.s_hat, self.acts_z, B, st)
-            self._gaussian(z, B, step, scale, st, full=True)
+            self._gaussian(z, code, ldz, B, step, scale, st, full=True)
             self._backward(p["z_W"], g["z_W"], g["z_b"], self.dims_z, self.s_hat, self.acts_z, self.dgp, self.delta_z, self.ds, B, st)
             self.dx[:B].add_(self.ds[:B])
             self._backward(p["side_W"], g["side_W"], g["side_b"], self.dims_s, self.y, self.acts_s, self.dx, self.delta_s,
@@ -317,15 +253,11 @@ class _DeviceEngine:
                                    P(g["scaling"]), P(g["biasing"]), P(self.ws), st)
             _lib.check(rc, "lla_affine_grad")
             self.t += 1
-            self._adamw(self.flat[0], self.flat[1], self.flat[2], self.flat[3], self.n, self.adam, st)
+            _adamw_step(L, *self.flat, self.adam, *self.adam.corrections(self.t), st)
             rc = L.lla_eb_aux_grad_any(P(p["net"]), P(self.q), P(self.target), S, P(self.gq), P(slot[3:]), st)
             _lib.check(rc, "lla_eb_aux_grad_any")
-            self._adamw(self.q, self.gq, self.mq, self.vq, self.q.numel(), self.adam_coder, st)
+            _adamw_step(L, self.q, self.gq, self.mq, self.vq, self.adam_coder, *self.adam_coder.corrections(self.t), st)
         self.n_log += 1
-
-    def epoch_log(self):
-        out, self.n_log = self.sums[:self.n_log].cpu().numpy().copy(), 0
-        return out
 
     def state(self):
         """-> (parameters without their padding, quantiles) on the CPU."""
@@ -405,10 +337,8 @@ class HyperpriorFit(BottleneckFit):
         with torch.random.fork_rng(devices=[]):
             m = HRateHyperprior(int(z_dim), factor_dim=self.factor_dim, side_z_dim=self.side_z_dim,
                                 kwargs_ent_bottleneck=dict(init_scale=self.init_scale, filters=FILTERS))
+        self._draw_biases(m.entropy_bottleneck, g)
         with torch.no_grad():
-            for i in range(5):
-                b = getattr(m.entropy_bottleneck, f"_bias{i}")
-                b.copy_(torch.empty(b.shape).uniform_(-0.5, 0.5, generator=g))
             for mlp in (m.side_encoder, m.z_encoder):
                 for lin in _linears(mlp):
                     a = math.sqrt(6.0 / lin.weight.shape[1])
@@ -416,53 +346,18 @@ class HyperpriorFit(BottleneckFit):
                     lin.bias.zero_()
         return m
 
-    def fit(self, Z):
-        if hasattr(Z, "batches"):
-            N, C, dev = len(Z), int(Z.z_dim), torch.device(Z.device)
-        else:
-            if not isinstance(Z, torch.Tensor):
-                Z = torch.from_numpy(np.ascontiguousarray(Z))
-            if Z.dim() != 2 or Z.shape[0] < 1:
-                raise ValueError("Z must be a non-empty [N, C] matrix")
-            N, C, dev = int(Z.shape[0]), int(Z.shape[1]), Z.device
-        g = torch.Generator().manual_seed(self.seed)
-        m = self.initial_estimator(C, g)
+    # ---- the three hooks of ``BottleneckFit.fit``
+    def _engine(self, m, adam, adam_coder, dev, max_batch, steps_per_epoch):
         P, q = pack_parameters(m)
         target = m.entropy_bottleneck.target
         bound = float(m.gaussian_conditional.lower_bound_scale.bound.float().item())
-        steps_per_epoch = -(-N // self.batch_size)
-        betas = beta_schedule(self.beta, self.epochs * steps_per_epoch, self.beta_anneal)
-        adam = _Adam(self.lr, self.weight_decay, (0.9, 0.999), 1e-8)
-        adam_coder = _Adam(self.lr_coder, self.weight_decay_coder, (0.9, 0.999), 1e-8)
         if dev.type == "cuda":
-            eng = _DeviceEngine(P, q, target, bound, adam, adam_coder, self.seed, dev, min(self.batch_size, N), steps_per_epoch)
-        else:
-            eng = _TwinEngine(P, q, target, bound, adam, adam_coder, self.seed)
-        curves = {k: [] for k in ("rate", "side_rate", "distortion", "loss", "aux", "beta")}
-        step = 0
-        for epoch in range(self.epochs):
-            adam.lr, adam_coder.lr = self.lr_curve_[epoch], self._lr_coder_curve[epoch]
-            for zb in self._batches(Z, g):
-                eng.step(zb, step, betas[step])
-                step += 1
-            log = eng.epoch_log()
-            rate = log[:, 1] + log[:, 2]
-            curves["rate"].append(float(rate.sum() / N / math.log(BASE_LOG)))
-            curves["side_rate"].append(float(log[:, 2].sum() / N / math.log(BASE_LOG)))
-            curves["distortion"].append(float(log[:, 0].sum() / N))
-            curves["loss"].append(float((log[:, 0] + self.beta * rate).sum() / N))
-            curves["aux"].append(float(log[:, 3].mean()))
-            curves["beta"].append(float(betas[step - 1]))
-        for k, v in curves.items():
-            setattr(self, f"{k}_curve_", v)
-        unpack_parameters_(m, *eng.state())
-        m.eval()
-        m.update(force=True)
-        self.engine_ = "device" if dev.type == "cuda" else "twin"
-        self.rate_estimator_ = m.to(dev) if dev.type == "cuda" else m
-        return self
+            return _DeviceEngine(P, q, target, bound, adam, adam_coder, self.seed, dev, max_batch, steps_per_epoch)
+        return _TwinEngine(P, q, target, bound, adam, adam_coder, self.seed)
 
-    def state_dict(self):
-        """What the reference's module saves, with the key set of ``synthetic_hyperprior_state_dict``: loads unchanged into
-        ``hubconf.clip_hyperprior_compressor`` and, ``strict=True``, into ``HRateHyperprior(z_dim)``."""
-        return {k: v.detach().cpu().clone() for k, v in self.rate_estimator_.state_dict().items()}
+    def _curve_entries(self, log, N):
+        return dict(self._rate_entries(log[:, 0], log[:, 1] + log[:, 2], log[:, 3], N),
+                    side_rate=float(log[:, 2].sum() / N / math.log(BASE_LOG)))
+
+    def _store(self, m, state):
+        unpack_parameters_(m, *state)

@@ -1258,6 +1258,36 @@ def _adamw(params, grads, moments, a, t):
         p.sub_((a.lr / bc1) * m / (v.sqrt() / bc2 ** 0.5 + a.eps))
 
 
+def _adamw_step(L, p, g, m, v, a, bc1, bc2, st):
+    """``lla_adamw_step`` on the device: AdamW with the hyper-parameters ``a`` and the bias corrections (bc1, bc2) on the whole
+    of the fp32 buffers p (parameters), g (gradients), m and v (moments), in place, on stream ``st``."""
+    rc = L.lla_adamw_step(_lib.ptr(p), _lib.ptr(g), _lib.ptr(m), _lib.ptr(v), p.numel(), a.lr, a.b1, a.b2, a.eps, a.wd, bc1, bc2, st)
+    _lib.check(rc, "lla_adamw_step")
+
+
+def _mlp_forward(Ws, bs, x, pre=None):
+    """-> (output, [x, h_1, ..., h_L]): h = relu(h W^T + b) (``lla_gemm_f32``, relu = 1), then the last Linear.  ``pre``, a
+    list, receives the hidden pre-activations."""
+    hs = [x]
+    for W, b in zip(Ws[:-1], bs[:-1]):
+        a = hs[-1] @ W.T + b
+        if pre is not None:
+            pre.append(a)
+        hs.append(torch.where(a > 0, a, torch.zeros((), dtype=a.dtype)))
+    return hs[-1] @ Ws[-1].T + bs[-1], hs
+
+
+def _mlp_backward(Ws, hs, delta, below=False):
+    """The output's gradient -> (dW per layer, db per layer, the input's gradient -- computed only with ``below``, else None):
+    ``lla_gemm_f32_tn``, and ``lla_gemm_f32_nn`` with the ReLU mask of the layer below."""
+    gW, gb = [None] * len(Ws), [None] * len(Ws)
+    for l in range(len(Ws) - 1, -1, -1):
+        gW[l], gb[l] = delta.T @ hs[l], delta.sum(0)
+        if l > 0:
+            delta = torch.where(hs[l] > 0, delta @ Ws[l], torch.zeros((), dtype=delta.dtype))
+    return gW, gb, delta @ Ws[0] if below else None
+
+
 class _Twin:
     """What the two float64 twins share: the AdamW update of ``_params()`` and the sums of an epoch.  With ``step(x, y)``
     and ``fitted(n_out)`` of its own a twin has the interface of the device engine (``_DeviceMLP``)."""
@@ -1292,13 +1322,7 @@ class _TwinMLP(_Twin):
     def forward(self, x, pre=None):
         """-> (logits, [x, h_1, ..., h_L]): h = relu(h W^T + b) (lla_gemm_f32, relu = 1), then the last Linear.  ``pre``, a
         list, receives the hidden pre-activations."""
-        hs = [x.to(torch.float64)]
-        for W, b in zip(self.Ws[:-1], self.bs[:-1]):
-            a = hs[-1] @ W.T + b
-            if pre is not None:
-                pre.append(a)
-            hs.append(torch.where(a > 0, a, torch.zeros((), dtype=torch.float64)))
-        return hs[-1] @ self.Ws[-1].T + self.bs[-1], hs
+        return _mlp_forward(self.Ws, self.bs, x.to(torch.float64), pre)
 
     @staticmethod
     def xent(s, y):
@@ -1314,11 +1338,7 @@ class _TwinMLP(_Twin):
         """-> (loss sum, rows right, dW per layer, db per layer) of the mean cross-entropy of the minibatch."""
         s, hs = self.forward(x)
         delta, loss, right = self.xent(s, y)
-        gW, gb = [None] * len(self.Ws), [None] * len(self.Ws)
-        for l in range(len(self.Ws) - 1, -1, -1):
-            gW[l], gb[l] = delta.T @ hs[l], delta.sum(0)                     # lla_gemm_f32_tn
-            if l > 0:                                                        # lla_gemm_f32_nn with the ReLU mask
-                delta = torch.where(hs[l] > 0, delta @ self.Ws[l], torch.zeros((), dtype=torch.float64))
+        gW, gb, _ = _mlp_backward(self.Ws, hs, delta)                         # (nothing reads the gradient below layer 0)
         return loss, right, gW, gb
 
     def step(self, x, y):
@@ -1447,10 +1467,7 @@ class _DeviceMLP:
         _lib.check(rc, "lla_bn_bwd")
 
     def adamw(self, bc1, bc2, st):
-        P, a = _lib.ptr, self.adam
-        rc = self.L.lla_adamw_step(P(self.flat[0]), P(self.flat[1]), P(self.flat[2]), P(self.flat[3]), self.n, a.lr, a.b1, a.b2,
-                                   a.eps, a.wd, bc1, bc2, st)
-        _lib.check(rc, "lla_adamw_step")
+        _adamw_step(self.L, *self.flat, self.adam, bc1, bc2, st)
 
     def step(self, z, y):
         """One training step on the minibatch (z, y int32 class indexes), the epoch's next."""
