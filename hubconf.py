@@ -65,12 +65,16 @@ clip_compressor_b001 = _entry("b001", 1e-2)
 clip_compressor_b01 = _entry("b01", 1e-1)
 
 
-def clip_hyperprior_compressor(state_dict, device=_ON, **kwargs):
+def clip_hyperprior_compressor(state_dict, device=_ON, coded_means="scales", **kwargs):
     """CLIP ViT-B/32 + scale-hyperprior compressor (the model behind the reference's headline table), MI355X kernels.
 
     state_dict   : what the reference's ``HRateHyperprior`` saves (``main.py`` training), as a dict or a path to it.  No
                    hyperprior checkpoint ships with the reference, so there is nothing to fetch:
                    ``lossyless_amd.HyperpriorFit(beta).fit(Z).state_dict()`` trains one on frozen features.
+    coded_means  : ``"scales"`` (default; the reference's coder, which codes with the scales in the means' place) or
+                   ``"predicted"`` (opt-in: code with the means the model was trained with -- a lower rate for a model of
+                   one's own, not the reference's format).  The file does not record the mode: one written in one mode
+                   and read in the other, like one read with another state dict, decodes to wrong values without an error.
     device, clip_weights, gpu_preprocess, other kwargs : as for ``clip_compressor_b005``; forwarded to
                    ``lossyless_amd.HyperpriorClipCompressor``
 
@@ -78,7 +82,7 @@ def clip_hyperprior_compressor(state_dict, device=_ON, **kwargs):
     ``[z_strings, side_z_strings]``, the ``.bin`` file holds two records per image, and ``decompress_dataset`` decodes on
     the GPU (``is_cpu=True`` raises: the coding-table rows come from an MLP evaluated on the fp32 matrix cores).
     """
-    model = _HyperpriorCompressor(pretrained_state_dict=state_dict, device=device, **kwargs)
+    model = _HyperpriorCompressor(pretrained_state_dict=state_dict, device=device, coded_means=coded_means, **kwargs)
     return model, model.preprocess
 
 

@@ -304,6 +304,54 @@ int lla_gaussian_decode_gather(const uint8_t *payload, const uint64_t *off, int 
  * and in global memory otherwise (same results): a caller that depends on the LDS path checks this. */
 size_t lla_gaussian_decode_gather_lds_bytes(int C, int T, int W, int z_dtype, size_t *front);
 
+/* The three conditional entry points with the PREDICTED means: opt-in, never what a reference container was coded with.
+ * The reference trains the conditional model on a likelihood centred at the predicted means (the second half of the
+ * z_encoder output, lossyless/rates.py:647-650) but codes with the scales in their place (rates.py:689-696 overwrite
+ * means_hat with scales_hat); the entry points above reproduce the latter.  These depart from rates.py:689-696 on
+ * purpose and code with the means the likelihood of rates.py:647-650 belongs to.  Per element, every operation rounded
+ * to fp32 on its own:
+ *   z_in  = (float(z) + bias) * exp_scale
+ *   row   = as above, from scales[b*ld_scales + c] alone: the row never depends on the mean
+ *   mean  = means[b*ld_means + c]
+ *   sym   = int(rint(z_in - mean))                      (encode)
+ *   z_hat = (float(sym) + mean) / exp_scale - bias      (decode, gather)
+ * means [dev] fp32, ld_means >= C ELEMENTS; a caller passes means = scales + C, ld_means = ld_scales to read the z_encoder
+ * output where it lies.  Rows are fetched with 16-byte loads where the row (the matrix, for the gather) is 16-byte
+ * aligned, element by element otherwise, independently of the scales' alignment.  means == NULL or ld_means < C:
+ * LLA_EINVAL, no launch.  means == scales with ld_means == ld_scales gives the bytes / values of the entry point
+ * without means.  Everything else -- arguments, statuses, bounds on every read -- as documented above.  The container
+ * does not record which of the two coded it: records written by one and read by the other decode to wrong values
+ * without an error. */
+
+/* lla_gaussian_quantise_encode with means (rates.py:647-650's means, not rates.py:689-696's). */
+int lla_gaussian_quantise_encode_means(const void *z, int z_dtype, int B, int C, const float *bias,
+                                       const float *exp_scale, const float *scales, size_t ld_scales,
+                                       const float *means, size_t ld_means, const float *scale_table,
+                                       float scale_bound, const int32_t *cdf, int T, int W, const int32_t *cdf_len,
+                                       const int32_t *offset, uint8_t *scratch, size_t stride, uint32_t *lengths,
+                                       int32_t *symbols_out, int32_t *indexes_out, void *stream);
+
+/* lla_gaussian_decode_dequantise with means (rates.py:647-650's means, not rates.py:689-696's). */
+int lla_gaussian_decode_dequantise_means(const uint8_t *payload, const uint64_t *off, int record_prefix, int off_first,
+                                         int off_step, int B, int C, const float *bias, const float *exp_scale,
+                                         const float *scales, size_t ld_scales, const float *means, size_t ld_means,
+                                         const float *scale_table, float scale_bound, const int32_t *cdf, int T, int W,
+                                         const int32_t *cdf_len, const int32_t *offset, float *z_hat, int32_t *status,
+                                         void *stream);
+
+/* lla_gaussian_decode_gather with means (rates.py:647-650's means, not rates.py:689-696's): `means` is indexed by the
+ * OUTPUT row b, as `scales` is.  A row whose status_in is non-zero reads neither matrix.  The means are staged in LDS
+ * next to the scales (32 KiB more in front of the packed rows): lla_gaussian_decode_gather_means_lds_bytes is this entry
+ * point's size query, with the meaning of lla_gaussian_decode_gather_lds_bytes. */
+int lla_gaussian_decode_gather_means(const uint8_t *payload, const uint64_t *off, int record_prefix, int off_first,
+                                     int off_step, int N, const int64_t *index, int B, int C, const float *bias,
+                                     const float *exp_scale, const float *scales, size_t ld_scales, const float *means,
+                                     size_t ld_means, const float *scale_table, float scale_bound, const int32_t *cdf,
+                                     int T, int W, const int32_t *cdf_len, const int32_t *offset, void *z_hat,
+                                     int z_dtype, size_t ld_out, const int32_t *status_in, int32_t *status,
+                                     void *stream);
+size_t lla_gaussian_decode_gather_means_lds_bytes(int C, int T, int W, int z_dtype, size_t *front);
+
 /* EntropyModel.dequantize + process_z_out (hub/compressor.py:111-115):
  * z_hat = (float(sym) + median) / exp_scale - bias, fp32 per operation. */
 int lla_dequantise(const int32_t *symbols, int B, int C, const float *bias,

@@ -57,6 +57,14 @@ _SIGNATURES = {
     "lla_gaussian_decode_gather": (_i, [_vp, _vp, _i, _i, _i, _i, _vp, _i, _i, _vp, _vp, _vp, _sz, _vp, ctypes.c_float, _vp,
                                         _i, _i, _vp, _vp, _vp, _i, _sz, _vp, _vp, _vp]),
     "lla_gaussian_decode_gather_lds_bytes": (_sz, [_i, _i, _i, _i, _vp]),
+    # (the three above + `means, ld_means` after `scales, ld_scales`)
+    "lla_gaussian_quantise_encode_means": (_i, [_vp, _i, _i, _i, _vp, _vp, _vp, _sz, _vp, _sz, _vp, ctypes.c_float, _vp, _i,
+                                                _i, _vp, _vp, _vp, _sz, _vp, _vp, _vp, _vp]),
+    "lla_gaussian_decode_dequantise_means": (_i, [_vp, _vp, _i, _i, _i, _i, _i, _vp, _vp, _vp, _sz, _vp, _sz, _vp,
+                                                  ctypes.c_float, _vp, _i, _i, _vp, _vp, _vp, _vp, _vp]),
+    "lla_gaussian_decode_gather_means": (_i, [_vp, _vp, _i, _i, _i, _i, _vp, _i, _i, _vp, _vp, _vp, _sz, _vp, _sz, _vp,
+                                              ctypes.c_float, _vp, _i, _i, _vp, _vp, _vp, _i, _sz, _vp, _vp, _vp]),
+    "lla_gaussian_decode_gather_means_lds_bytes": (_sz, [_i, _i, _i, _i, _vp]),
     "lla_rans_decode_gather_host": (_i, [_vp, _vp, _i, _i, _vp, _i, _i, _vp, _i, _vp, _vp, _vp, _vp, _vp, _vp, _i, _sz, _vp]),
     "lla_rans_encode_indexed": (_i, [_vp, _vp, _i, _i, _vp, _i, _i, _vp, _vp, _vp, _sz, _vp, _vp]),
     "lla_rans_decode_indexed": (_i, [_vp, _vp, _i, _i, _i, _vp, _vp, _i, _i, _vp, _vp, _vp, _vp, _vp]),

@@ -791,14 +791,29 @@ __device__ __forceinline__ void scale_rows(const float *stab, int T, float bound
   }
 }
 
-template <int ZMODE>
+// Opt-in operand of the three conditional kernels: the means the coder subtracts and adds back, element (b, c) at
+// p[b*ld + c] (the second half of the z_encoder output, lossyless/rates.py:647-650).  It is a trailing parameter PACK
+// (`Means...` is empty or one MeanRows): the instantiations without it are the kernels as they were -- same arguments,
+// same kernarg layout, same instructions, the mean is the predicted scale (rates.py:694-696) -- and every use of the
+// means sits behind `if constexpr (kMeans)`.
+struct MeanRows {
+  const float *p;
+  size_t ld;
+};
+__device__ __forceinline__ const float *mean_row(size_t) { return nullptr; }
+__device__ __forceinline__ const float *mean_row(size_t b, MeanRows m) { return m.p + b * m.ld; }
+__device__ __forceinline__ size_t mean_ld() { return 0; }
+__device__ __forceinline__ size_t mean_ld(MeanRows m) { return m.ld; }
+
+template <int ZMODE, typename... Means>
 __global__ __launch_bounds__(kEncThreads) void gaussian_encode_kernel(
     const void *__restrict__ in, int B, int C, const float *__restrict__ bias,
     const float *__restrict__ exp_scale, const float *__restrict__ scales, size_t ld_scales,
     const float *__restrict__ scale_table, float scale_bound, const int32_t *__restrict__ cdf, int T, int W,
     const int32_t *__restrict__ cdf_len, const int32_t *__restrict__ offset, uint8_t *__restrict__ scratch,
     size_t stride, uint32_t *__restrict__ lengths, int32_t *__restrict__ symbols_out,
-    int32_t *__restrict__ indexes_out) {
+    int32_t *__restrict__ indexes_out, Means... means) {
+  constexpr bool kMeans = sizeof...(Means) != 0;
   extern __shared__ __attribute__((aligned(16))) uint8_t smem[];
   const AffineParams *aff = reinterpret_cast<const AffineParams *>(smem);
   const float *stab = reinterpret_cast<const float *>(smem + (size_t)C * sizeof(AffineParams));
@@ -815,19 +830,21 @@ __global__ __launch_bounds__(kEncThreads) void gaussian_encode_kernel(
   using elem = typename F::elem;
   const elem *src = reinterpret_cast<const elem *>(in) + (size_t)img * C;
   const float *sc = scales + (size_t)img * ld_scales;
+  [[maybe_unused]] const float *mn = mean_row((size_t)img, means...);
 
   uint8_t *end = scratch + (size_t)img * stride + stride;
   EncState s;
   s.x = kStateLow;
   s.wp = reinterpret_cast<uint32_t *>(end);
 
-  auto prep = [&](int c, elem raw_in, float scale, int t) {
+  auto prep = [&](int c, elem raw_in, float mean, int t) {
     const AffineParams a = aff[c];
     float zf;
     if constexpr (ZMODE == 1) zf = __half2float(raw_in);
     else zf = raw_in;
-    // (z + bias) * exp_scale - mean, three separately rounded operations; the mean IS the predicted scale, unbounded
-    const int32_t sym = quantise_one(zf, a.bias, a.es, scale);
+    // (z + bias) * exp_scale - mean, three separately rounded operations; without kMeans the mean IS the predicted
+    // scale, unbounded
+    const int32_t sym = quantise_one(zf, a.bias, a.es, mean);
     if (symbols_out) symbols_out[(size_t)img * C + c] = sym;
     if (indexes_out) indexes_out[(size_t)img * C + c] = t;
     const int2 q = par[t];
@@ -839,10 +856,14 @@ __global__ __launch_bounds__(kEncThreads) void gaussian_encode_kernel(
     const float sv[1] = {sc[c]};
     int t[1];
     scale_rows<1>(stab, T, scale_bound, sv, t);
-    emit_channel(s, prep(c, src[c], sv[0], t[0]));
+    float mean = sv[0];
+    if constexpr (kMeans) mean = mn[c];
+    emit_channel(s, prep(c, src[c], mean, t[0]));
   }
   const bool vec_z = (reinterpret_cast<uintptr_t>(src) & 15u) == 0;
   const bool vec_s = (reinterpret_cast<uintptr_t>(sc) & 15u) == 0;
+  // (means = scales + C is the caller's layout: for C % 4 != 0 the two rows are not aligned alike)
+  [[maybe_unused]] const bool vec_m = (reinterpret_cast<uintptr_t>(mn) & 15u) == 0;
   for (int g = (C - tail) / G - 1; g >= 0; --g) {
     elem v[G];
     float sv[G];
@@ -863,8 +884,22 @@ __global__ __launch_bounds__(kEncThreads) void gaussian_encode_kernel(
     int t[G];
     scale_rows<G>(stab, T, scale_bound, sv, t);
     Prepared pr[G];
+    if constexpr (kMeans) {
+      float mv[G];
+      if (vec_m) {
 #pragma unroll
-    for (int k = 0; k < G; ++k) pr[k] = prep(g * G + k, v[k], sv[k], t[k]);
+        for (int k = 0; k < G; k += 4)
+          *reinterpret_cast<float4 *>(mv + k) = *reinterpret_cast<const float4 *>(mn + g * G + k);
+      } else {
+#pragma unroll
+        for (int k = 0; k < G; ++k) mv[k] = mn[g * G + k];
+      }
+#pragma unroll
+      for (int k = 0; k < G; ++k) pr[k] = prep(g * G + k, v[k], mv[k], t[k]);
+    } else {
+#pragma unroll
+      for (int k = 0; k < G; ++k) pr[k] = prep(g * G + k, v[k], sv[k], t[k]);
+    }
 #pragma unroll
     for (int k = G - 1; k >= 0; --k) emit_channel(s, pr[k]);
   }
@@ -878,13 +913,15 @@ __global__ __launch_bounds__(kEncThreads) void gaussian_encode_kernel(
 // Inverse: image i's stream is record i * off_step of `off` (off_step = 2 walks the z records of an interleaved
 // (z, side) body).  Every read is bounded by the record (refill) and by the row length (search_row); the row comes
 // from scale_rows, i.e. is in range whatever the scales hold.
+template <typename... Means>
 __global__ __launch_bounds__(kEncThreads) void gaussian_decode_kernel(
     const uint8_t *__restrict__ payload, const uint64_t *__restrict__ off, int skip, int off_step, int B, int C,
     const float *__restrict__ bias, const float *__restrict__ exp_scale, const float *__restrict__ scales,
     size_t ld_scales, const float *__restrict__ scale_table, float scale_bound,
     const int32_t *__restrict__ cdf, int T, int W, const int32_t *__restrict__ cdf_len,
     const int32_t *__restrict__ offset, float *__restrict__ z_hat, int32_t *__restrict__ status,
-    unsigned lds_bytes) {
+    unsigned lds_bytes, Means... means) {
+  constexpr bool kMeans = sizeof...(Means) != 0;
   extern __shared__ __attribute__((aligned(16))) uint8_t smem[];
   const AffineParams *aff = reinterpret_cast<const AffineParams *>(smem);
   const float *stab = reinterpret_cast<const float *>(smem + (size_t)C * sizeof(AffineParams));
@@ -909,13 +946,28 @@ __global__ __launch_bounds__(kEncThreads) void gaussian_decode_kernel(
   float sv_next[G];
 #pragma unroll
   for (int k = 0; k < G; ++k) sv_next[k] = k < C ? sc[k] : 0.f;
+  // (kMeans: the means travel with the scales, a group ahead, aligned or not as their own row is)
+  [[maybe_unused]] const float *mn = mean_row((size_t)i, means...);
+  [[maybe_unused]] float mv_next[G];
+  if constexpr (kMeans) {
+#pragma unroll
+    for (int k = 0; k < G; ++k) mv_next[k] = k < C ? mn[k] : 0.f;
+  }
   for (int c0 = 0; c0 < C; c0 += G) {
     float sv[G];
+    [[maybe_unused]] float mv[G];
     int t[G];
 #pragma unroll
     for (int k = 0; k < G; ++k) {
       sv[k] = sv_next[k];
       sv_next[k] = c0 + G + k < C ? sc[c0 + G + k] : 0.f;
+    }
+    if constexpr (kMeans) {
+#pragma unroll
+      for (int k = 0; k < G; ++k) {
+        mv[k] = mv_next[k];
+        mv_next[k] = c0 + G + k < C ? mn[c0 + G + k] : 0.f;
+      }
     }
     scale_rows<G>(stab, T, scale_bound, sv, t);
 #pragma unroll
@@ -930,7 +982,9 @@ __global__ __launch_bounds__(kEncThreads) void gaussian_decode_kernel(
         sym = decode_symbol<true>(s, cdf + (size_t)t[k] * W, min(max(cdf_len[t[k]], 3), W)) + offset[t[k]];
       }
       const AffineParams a = aff[c];
-      dst[c] = dequantise_one((float)sym, a.bias, a.es, sv[k]);   // (sym + mean) / exp_scale - bias
+      float mean = sv[k];
+      if constexpr (kMeans) mean = mv[k];
+      dst[c] = dequantise_one((float)sym, a.bias, a.es, mean);   // (sym + mean) / exp_scale - bias
     }
   }
   if (status) status[i] = s.pos > s.nwords ? 1 : 0;
@@ -953,26 +1007,31 @@ __global__ __launch_bounds__(kEncThreads) void gaussian_decode_kernel(
 // Every lane reaches every barrier; a lane without a record (past B, status_in set, index out of range, stream
 // unopenable) skips the decode and parks zeros.
 // ---------------------------------------------------------------------------
+// With means (MeanRows, see gaussian_encode_kernel) they take the scales' road through two buffers of their own, in front
+// of the scales' (+ 32 768 bytes), and a row whose status_in is set is left out of BOTH block reads.
 constexpr size_t kGatherStageBytes = (size_t)kEncThreads * kGatherG * sizeof(float);
-__host__ __device__ inline size_t gauss_gather_front(int C, int T) {
-  return ((gauss_head_bytes(C, T) + 15u) & ~(size_t)15u) + 16 + 3 * kGatherStageBytes;   // (16: the overrun vote)
+__host__ __device__ inline size_t gauss_gather_front(int C, int T, int stages = 3) {
+  return ((gauss_head_bytes(C, T) + 15u) & ~(size_t)15u) + 16 + stages * kGatherStageBytes;   // (16: the overrun vote)
 }
 
-template <typename OutT>
+template <typename OutT, typename... Means>
 __global__ __launch_bounds__(kEncThreads) void gaussian_decode_gather_kernel(
     const uint8_t *__restrict__ payload, const uint64_t *__restrict__ off, int skip, int off_first, int off_step, int N,
     const int64_t *__restrict__ index, int B, int C, const float *__restrict__ bias,
     const float *__restrict__ exp_scale, const float *__restrict__ scales, size_t ld_scales,
     const float *__restrict__ scale_table, float scale_bound, const int32_t *__restrict__ cdf, int T, int W,
     const int32_t *__restrict__ cdf_len, const int32_t *__restrict__ offset, OutT *__restrict__ out, size_t ld_out,
-    const int32_t *__restrict__ status_in, int32_t *__restrict__ status, unsigned lds_bytes) {
+    const int32_t *__restrict__ status_in, int32_t *__restrict__ status, unsigned lds_bytes, Means... means) {
+  constexpr bool kMeans = sizeof...(Means) != 0;
+  constexpr int kStages = kMeans ? 5 : 3;
   extern __shared__ __attribute__((aligned(16))) uint8_t smem[];
   const AffineParams *aff = reinterpret_cast<const AffineParams *>(smem);
   const float *stab = reinterpret_cast<const float *>(smem + (size_t)C * sizeof(AffineParams));
-  const size_t front = gauss_gather_front(C, T);     // (<= lds_bytes: checked by the launcher)
+  const size_t front = gauss_gather_front(C, T, kStages);     // (<= lds_bytes: checked by the launcher)
+  [[maybe_unused]] float4 *mstage = reinterpret_cast<float4 *>(smem + front - 5 * kGatherStageBytes);   // [2][256][kGatherG] means
   float4 *sstage = reinterpret_cast<float4 *>(smem + front - 3 * kGatherStageBytes);   // [2][256][kGatherG] scales
   float4 *stage = reinterpret_cast<float4 *>(smem + front - kGatherStageBytes);        // [256][kGatherG] values
-  int *vote = reinterpret_cast<int *>(smem + front - 3 * kGatherStageBytes - 16);
+  int *vote = reinterpret_cast<int *>(smem + front - kStages * kGatherStageBytes - 16);
   stage_gauss_head(smem, C, T, bias, exp_scale, scale_table);
   if (threadIdx.x == 0) *vote = 0;
   __syncthreads();
@@ -999,6 +1058,17 @@ __global__ __launch_bounds__(kEncThreads) void gaussian_decode_gather_kernel(
   const bool vec_ok = (reinterpret_cast<uintptr_t>(out) % (4 * sizeof(OutT)) == 0) && (ld_out % 4 == 0);
   const bool vec_in = ((reinterpret_cast<uintptr_t>(scales) & 15u) == 0) && (ld_scales % 4 == 0);
   const int rows_here = min(kEncThreads, B - row0);
+  // kMeans: bit p = row p * 64 + wr has its status_in set, and neither block read touches it
+  [[maybe_unused]] unsigned dead = 0;
+  if constexpr (kMeans) {
+    if (status_in) {
+#pragma unroll
+      for (int p = 0; p < kPasses; ++p) {
+        const int r = p * 64 + wr;
+        if (r < rows_here && status_in[row0 + r] != 0) dead |= 1u << p;
+      }
+    }
+  }
 
   // this thread's share of the scales block of the group at c0: chunk wj of rows p * 64 + wr (zeros outside B x C)
   auto fetch = [&](int c0, float4 (&q)[kPasses]) {
@@ -1008,8 +1078,35 @@ __global__ __launch_bounds__(kEncThreads) void gaussian_decode_gather_kernel(
       const int r = p * 64 + wr;
       q[p] = float4{0.f, 0.f, 0.f, 0.f};
       if (r < rows_here && c < C) {
+        if constexpr (kMeans) {
+          if ((dead >> p) & 1u) continue;
+        }
         const float *src = scales + (size_t)(row0 + r) * ld_scales + c;
         if (vec_in && c + 3 < C) {
+          q[p] = *reinterpret_cast<const float4 *>(src);
+        } else {
+          q[p].x = src[0];
+          if (c + 1 < C) q[p].y = src[1];
+          if (c + 2 < C) q[p].z = src[2];
+          if (c + 3 < C) q[p].w = src[3];
+        }
+      }
+    }
+  };
+  // ... and of the means block (kMeans), whose base may be aligned otherwise: the same walk.  (A second lambda, not one
+  // with the matrix as an argument: that form changed the register allocation of the instantiations without means.)
+  [[maybe_unused]] const float *mbase = mean_row(0, means...);
+  [[maybe_unused]] const size_t ld_means = mean_ld(means...);
+  [[maybe_unused]] const bool vec_mn = ((reinterpret_cast<uintptr_t>(mbase) & 15u) == 0) && (ld_means % 4 == 0);
+  [[maybe_unused]] auto fetch_means = [&](int c0, float4 (&q)[kPasses]) {
+    const int c = c0 + 4 * wj;
+#pragma unroll
+    for (int p = 0; p < kPasses; ++p) {
+      const int r = p * 64 + wr;
+      q[p] = float4{0.f, 0.f, 0.f, 0.f};
+      if (r < rows_here && c < C && !((dead >> p) & 1u)) {
+        const float *src = mbase + (size_t)(row0 + r) * ld_means + c;
+        if (vec_mn && c + 3 < C) {
           q[p] = *reinterpret_cast<const float4 *>(src);
         } else {
           q[p].x = src[0];
@@ -1029,8 +1126,13 @@ __global__ __launch_bounds__(kEncThreads) void gaussian_decode_gather_kernel(
   };
 
   float4 nx[kPasses];
+  [[maybe_unused]] float4 mx[kPasses];
   fetch(0, nx);
   park(sstage, nx);
+  if constexpr (kMeans) {
+    fetch_means(0, mx);
+    park(mstage, mx);
+  }
   __syncthreads();
 
   int g = 0;
@@ -1038,6 +1140,12 @@ __global__ __launch_bounds__(kEncThreads) void gaussian_decode_gather_kernel(
     const float4 *sbuf = sstage + (size_t)(g & 1) * kEncThreads * kChunks;
     const bool more = c0 + kGatherG < C;               // (uniform)
     if (more) fetch(c0 + kGatherG, nx);                // in flight under this group's decode
+    [[maybe_unused]] const float4 *mbuf = mstage + (size_t)(g & 1) * kEncThreads * kChunks;
+    [[maybe_unused]] float4 qm;
+    if constexpr (kMeans) {
+      if (more) fetch_means(c0 + kGatherG, mx);
+      qm = mbuf[lane * kChunks + (rot & 3)];
+    }
 
     // the lane's own line, one 16-byte chunk (four channels) at a time as gaussian_decode_kernel walks a row: the rows
     // of four elements are counted together, the next chunk's scales are requested ahead of the serial decode.  (Not
@@ -1047,6 +1155,11 @@ __global__ __launch_bounds__(kEncThreads) void gaussian_decode_gather_kernel(
     for (int j = 0; j < kChunks; ++j) {
       const float sv[4] = {qs.x, qs.y, qs.z, qs.w};
       if (j + 1 < kChunks) qs = sbuf[lane * kChunks + ((j + 1 + rot) & 3)];
+      [[maybe_unused]] float mv[4];
+      if constexpr (kMeans) {
+        mv[0] = qm.x, mv[1] = qm.y, mv[2] = qm.z, mv[3] = qm.w;
+        if (j + 1 < kChunks) qm = mbuf[lane * kChunks + ((j + 1 + rot) & 3)];
+      }
       float v[4] = {0.f, 0.f, 0.f, 0.f};
       if (live) {
         int t[4];
@@ -1063,12 +1176,17 @@ __global__ __launch_bounds__(kEncThreads) void gaussian_decode_gather_kernel(
             sym = decode_symbol<true>(s, cdf + (size_t)t[k] * W, min(max(cdf_len[t[k]], 3), W)) + offset[t[k]];
           }
           const AffineParams a = aff[c];
-          v[k] = dequantise_one((float)sym, a.bias, a.es, sv[k]);   // (sym + mean) / exp_scale - bias
+          float mean = sv[k];
+          if constexpr (kMeans) mean = mv[k];
+          v[k] = dequantise_one((float)sym, a.bias, a.es, mean);   // (sym + mean) / exp_scale - bias
         }
       }
       stage[lane * kChunks + ((j + rot) & 3)] = float4{v[0], v[1], v[2], v[3]};
     }
     if (more) park(sstage + (size_t)((g + 1) & 1) * kEncThreads * kChunks, nx);
+    if constexpr (kMeans) {
+      if (more) park(mstage + (size_t)((g + 1) & 1) * kEncThreads * kChunks, mx);
+    }
     __syncthreads();
     const int c = c0 + 4 * wj;
 #pragma unroll
@@ -1469,12 +1587,15 @@ int lla_rans_decode_indexed(const uint8_t *payload, const uint64_t *off, int rec
   return check_launch();
 }
 
-int lla_gaussian_quantise_encode(const void *z, int z_dtype, int B, int C, const float *bias,
-                                 const float *exp_scale, const float *scales, size_t ld_scales,
-                                 const float *scale_table, float scale_bound, const int32_t *cdf, int T, int W,
-                                 const int32_t *cdf_len, const int32_t *offset, uint8_t *scratch, size_t stride,
-                                 uint32_t *lengths, int32_t *symbols_out, int32_t *indexes_out, void *stream) {
+// The three conditional entry points and their _means siblings share argument checks and launch; `means` = NULL is the
+// entry point without means (the kernels' instantiations with an empty pack).
+static int gaussian_encode(const void *z, int z_dtype, int B, int C, const float *bias, const float *exp_scale,
+                           const float *scales, size_t ld_scales, const float *means, size_t ld_means, bool with_means,
+                           const float *scale_table, float scale_bound, const int32_t *cdf, int T, int W,
+                           const int32_t *cdf_len, const int32_t *offset, uint8_t *scratch, size_t stride,
+                           uint32_t *lengths, int32_t *symbols_out, int32_t *indexes_out, void *stream) {
   if (B == 0) return LLA_OK;
+  if (with_means && (!means || ld_means < (size_t)(C > 0 ? C : 0))) return LLA_EINVAL;
   if (B < 0 || C <= 0 || T <= 0 || W < 3 || !z || !bias || !exp_scale || !scales || ld_scales < (size_t)C ||
       !scale_table || !cdf || !cdf_len || !offset || !scratch || !lengths)
     return LLA_EINVAL;
@@ -1483,7 +1604,16 @@ int lla_gaussian_quantise_encode(const void *z, int z_dtype, int B, int C, const
   const size_t lds = gauss_head_bytes(C, T) + (size_t)T * sizeof(int2);
   if (lds > 64 * 1024) return LLA_EINVAL;
   const int grid = (B + kEncThreads - 1) / kEncThreads;
-  if (z_dtype == LLA_Z_F16)
+  const MeanRows mr{means, ld_means};
+  if (with_means && z_dtype == LLA_Z_F16)
+    gaussian_encode_kernel<1><<<grid, kEncThreads, lds, as_stream(stream)>>>(
+        z, B, C, bias, exp_scale, scales, ld_scales, scale_table, scale_bound, cdf, T, W, cdf_len, offset, scratch,
+        stride, lengths, symbols_out, indexes_out, mr);
+  else if (with_means)
+    gaussian_encode_kernel<2><<<grid, kEncThreads, lds, as_stream(stream)>>>(
+        z, B, C, bias, exp_scale, scales, ld_scales, scale_table, scale_bound, cdf, T, W, cdf_len, offset, scratch,
+        stride, lengths, symbols_out, indexes_out, mr);
+  else if (z_dtype == LLA_Z_F16)
     gaussian_encode_kernel<1><<<grid, kEncThreads, lds, as_stream(stream)>>>(
         z, B, C, bias, exp_scale, scales, ld_scales, scale_table, scale_bound, cdf, T, W, cdf_len, offset, scratch,
         stride, lengths, symbols_out, indexes_out);
@@ -1494,55 +1624,122 @@ int lla_gaussian_quantise_encode(const void *z, int z_dtype, int B, int C, const
   return check_launch();
 }
 
-int lla_gaussian_decode_dequantise(const uint8_t *payload, const uint64_t *off, int record_prefix, int off_first,
-                                   int off_step, int B, int C, const float *bias, const float *exp_scale,
-                                   const float *scales, size_t ld_scales, const float *scale_table,
-                                   float scale_bound, const int32_t *cdf, int T, int W, const int32_t *cdf_len,
-                                   const int32_t *offset, float *z_hat, int32_t *status, void *stream) {
+int lla_gaussian_quantise_encode(const void *z, int z_dtype, int B, int C, const float *bias,
+                                 const float *exp_scale, const float *scales, size_t ld_scales,
+                                 const float *scale_table, float scale_bound, const int32_t *cdf, int T, int W,
+                                 const int32_t *cdf_len, const int32_t *offset, uint8_t *scratch, size_t stride,
+                                 uint32_t *lengths, int32_t *symbols_out, int32_t *indexes_out, void *stream) {
+  return gaussian_encode(z, z_dtype, B, C, bias, exp_scale, scales, ld_scales, nullptr, 0, false, scale_table, scale_bound,
+                         cdf, T, W, cdf_len, offset, scratch, stride, lengths, symbols_out, indexes_out, stream);
+}
+
+int lla_gaussian_quantise_encode_means(const void *z, int z_dtype, int B, int C, const float *bias,
+                                       const float *exp_scale, const float *scales, size_t ld_scales,
+                                       const float *means, size_t ld_means, const float *scale_table,
+                                       float scale_bound, const int32_t *cdf, int T, int W, const int32_t *cdf_len,
+                                       const int32_t *offset, uint8_t *scratch, size_t stride, uint32_t *lengths,
+                                       int32_t *symbols_out, int32_t *indexes_out, void *stream) {
+  return gaussian_encode(z, z_dtype, B, C, bias, exp_scale, scales, ld_scales, means, ld_means, true, scale_table,
+                         scale_bound, cdf, T, W, cdf_len, offset, scratch, stride, lengths, symbols_out, indexes_out, stream);
+}
+
+static int gaussian_decode(const uint8_t *payload, const uint64_t *off, int record_prefix, int off_first, int off_step,
+                           int B, int C, const float *bias, const float *exp_scale, const float *scales,
+                           size_t ld_scales, const float *means, size_t ld_means, bool with_means,
+                           const float *scale_table, float scale_bound, const int32_t *cdf, int T, int W,
+                           const int32_t *cdf_len, const int32_t *offset, float *z_hat, int32_t *status, void *stream) {
   if (B == 0) return LLA_OK;
+  if (with_means && (!means || ld_means < (size_t)(C > 0 ? C : 0))) return LLA_EINVAL;
   if (B < 0 || C <= 0 || T <= 0 || W < 3 || !payload || !off || off_first < 0 || off_step < 1 || !bias ||
       !exp_scale || !scales || ld_scales < (size_t)C || !scale_table || !cdf || !cdf_len || !offset || !z_hat)
     return LLA_EINVAL;
   const size_t front = gauss_head_bytes(C, T);
   if (front > 32 * 1024) return LLA_EINVAL;
-  const unsigned lds = packed_rows_lds(reinterpret_cast<const void *>(gaussian_decode_kernel), front, T, W);
   const int grid = (B + kEncThreads - 1) / kEncThreads;
-  gaussian_decode_kernel<<<grid, kEncThreads, lds, as_stream(stream)>>>(
-      payload, off + off_first, record_prefix ? 4 : 0, off_step, B, C, bias, exp_scale, scales, ld_scales,
-      scale_table, scale_bound, cdf, T, W, cdf_len, offset, z_hat, status, lds);
+  if (with_means) {
+    const unsigned lds = packed_rows_lds(reinterpret_cast<const void *>(gaussian_decode_kernel<MeanRows>), front, T, W);
+    gaussian_decode_kernel<<<grid, kEncThreads, lds, as_stream(stream)>>>(
+        payload, off + off_first, record_prefix ? 4 : 0, off_step, B, C, bias, exp_scale, scales, ld_scales,
+        scale_table, scale_bound, cdf, T, W, cdf_len, offset, z_hat, status, lds, MeanRows{means, ld_means});
+  } else {
+    const unsigned lds = packed_rows_lds(reinterpret_cast<const void *>(gaussian_decode_kernel<>), front, T, W);
+    gaussian_decode_kernel<<<grid, kEncThreads, lds, as_stream(stream)>>>(
+        payload, off + off_first, record_prefix ? 4 : 0, off_step, B, C, bias, exp_scale, scales, ld_scales,
+        scale_table, scale_bound, cdf, T, W, cdf_len, offset, z_hat, status, lds);
+  }
   return check_launch();
 }
 
-size_t lla_gaussian_decode_gather_lds_bytes(int C, int T, int W, int z_dtype, size_t *front) {
+int lla_gaussian_decode_dequantise(const uint8_t *payload, const uint64_t *off, int record_prefix, int off_first,
+                                   int off_step, int B, int C, const float *bias, const float *exp_scale,
+                                   const float *scales, size_t ld_scales, const float *scale_table,
+                                   float scale_bound, const int32_t *cdf, int T, int W, const int32_t *cdf_len,
+                                   const int32_t *offset, float *z_hat, int32_t *status, void *stream) {
+  return gaussian_decode(payload, off, record_prefix, off_first, off_step, B, C, bias, exp_scale, scales, ld_scales,
+                         nullptr, 0, false, scale_table, scale_bound, cdf, T, W, cdf_len, offset, z_hat, status, stream);
+}
+
+int lla_gaussian_decode_dequantise_means(const uint8_t *payload, const uint64_t *off, int record_prefix, int off_first,
+                                         int off_step, int B, int C, const float *bias, const float *exp_scale,
+                                         const float *scales, size_t ld_scales, const float *means, size_t ld_means,
+                                         const float *scale_table, float scale_bound, const int32_t *cdf, int T, int W,
+                                         const int32_t *cdf_len, const int32_t *offset, float *z_hat, int32_t *status,
+                                         void *stream) {
+  return gaussian_decode(payload, off, record_prefix, off_first, off_step, B, C, bias, exp_scale, scales, ld_scales,
+                         means, ld_means, true, scale_table, scale_bound, cdf, T, W, cdf_len, offset, z_hat, status, stream);
+}
+
+static size_t gaussian_gather_lds(int C, int T, int W, int z_dtype, size_t *front, bool with_means) {
   if (front) *front = 0;
   if ((z_dtype != LLA_Z_F16 && z_dtype != LLA_Z_F32) || C <= 0 || T <= 0 || W < 3 || gauss_head_bytes(C, T) > 32 * 1024)
     return 0;
-  const size_t fr = gauss_gather_front(C, T);
-  const void *kernel = z_dtype == LLA_Z_F16 ? reinterpret_cast<const void *>(gaussian_decode_gather_kernel<__half>)
-                                            : reinterpret_cast<const void *>(gaussian_decode_gather_kernel<float>);
+  const size_t fr = gauss_gather_front(C, T, with_means ? 5 : 3);
+  const void *kernel =
+      with_means ? (z_dtype == LLA_Z_F16 ? reinterpret_cast<const void *>(gaussian_decode_gather_kernel<__half, MeanRows>)
+                                         : reinterpret_cast<const void *>(gaussian_decode_gather_kernel<float, MeanRows>))
+                 : (z_dtype == LLA_Z_F16 ? reinterpret_cast<const void *>(gaussian_decode_gather_kernel<__half>)
+                                         : reinterpret_cast<const void *>(gaussian_decode_gather_kernel<float>));
   if (fr > dynamic_lds_limit(kernel)) return 0;
   if (front) *front = fr;
   return packed_rows_lds(kernel, fr, T, W);
 }
 
-int lla_gaussian_decode_gather(const uint8_t *payload, const uint64_t *off, int record_prefix, int off_first,
-                               int off_step, int N, const int64_t *index, int B, int C, const float *bias,
-                               const float *exp_scale, const float *scales, size_t ld_scales,
-                               const float *scale_table, float scale_bound, const int32_t *cdf, int T, int W,
-                               const int32_t *cdf_len, const int32_t *offset, void *z_hat, int z_dtype,
-                               size_t ld_out, const int32_t *status_in, int32_t *status, void *stream) {
+size_t lla_gaussian_decode_gather_lds_bytes(int C, int T, int W, int z_dtype, size_t *front) {
+  return gaussian_gather_lds(C, T, W, z_dtype, front, false);
+}
+
+size_t lla_gaussian_decode_gather_means_lds_bytes(int C, int T, int W, int z_dtype, size_t *front) {
+  return gaussian_gather_lds(C, T, W, z_dtype, front, true);
+}
+
+static int gaussian_gather(const uint8_t *payload, const uint64_t *off, int record_prefix, int off_first, int off_step,
+                           int N, const int64_t *index, int B, int C, const float *bias, const float *exp_scale,
+                           const float *scales, size_t ld_scales, const float *means, size_t ld_means, bool with_means,
+                           const float *scale_table, float scale_bound, const int32_t *cdf, int T, int W,
+                           const int32_t *cdf_len, const int32_t *offset, void *z_hat, int z_dtype, size_t ld_out,
+                           const int32_t *status_in, int32_t *status, void *stream) {
   if (z_dtype != LLA_Z_F16 && z_dtype != LLA_Z_F32) return LLA_EINVAL;
   if (off_first < 0 || off_step < 1) return LLA_EINVAL;
   if (B == 0) return LLA_OK;
+  if (with_means && (!means || ld_means < (size_t)(C > 0 ? C : 0))) return LLA_EINVAL;
   if (B < 0 || N < 0 || C <= 0 || T <= 0 || W < 3 || !payload || !off || !index || !bias || !exp_scale || !scales ||
       ld_scales < (size_t)C || !scale_table || !cdf || !cdf_len || !offset || !z_hat || ld_out < (size_t)C || !status)
     return LLA_EINVAL;
-  // (52 KiB in front of the rows: a gfx950 has 160; 0 = the head or the front does not fit)
-  const unsigned lds = (unsigned)lla_gaussian_decode_gather_lds_bytes(C, T, W, z_dtype, nullptr);
+  // (52 KiB in front of the rows, 84 KiB with means: a gfx950 has 160; 0 = the head or the front does not fit)
+  const unsigned lds = (unsigned)gaussian_gather_lds(C, T, W, z_dtype, nullptr, with_means);
   if (lds == 0) return LLA_EINVAL;
   const int grid = (B + kEncThreads - 1) / kEncThreads;
   const int skip = record_prefix ? 4 : 0;
-  if (z_dtype == LLA_Z_F16)
+  const MeanRows mr{means, ld_means};
+  if (with_means && z_dtype == LLA_Z_F16)
+    gaussian_decode_gather_kernel<__half><<<grid, kEncThreads, lds, as_stream(stream)>>>(
+        payload, off, skip, off_first, off_step, N, index, B, C, bias, exp_scale, scales, ld_scales, scale_table,
+        scale_bound, cdf, T, W, cdf_len, offset, reinterpret_cast<__half *>(z_hat), ld_out, status_in, status, lds, mr);
+  else if (with_means)
+    gaussian_decode_gather_kernel<float><<<grid, kEncThreads, lds, as_stream(stream)>>>(
+        payload, off, skip, off_first, off_step, N, index, B, C, bias, exp_scale, scales, ld_scales, scale_table,
+        scale_bound, cdf, T, W, cdf_len, offset, reinterpret_cast<float *>(z_hat), ld_out, status_in, status, lds, mr);
+  else if (z_dtype == LLA_Z_F16)
     gaussian_decode_gather_kernel<__half><<<grid, kEncThreads, lds, as_stream(stream)>>>(
         payload, off, skip, off_first, off_step, N, index, B, C, bias, exp_scale, scales, ld_scales, scale_table,
         scale_bound, cdf, T, W, cdf_len, offset, reinterpret_cast<__half *>(z_hat), ld_out, status_in, status, lds);
@@ -1551,6 +1748,29 @@ int lla_gaussian_decode_gather(const uint8_t *payload, const uint64_t *off, int 
         payload, off, skip, off_first, off_step, N, index, B, C, bias, exp_scale, scales, ld_scales, scale_table,
         scale_bound, cdf, T, W, cdf_len, offset, reinterpret_cast<float *>(z_hat), ld_out, status_in, status, lds);
   return check_launch();
+}
+
+int lla_gaussian_decode_gather(const uint8_t *payload, const uint64_t *off, int record_prefix, int off_first,
+                               int off_step, int N, const int64_t *index, int B, int C, const float *bias,
+                               const float *exp_scale, const float *scales, size_t ld_scales,
+                               const float *scale_table, float scale_bound, const int32_t *cdf, int T, int W,
+                               const int32_t *cdf_len, const int32_t *offset, void *z_hat, int z_dtype,
+                               size_t ld_out, const int32_t *status_in, int32_t *status, void *stream) {
+  return gaussian_gather(payload, off, record_prefix, off_first, off_step, N, index, B, C, bias, exp_scale, scales,
+                         ld_scales, nullptr, 0, false, scale_table, scale_bound, cdf, T, W, cdf_len, offset, z_hat, z_dtype,
+                         ld_out, status_in, status, stream);
+}
+
+int lla_gaussian_decode_gather_means(const uint8_t *payload, const uint64_t *off, int record_prefix, int off_first,
+                                     int off_step, int N, const int64_t *index, int B, int C, const float *bias,
+                                     const float *exp_scale, const float *scales, size_t ld_scales, const float *means,
+                                     size_t ld_means, const float *scale_table, float scale_bound, const int32_t *cdf,
+                                     int T, int W, const int32_t *cdf_len, const int32_t *offset, void *z_hat,
+                                     int z_dtype, size_t ld_out, const int32_t *status_in, int32_t *status,
+                                     void *stream) {
+  return gaussian_gather(payload, off, record_prefix, off_first, off_step, N, index, B, C, bias, exp_scale, scales,
+                         ld_scales, means, ld_means, true, scale_table, scale_bound, cdf, T, W, cdf_len, offset, z_hat,
+                         z_dtype, ld_out, status_in, status, stream);
 }
 
 int lla_dequantise(const int32_t *symbols, int B, int C, const float *bias,

@@ -96,6 +96,12 @@ class HyperpriorClipCompressor(ClipCompressor):
         ``HRateHyperprior._load_from_state_dict``.  Coding tables the state dict carries are kept, missing ones built.
     is_jit, device, clip_weights, vit_chunk, gpu_preprocess
         As for :class:`ClipCompressor`.  ``"cpu"`` builds the module; every compute entry point raises.
+    coded_means : ``"scales"`` (default) or ``"predicted"``
+        Passed to :class:`~lossyless_amd.rates.HRateHyperprior`: the reference's coder (the scales stand in for the means),
+        or the opt-in one that codes with the predicted means the likelihood was trained with.  ``forward``, ``compress``,
+        ``decompress``, ``get_rate``, ``compress_dataset``, ``decompress_dataset`` and ``open_dataset`` all follow it.  The
+        container format is the same in both modes and does not record the mode: a file written in one and read in the
+        other -- like a file read with another state dict -- decodes to wrong values without an error.
 
     ``compress(X)`` returns ``[z_strings, side_z_strings]`` (what ``HRateHyperprior.compress`` returns), ``decompress``
     takes it back.  ``compressor(X)`` is the coded representation without coding and equals ``decompress(compress(X))``
@@ -108,13 +114,14 @@ class HyperpriorClipCompressor(ClipCompressor):
 
     def __init__(self, pretrained_state_dict, is_jit=False,
                  device="cuda" if torch.cuda.is_available() else "cpu", *,
-                 clip_weights=None, vit_chunk=0, gpu_preprocess=False):
+                 clip_weights=None, vit_chunk=0, gpu_preprocess=False, coded_means="scales"):
         nn.Module.__init__(self)     # (ClipCompressor's own constructor goes on to build the factorized model)
         self._init_tower(clip_weights, vit_chunk, gpu_preprocess)
         if not isinstance(pretrained_state_dict, dict):
             pretrained_state_dict = torch.load(pretrained_state_dict, map_location="cpu", weights_only=True)
         side_w = pretrained_state_dict.get("side_encoder.module.8.weight")
-        self.hyperprior = HRateHyperprior(self.z_dim, side_z_dim=None if side_w is None else int(side_w.shape[0]))
+        self.hyperprior = HRateHyperprior(self.z_dim, side_z_dim=None if side_w is None else int(side_w.shape[0]),
+                                          coded_means=coded_means)
         self.side_z_dim = self.hyperprior.side_z_dim
         missing, _ = self.hyperprior.load_state_dict(pretrained_state_dict, strict=False)
         tables = ("_quantized_cdf", "_offset", "_cdf_length", "scale_table")     # (built below when not carried)

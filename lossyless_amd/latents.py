@@ -229,7 +229,10 @@ class HyperpriorLatents(_Latents):
     (``lla_rans_decode_gather_strided``: ``float(sym) + median``), the MLP runs on that buffer
     (``MLP.forward_padded``), and ``lla_gaussian_decode_gather`` decodes the z records with the scales the MLP left,
     taking the side pass's statuses as ``status_in``.  Same values, bit for bit, as
-    ``decompress_dataset(file)[indices]``.
+    ``decompress_dataset(file)[indices]``.  The coder's mode is the compressor's (``hyperprior.coded_means``): with
+    ``"predicted"`` the last step is ``lla_gaussian_decode_gather_means``, which reads the means where the MLP left them
+    next to the scales.  The file does not record the mode: opened with a compressor in the other mode (or with another
+    state dict) it decodes to wrong values without an error.
 
     Working memory: besides the compressed bytes (``nbytes``) the object keeps the buffers of the LAST batch length --
     s_hat and the MLP activations, ``workspace_nbytes`` = B x (104 + 512 + 512 + 1024) x 4 bytes, 0.56 GB at B = 65536
@@ -285,9 +288,11 @@ class HyperpriorLatents(_Latents):
         gct = self._model.gaussian_conditional.device_tables()
         T, W = gct["T"], gct["W"]
         front = ctypes.c_size_t(0)
+        L = _lib.lib()
+        query = (L.lla_gaussian_decode_gather_means_lds_bytes if self._model.coded_means == "predicted"
+                 else L.lla_gaussian_decode_gather_lds_bytes)
         with torch.cuda.device(self.device):
-            granted = int(_lib.lib().lla_gaussian_decode_gather_lds_bytes(self.z_dim, T, W, _DTYPES[dtype],
-                                                                         ctypes.byref(front)))
+            granted = int(query(self.z_dim, T, W, _DTYPES[dtype], ctypes.byref(front)))
         packed = ((T + 1) * 4 + 7) // 8 * 8 + 8 * T + 2 * int(gct["cdf_len"].clamp(3, W).sum())
         return dict(granted=granted, front=int(front.value), packed_rows=packed,
                     rows_in_lds=granted > 0 and int(front.value) + packed <= granted)
@@ -308,10 +313,14 @@ class HyperpriorLatents(_Latents):
             _lib.check(rc, "lla_rans_decode_gather_strided")
             params = m.z_encoder.forward_padded(s_hat, acts)
             # z records (0, 2) with row b of the MLP output; a row whose side record failed is not decoded
-            rc = L.lla_gaussian_decode_gather(
-                _lib.ptr(self._body), _lib.ptr(self._off), 1, 0, 2, self._n, _lib.ptr(idx), B, C, _lib.ptr(p["bias"]),
-                _lib.ptr(p["exp_scale"]), _lib.ptr(params), params.stride(0), _lib.ptr(p["scale_table"]), p["scale_bound"],
-                _lib.ptr(gct["cdf"]), gct["T"], gct["W"], _lib.ptr(gct["cdf_len"]), _lib.ptr(gct["offset"]), _lib.ptr(out),
-                _DTYPES[dtype], ld, _lib.ptr(status[0]), _lib.ptr(status[1]), st)
-            _lib.check(rc, "lla_gaussian_decode_gather")
+            head = (_lib.ptr(self._body), _lib.ptr(self._off), 1, 0, 2, self._n, _lib.ptr(idx), B, C, _lib.ptr(p["bias"]),
+                    _lib.ptr(p["exp_scale"]), _lib.ptr(params), params.stride(0))
+            tail = (_lib.ptr(p["scale_table"]), p["scale_bound"], _lib.ptr(gct["cdf"]), gct["T"], gct["W"],
+                    _lib.ptr(gct["cdf_len"]), _lib.ptr(gct["offset"]), _lib.ptr(out), _DTYPES[dtype], ld,
+                    _lib.ptr(status[0]), _lib.ptr(status[1]), st)
+            if m.coded_means == "predicted":
+                _lib.check(L.lla_gaussian_decode_gather_means(*head, m._means_ptr(params), params.stride(0), *tail),
+                           "lla_gaussian_decode_gather_means")
+            else:
+                _lib.check(L.lla_gaussian_decode_gather(*head, *tail), "lla_gaussian_decode_gather")
         return status[1]

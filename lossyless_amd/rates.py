@@ -10,6 +10,7 @@ is_compute_real_rate`` :482-506), ``HRateFactorizedPrior`` :509-564 and ``HRateH
 ``LearnableCompressor`` can evaluate and code representations with the HIP kernels.  Training ``HRateFactorizedPrior`` on
 frozen features (noise, the auxiliary loss, both optimisers) is ``lossyless_amd.BottleneckFit`` (bottleneck_fit.py).
 """
+import ctypes
 import math
 
 import torch
@@ -419,11 +420,26 @@ class HRateHyperprior(HRateEstimator):
     with ``atleast_ndim(scales_hat, 4)``), while ``forward_help`` -- like the reference's, :631-678 -- evaluates the
     likelihood with the predicted means.  The two MLPs run in fp32 (``mlp_precision="fp16"`` opts in to the fp16
     GEMMs: strings are then only decodable by a module with the same setting).
+
+    ``coded_means``: which means the coder subtracts before rounding and adds back after decoding.  ``"scales"`` (the
+    default) is the reference's behaviour above, bit for bit: what every reference container was written with.
+    ``"predicted"`` departs from rates.py:689-696 on purpose and codes with the second half of ``z_encoder``'s output, the
+    means the trained likelihood (rates.py:647-650) is centred at; it needs ``is_pred_mean=True``.  The table row of an
+    element comes from its scale in both modes.  The mode is a constructor argument, not part of ``state_dict()`` (which
+    keeps loading ``strict=True`` into the reference's module), and no string or container records it: strings written in
+    one mode and read in the other -- like strings read with another state dict -- decode to wrong values without an
+    error.
     """
 
-    def __init__(self, z_dim, factor_dim=5, side_z_dim=None, is_pred_mean=True, mlp_precision="fp32", **kwargs):
+    def __init__(self, z_dim, factor_dim=5, side_z_dim=None, is_pred_mean=True, mlp_precision="fp32",
+                 coded_means="scales", **kwargs):
         from .entropy import GaussianConditional
+        if coded_means not in ("scales", "predicted"):
+            raise ValueError(f"coded_means must be 'scales' or 'predicted', got {coded_means!r}")
+        if coded_means == "predicted" and not is_pred_mean:
+            raise ValueError("coded_means='predicted' needs is_pred_mean=True: without it z_encoder predicts no means")
         super().__init__(z_dim, **kwargs)
+        self.coded_means = coded_means
         if side_z_dim is None:
             side_z_dim = max(10, z_dim // factor_dim)
         self.side_z_dim = side_z_dim
@@ -486,7 +502,10 @@ class HRateHyperprior(HRateEstimator):
         gaussian_params = self.z_encoder(side_z_hat)
         scales_hat, means_hat = self.chunk_params(gaussian_params)
         scales_hat = scales_hat.reshape(*scales_hat.shape, 1, 1)
-        means_hat = scales_hat  # (sic) rates.py:695-696
+        if self.coded_means == "predicted":
+            means_hat = means_hat.reshape(*means_hat.shape, 1, 1)
+        else:
+            means_hat = scales_hat  # (sic) rates.py:695-696
         indexes = self.gaussian_conditional.build_indexes(scales_hat)
         return indexes, means_hat
 
@@ -534,12 +553,17 @@ class HRateHyperprior(HRateEstimator):
 
     def _scales_of(self, side_sym):
         """Side symbols int32 [B, side_z_dim] -> (fp32 matrix the scales are the leading z_dim columns of, its row
-        stride): ``z_encoder(sym + median)``, read in place by the kernels (``chunk_params`` would be a view too)."""
+        stride): ``z_encoder(sym + median)``, read in place by the kernels (``chunk_params`` would be a view too).  The
+        predicted means are its next z_dim columns (``_means_ptr``)."""
         s_hat = side_sym.to(torch.float32) + self.entropy_bottleneck.device_tables()["median"][None, :]
         params = self.z_encoder(s_hat)
         if params.dtype != torch.float32 or params.stride(1) != 1:
             params = params.float().contiguous()
         return params, params.stride(0)
+
+    def _means_ptr(self, params):
+        """Address of the means inside the ``z_encoder`` output ``params`` (row stride: that of the scales), no copy."""
+        return ctypes.c_void_p(params.data_ptr() + 4 * self.z_dim)
 
     def _check_device_path(self, what):
         if not self.is_coder_updated:
@@ -584,12 +608,16 @@ class HRateHyperprior(HRateEstimator):
         z_sym = torch.empty((B, C), dtype=torch.int32, device=dev) if want_symbols else None
         z_idx = torch.empty((B, C), dtype=torch.int32, device=dev) if want_symbols else None
         stride_z, scratch_z, len_z = scratch_for(C)
-        rc = L.lla_gaussian_quantise_encode(
-            _lib.ptr(z), _lib.LLA_Z_F16 if z.dtype == torch.float16 else _lib.LLA_Z_F32, B, C, _lib.ptr(p["bias"]),
-            _lib.ptr(p["exp_scale"]), _lib.ptr(params), ld, _lib.ptr(p["scale_table"]), p["scale_bound"],
-            _lib.ptr(gct["cdf"]), gct["T"], gct["W"], _lib.ptr(gct["cdf_len"]), _lib.ptr(gct["offset"]),
-            _lib.ptr(scratch_z), stride_z, _lib.ptr(len_z), _lib.ptr(z_sym), _lib.ptr(z_idx), st)
-        _lib.check(rc, "lla_gaussian_quantise_encode")
+        head = (_lib.ptr(z), _lib.LLA_Z_F16 if z.dtype == torch.float16 else _lib.LLA_Z_F32, B, C, _lib.ptr(p["bias"]),
+                _lib.ptr(p["exp_scale"]), _lib.ptr(params), ld)
+        tail = (_lib.ptr(p["scale_table"]), p["scale_bound"], _lib.ptr(gct["cdf"]), gct["T"], gct["W"],
+                _lib.ptr(gct["cdf_len"]), _lib.ptr(gct["offset"]), _lib.ptr(scratch_z), stride_z, _lib.ptr(len_z),
+                _lib.ptr(z_sym), _lib.ptr(z_idx), st)
+        if self.coded_means == "predicted":
+            _lib.check(L.lla_gaussian_quantise_encode_means(*head, self._means_ptr(params), ld, *tail),
+                       "lla_gaussian_quantise_encode_means")
+        else:
+            _lib.check(L.lla_gaussian_quantise_encode(*head, *tail), "lla_gaussian_quantise_encode")
         cap = max(B, 1) * (stride_z + stride_s + 8)
         payload = torch.empty(cap, dtype=torch.uint8, device=dev)
         offsets = torch.empty(2 * B + 1, dtype=torch.int64, device=dev)
@@ -607,7 +635,8 @@ class HRateHyperprior(HRateEstimator):
         """Inverse of ``encode_device``: payload uint8 (at least 4 bytes longer than ``offsets[-1]``: the decoders read
         whole words) / offsets int64 [2B+1] on the GPU -> z_hat [B, z_dim] fp32 on the GPU, the values ``decompress``
         gives for the same strings.  The side records are decoded (``lla_rans_decode_batch_strided``), ``z_encoder``
-        runs, then ``lla_gaussian_decode_dequantise``.  ValueError if a record is malformed: the
+        runs, then ``lla_gaussian_decode_dequantise`` (``lla_gaussian_decode_dequantise_means`` when
+        ``coded_means="predicted"``).  ValueError if a record is malformed: the
         kernels bound every read and a damaged record sets its image's status, which costs ONE host sync per call, at the
         end, to read the statuses back."""
         self._check_device_path("decode_device")
@@ -629,11 +658,15 @@ class HRateHyperprior(HRateEstimator):
         _lib.check(rc, "lla_rans_decode_batch_strided")
         params, ld = self._scales_of(side_sym)
         z_hat = torch.empty((B, C), dtype=torch.float32, device=dev)
-        rc = L.lla_gaussian_decode_dequantise(
-            _lib.ptr(payload), _lib.ptr(offsets), 1, 0, 2, B, C, _lib.ptr(p["bias"]), _lib.ptr(p["exp_scale"]),
-            _lib.ptr(params), ld, _lib.ptr(p["scale_table"]), p["scale_bound"], _lib.ptr(gct["cdf"]), gct["T"], gct["W"],
-            _lib.ptr(gct["cdf_len"]), _lib.ptr(gct["offset"]), _lib.ptr(z_hat), _lib.ptr(status[1]), st)
-        _lib.check(rc, "lla_gaussian_decode_dequantise")
+        head = (_lib.ptr(payload), _lib.ptr(offsets), 1, 0, 2, B, C, _lib.ptr(p["bias"]), _lib.ptr(p["exp_scale"]),
+                _lib.ptr(params), ld)
+        tail = (_lib.ptr(p["scale_table"]), p["scale_bound"], _lib.ptr(gct["cdf"]), gct["T"], gct["W"],
+                _lib.ptr(gct["cdf_len"]), _lib.ptr(gct["offset"]), _lib.ptr(z_hat), _lib.ptr(status[1]), st)
+        if self.coded_means == "predicted":
+            _lib.check(L.lla_gaussian_decode_dequantise_means(*head, self._means_ptr(params), ld, *tail),
+                       "lla_gaussian_decode_dequantise_means")
+        else:
+            _lib.check(L.lla_gaussian_decode_dequantise(*head, *tail), "lla_gaussian_decode_dequantise")
         if B and int(status.max()) != 0:
             raise ValueError("malformed rANS stream")
         return z_hat
@@ -641,13 +674,15 @@ class HRateHyperprior(HRateEstimator):
     @torch.no_grad()
     def represent_device(self, z):
         """z -> the z_hat that ``decode_device(*encode_device(z))`` gives, without coding (the same fp32 operations in the
-        same order: round(side - median) + median, z_encoder, round(z_in - scales) + scales, process_z_out)."""
+        same order: round(side - median) + median, z_encoder, round(z_in - means) + means, process_z_out; the means are
+        the scales unless ``coded_means="predicted"``)."""
         self._check_device_path("represent_device")
         z_in = self.process_z_in(z)
         med = self.entropy_bottleneck.device_tables()["median"][None, :]
         s_hat = torch.round(self.side_encoder(z_in) - med) + med
-        scales = self.z_encoder(s_hat)[:, :self.z_dim]
-        return self.process_z_out(torch.round(z_in - scales) + scales)
+        first = self.z_dim if self.coded_means == "predicted" else 0
+        means = self.z_encoder(s_hat)[:, first:first + self.z_dim]
+        return self.process_z_out(torch.round(z_in - means) + means)
 
 
 def synthetic_hyperprior_state_dict(seed=0, z_dim=512):

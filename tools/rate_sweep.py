@@ -82,8 +82,11 @@ def _fit_leg(args, comp, train, data, weights, shaped, loader, hyperprior=False)
         fit = BottleneckFit(beta, epochs=epochs, batch_size=min(1024, n)).fit(feats)
     torch.cuda.synchronize()
     fit_s = time.perf_counter() - t0
-    hub = hubconf.clip_hyperprior_compressor if hyperprior else hubconf.clip_compressor
-    fitted, _ = hub(fit.state_dict(), device="cuda", clip_weights=weights, gpu_preprocess=shaped)
+    if hyperprior:
+        fitted, _ = hubconf.clip_hyperprior_compressor(fit.state_dict(), device="cuda", clip_weights=weights,
+                                                       gpu_preprocess=shaped, coded_means=args.coded_means)
+    else:
+        fitted, _ = hubconf.clip_compressor(fit.state_dict(), device="cuda", clip_weights=weights, gpu_preprocess=shaped)
     with tempfile.TemporaryDirectory() as d:
         f = os.path.join(d, "Z.bin")
         enc = _compress(fitted, train, f, None, loader)
@@ -98,6 +101,7 @@ def _fit_leg(args, comp, train, data, weights, shaped, loader, hyperprior=False)
             f"{key}_distortion_curve": [round(r, 5) for r in fit.distortion_curve_]}
     if hyperprior:
         line[f"{key}_side_rate_curve_bits"] = [round(r, 2) for r in fit.side_rate_curve_]
+        line["coded_means"] = args.coded_means
     print(json.dumps(line), flush=True)
 
 
@@ -152,6 +156,9 @@ def main():
                          "loaded through hubconf.clip_hyperprior_compressor (one more JSON line, with the side information's "
                          "share of the rate)")
     ap.add_argument("--hyperprior-fit-epochs", type=int, default=10)
+    ap.add_argument("--coded-means", choices=("scales", "predicted"), default="scales",
+                    help="--device-hyperprior-fit: code with the scales in the means' place (the reference's coder) or with the "
+                         "predicted means the model was trained with (HRateHyperprior(coded_means=))")
     args = ap.parse_args()
 
     weights = os.environ.get("LOSSYLESS_CLIP_WEIGHTS", "synthetic")
