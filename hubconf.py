@@ -100,3 +100,18 @@ def clip_compressor(state_dict, device=_ON, **kwargs):
     """
     model = _Compressor(pretrained_state_dict=state_dict, device=device, **kwargs)
     return model, model.preprocess
+
+
+def clip_text_encoder(clip_weights=None, device=_ON, **kwargs):
+    """CLIP's text tower (``model.encode_text``), MI355X kernels: ``encoder(tokens [P, T]) -> [P, embed_dim]``, and
+    ``encoder.encode_classes(tokens [K, n_templates, T])`` for ``lossyless_amd.ZeroShotProbe``.
+
+    clip_weights : path to OpenAI ViT-B-32.pt (the file the compressors read: it holds both towers) / a state-dict; default
+                   $LOSSYLESS_CLIP_WEIGHTS; "synthetic" = seed-1 random weights, tests and the bench tool only
+    device       : "cuda", or "cpu" for the float64 twin
+    other kwargs : forwarded to ``lossyless_amd.clip_text.TextTransformer`` (``chunk``, ``truncate``, ``tokenizer``)
+
+    Tokens are integers; strings need ``tokenizer=`` (no vocabulary ships here).
+    """
+    from lossyless_amd.clip_text import TextTransformer, resolve_clip_text_weights
+    return TextTransformer(resolve_clip_text_weights(clip_weights)[0], device=device, **kwargs)

@@ -1065,6 +1065,47 @@ int lla_rn50_attnpool_tokens_f16(const void *x, const float *pos, void *tok, int
  * softmax(q k^T / 8) v per head. */
 int lla_rn50_attnpool_attend_f16(const void *q, const void *kv, void *o, int B, void *stream);
 
+/* ------------------------------------------------------------------------- *
+ * CLIP text tower (csrc/text_tower.hip): the kernels of  clip/model.py CLIP.encode_text  that are not Linear layers
+ *   x = token_embedding(text) + positional_embedding;  x = transformer(x)  (pre-LN residual blocks, causal
+ *   nn.MultiheadAttention, QuickGELU MLP);  x = ln_final(x);  x[arange, text.argmax(-1)] @ text_projection
+ * as the reference calls it on captions (utils/data/images.py:1299-1323).  The Linear layers (in_proj, out_proj, c_fc,
+ * c_proj, and text_projection as a bias-free Linear on its transpose) run on lla_gemm_f32.  Everything is fp32, row-major;
+ * no floating-point atomics; the order of every sum is fixed by the row's own length, so a prompt's values do not depend
+ * on the batch size or on its place in the batch.  Refusals are LLA_EINVAL, decided before any device call; a call with
+ * no rows is LLA_OK with no launch.
+ * ------------------------------------------------------------------------- */
+
+/* x[p*T + t][:] = tok_emb[tokens[p][t]][:] + pos[t][:]  (one fp32 sum).  tokens int32 [P][T], tok_emb [V][D], pos [T][D]
+ * (the first T rows of the positional embedding), x [P*T][D].  The caller checks that the ids lie in [0, V); the kernel
+ * clamps the index to that range, so nothing outside tok_emb is ever read.  D % 4 == 0, tok_emb / pos / x 16-byte aligned. */
+int lla_text_embed(const int32_t *tokens, int P, int T, const float *tok_emb, int V, const float *pos, int D, float *x,
+                   void *stream);
+/* Row LayerNorm (clip/model.py LayerNorm on fp32): y[r] = (x[r] - mean) * rstd * w + b with
+ *   mean = (1/D) sum_c x[r][c];  var = (1/D) sum_c (x[r][c] - mean)^2  (two-pass);  rstd = 1 / sqrtf(var + eps)
+ * x [rows] rows of D at pitch row_stride, y at pitch y_stride (elements, >= D; y may be x).  One wave per row: lane l adds
+ * its elements l, l + 64, ... in index order, the 64 lane sums go through one fixed tree.  D % 64 == 0, 64 <= D <= 1024.
+ * lla_layernorm768 (fp16 output, the image tower's) is another kernel and is unchanged. */
+int lla_layernorm_rows(const float *x, size_t row_stride, const float *w, const float *b, float *y, size_t y_stride, int rows,
+                       int D, float eps, void *stream);
+/* Causal multi-head attention of the text transformer (nn.MultiheadAttention with attn_mask = triu(-inf, 1)):
+ * qkv [P*T][3D] = q | k | v per row as in_proj_weight produces it, D = 64 heads, head dimension 64; o [P*T][D].
+ * Per prompt, head and query row i:
+ *   s_ij = (q_i . k_j) / 8 for j <= i (an fmaf chain over the 64 dimensions in index order; keys j > i take no part in
+ *   row i: the kernel walks j up to its wave's last row, so it reads them from LDS and discards what it computed);  m_i = max_j s_ij;  e_ij = expf(s_ij - m_i);  p_ij = e_ij / sum_{j <= i} e_ij (sum in
+ *   increasing j);  o_i = sum_{j <= i} p_ij v_j in increasing j  (row 0 is v_0 exactly).
+ * 1 <= T <= 77, heads >= 1, qkv and o 16-byte aligned. */
+int lla_attention_causal(const float *qkv, float *o, int P, int T, int heads, void *stream);
+/* The two pointwise steps between the GEMMs, over n contiguous floats:
+ *   mode 0  x[e] += y[e]                                   (the residual; x and y must not overlap)
+ *   mode 1  y[e] = y[e] * sigmoid(1.702f * y[e]),  sigmoid(t) = 1 / (1 + expf(-t))    (QuickGELU, in place; x is not used)
+ * x (mode 0) and y 16-byte aligned; any other mode is LLA_EINVAL. */
+int lla_text_pointwise(float *x, float *y, long long n, int mode, void *stream);
+/* out[r][:] = z[r][:] / |z[r]|_2 for C columns at pitches ld_z / ld_out (elements); a row of zeros gives zeros.  The
+ * normalisation of ZeroShotProbe (the image side of CLIP's cosine logits): one wave per row, lane l adds the squares of
+ * elements l, l + 64, ... in index order, the lane sums go through one fixed tree; sqrtf, one division per element. */
+int lla_unit_rows(const float *z, size_t ld_z, float *out, size_t ld_out, int rows, int C, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -157,6 +157,11 @@ _SIGNATURES = {
     "lla_rn50_avgpool2_f16": (_i, [_vp, _i, _i, _i, _i, _i, _vp, _i, _vp]),
     "lla_rn50_attnpool_tokens_f16": (_i, [_vp, _vp, _vp, _i, _vp]),
     "lla_rn50_attnpool_attend_f16": (_i, [_vp, _vp, _vp, _i, _vp]),
+    "lla_text_embed": (_i, [_vp, _i, _i, _vp, _i, _vp, _i, _vp, _vp]),
+    "lla_layernorm_rows": (_i, [_vp, _sz, _vp, _vp, _vp, _sz, _i, _i, ctypes.c_float, _vp]),
+    "lla_attention_causal": (_i, [_vp, _vp, _i, _i, _i, _vp]),
+    "lla_text_pointwise": (_i, [_vp, _vp, ctypes.c_longlong, _i, _vp]),
+    "lla_unit_rows": (_i, [_vp, _sz, _vp, _sz, _i, _i, _vp]),
 }
 EXPORTS = tuple(sorted(_SIGNATURES))
 

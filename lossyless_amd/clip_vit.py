@@ -295,14 +295,10 @@ class KernelProfiler:
 from .preprocess import ClipPreprocess  # noqa: E402,F401  (kept importable from here)
 
 
-def resolve_clip_weights(spec=None):
-    """``spec``: a state-dict, a path to OpenAI ``ViT-B-32.pt`` / a state-dict file, the literal
-    ``"synthetic"`` (seed-1 random weights: tests, bench and smoke only), or None = take the
-    path from ``$LOSSYLESS_CLIP_WEIGHTS``.  Returns (state_dict, description).
-
-    The shipped rate models were trained on real CLIP features, so a compressor built on anything
-    else produces meaningless rates: with nothing configured this raises instead of guessing
-    (``clip.load`` -- what the reference calls at hub/compressor.py:39 -- needs the network)."""
+def _resolve_weights(spec, load_file, of_clip_model, synthetic, what, dict_kind):
+    """The rules ``resolve_clip_weights`` and ``clip_text.resolve_clip_text_weights`` share; the towers differ in how a
+    file is read (``load_file``), what is kept of a ``clip.load`` model (``of_clip_model``), the seed-1 stand-in
+    (``synthetic``) and two words of the error text."""
     if isinstance(spec, dict):
         return spec, "state-dict"
     if spec is None:
@@ -317,14 +313,27 @@ def resolve_clip_weights(spec=None):
                 try:
                     import clip  # noqa: PLC0415
                     model, _ = clip.load("ViT-B/32", device="cpu", jit=False)
-                    return ({k: v for k, v in model.visual.state_dict().items()}, "clip.load('ViT-B/32')")
+                    return of_clip_model(model), "clip.load('ViT-B/32')"
                 except Exception as err:
                     raise ValueError(
-                        "no CLIP ViT-B/32 weights found: pass clip_weights=<path to ViT-B-32.pt or a visual "
-                        "state-dict>, set $LOSSYLESS_CLIP_WEIGHTS, or make `clip.load('ViT-B/32')` work "
+                        f"no {what} found: pass clip_weights=<path to ViT-B-32.pt or {dict_kind}>, "
+                        "set $LOSSYLESS_CLIP_WEIGHTS, or make `clip.load('ViT-B/32')` work "
                         f"(~/.cache/clip/ViT-B-32.pt is absent and clip.load failed: {err!r}). "
                         "clip_weights='synthetic' selects seed-1 random weights explicitly -- embeddings are "
                         "then NOT CLIP embeddings.") from None
     if spec == "synthetic":
-        return synthetic_vit_state_dict(1), "synthetic-seed1"
-    return load_clip_visual_state_dict(spec), str(spec)
+        return synthetic(), "synthetic-seed1"
+    return load_file(spec), str(spec)
+
+
+def resolve_clip_weights(spec=None):
+    """``spec``: a state-dict, a path to OpenAI ``ViT-B-32.pt`` / a state-dict file, the literal
+    ``"synthetic"`` (seed-1 random weights: tests, bench and smoke only), or None = take the
+    path from ``$LOSSYLESS_CLIP_WEIGHTS``.  Returns (state_dict, description).
+
+    The shipped rate models were trained on real CLIP features, so a compressor built on anything
+    else produces meaningless rates: with nothing configured this raises instead of guessing
+    (``clip.load`` -- what the reference calls at hub/compressor.py:39 -- needs the network)."""
+    return _resolve_weights(spec, load_clip_visual_state_dict,
+                            lambda model: {k: v for k, v in model.visual.state_dict().items()},
+                            lambda: synthetic_vit_state_dict(1), "CLIP ViT-B/32 weights", "a visual state-dict")

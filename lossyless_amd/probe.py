@@ -379,6 +379,11 @@ class _Scores:
 
     coef_ = intercept_ = classes_ = None
 
+    @staticmethod
+    def _rows_in(z):
+        """What is scored in the place of a group's rows (ZeroShotProbe: the rows over their norms)."""
+        return z
+
     def _set(self, W, b, classes, n_passes, objective, converged):
         self.coef_, self.intercept_ = W.to(torch.float32), b.to(torch.float32)
         self.classes_ = classes.numpy()
@@ -417,6 +422,7 @@ class _Scores:
                     for g0, z in rows.groups():
                         z = z if z.dtype == torch.float32 else z.float()
                         z = z if z.stride(1) == 1 and z.stride(0) % 4 == 0 else z.contiguous()
+                        z = self._rows_in(z)
                         g = int(z.shape[0])
                         o = out[g0:g0 + g]
                         rc = L.lla_gemm_f32(_lib.ptr(z), int(z.stride(0)) if g > 1 else C, _lib.ptr(w), C, _lib.ptr(b),
@@ -425,7 +431,7 @@ class _Scores:
                 s = out[:, :K]
             else:
                 W, b = self.coef_.to(torch.float64).cpu(), self.intercept_.to(torch.float64).cpu()
-                s = torch.cat([z.to(torch.float64) @ W.T + b for _, z in rows.groups()]) if rows.n else \
+                s = torch.cat([self._rows_in(z.to(torch.float64)) @ W.T + b for _, z in rows.groups()]) if rows.n else \
                     torch.zeros((0, K), dtype=torch.float64)
         finally:
             rows.close()
@@ -3045,3 +3051,78 @@ class RidgeProbeCV:
                     if f < nf:
                         count(z[a0:a1] @ W[f].reshape(A * Kp, C).T + b[f].reshape(-1), f, g0 + a0)
         return right.cpu()
+
+
+# ------------------------------------------------------------------------------------------------------------- zero-shot
+class ZeroShotProbe(_Scores):
+    """``ZeroShotProbe(class_embeddings [K, E], logit_scale=None, classes=None)``: CLIP's zero-shot classifier over coded
+    features -- no training rows, no ``fit``.  The logit of row i for class k is
+
+        logit_scale * (z_i / |z_i|) . w_k
+
+    with ``w_k`` the class embeddings as given (:meth:`from_tokens` makes them with a text tower's ``encode_classes``:
+    unit-norm prompt ensembles) and ``logit_scale`` 100 unless given (CLIP's trained ``exp(logit_scale)``).  A row of zeros
+    gives zero logits.
+
+    ``decision_function`` ``[N, K]``, ``predict``, ``predict_proba`` (softmax of the logits), ``score(X, y=None)`` and
+    ``top_k_score(X, k, y=None)`` take a ``CompressedLatents`` / ``HyperpriorLatents`` (its own labels unless ``y`` is
+    given), a tensor or an ndarray, and score one decode group at a time with the walk of the other probes' ``predict``:
+    ``lla_unit_rows`` (the row norm in a fixed order), then ``lla_gemm_f32``, fp32 -- the same bits for a container, its
+    kept rows and the decoded tensor.  CPU data run the float64 twin.  ``coef_`` fp32 ``[K, E]``, ``intercept_`` zeros,
+    ``classes_`` (numpy; ``arange(K)`` unless given)."""
+
+    def __init__(self, class_embeddings, logit_scale=None, classes=None):
+        W = class_embeddings.detach().cpu() if isinstance(class_embeddings, torch.Tensor) else \
+            torch.from_numpy(np.asarray(class_embeddings))
+        if W.dim() != 2 or not W.is_floating_point() or not bool(torch.isfinite(W).all()):
+            raise ValueError("class_embeddings must be finite floats [K, E]")
+        K = int(W.shape[0])
+        classes = torch.arange(K) if classes is None else torch.from_numpy(np.asarray(classes)).reshape(-1)
+        if classes.numel() != K:
+            raise ValueError(f"{classes.numel()} classes for {K} class embeddings")
+        self.logit_scale = 100.0 if logit_scale is None else float(logit_scale)
+        if not self.logit_scale > 0:
+            raise ValueError("logit_scale must be positive")
+        self._set(W, torch.zeros(K), classes, 0, None, True)
+
+    @classmethod
+    def from_tokens(cls, text_tower, tokens, classes=None, logit_scale=None):
+        """Class embeddings from ``text_tower.encode_classes(tokens [K, n_templates, T])``; ``logit_scale`` defaults to the
+        ``exp(logit_scale)`` of the tower's state dict when it holds one, otherwise 100."""
+        if logit_scale is None:
+            logit_scale = text_tower.logit_scale
+        return cls(text_tower.encode_classes(tokens), logit_scale, classes)
+
+    @staticmethod
+    def _rows_in(z):
+        from .clip_text import unit_rows
+        return unit_rows(z)
+
+    def decision_function(self, data, rows_per_pass=65536):
+        return (self._scores(data, rows_per_pass) * self.logit_scale).contiguous()
+
+    def predict(self, data, rows_per_pass=65536):
+        s = self.decision_function(data, rows_per_pass)
+        return torch.from_numpy(self.classes_).to(s.device)[_first_argmax(s)]
+
+    def predict_proba(self, data, rows_per_pass=65536):
+        return torch.softmax(self.decision_function(data, rows_per_pass), 1)
+
+    def score(self, data, y=None, rows_per_pass=65536):
+        return self.top_k_score(data, 1, y, rows_per_pass)
+
+    def top_k_score(self, data, k, y=None, rows_per_pass=65536):
+        """The share of rows whose label is among the ``k`` classes of largest logit (ties go to the lower index)."""
+        s = self.decision_function(data, rows_per_pass)
+        K = int(s.shape[1])
+        if not 1 <= int(k) <= K:
+            raise ValueError(f"k = {k} outside [1, {K}]")
+        y = _labels_of(data, y, int(s.shape[0])).to(s.device)
+        cls = torch.from_numpy(self.classes_).to(s.device)
+        own = (y[:, None] == cls[None, :])
+        if not bool(own.any(1).all()):
+            raise ValueError("labels outside classes_")
+        mine = (s * own).sum(1, keepdim=True)                      # the logit of the row's own class
+        at = torch.arange(K, device=s.device)[None, :]
+        ahead = ((s > mine) | ((s == mine) & (at < own.to(torch.int64).argmax(1, keepdim=True)))).sum(1)
+        return float((ahead < int(k)).double().mean()) if s.shape[0] else float("nan")

@@ -146,6 +146,11 @@ def main():
                     help="also run lossyless_amd.RidgeProbeCV (scikit-learn's RidgeClassifier objective, N values of alpha "
                          "log-spaced in [1e-3, 1e3], 5 stratified folds, two walks of the container in all) on the device "
                          "(adds ridge_probe_cv_best, _validation_accuracy, _accuracy and _fit_s)")
+    ap.add_argument("--device-zero-shot", default=None, metavar="TOKENS.npy",
+                    help="also classify the test split with no training rows: lossyless_amd.ZeroShotProbe over the class "
+                         "prompts' token ids [K, n_templates, T] in TOKENS.npy (class k = label k), embedded by the text tower "
+                         "of $LOSSYLESS_CLIP_WEIGHTS on the device (adds zero_shot_accuracy, zero_shot_top5_accuracy and "
+                         "zero_shot_s; with the synthetic weights the figure is the path's, not CLIP's)")
     ap.add_argument("--device-bottleneck-fit", type=float, default=0.0, metavar="BETA",
                     help="also train a rate point of its own with lossyless_amd.BottleneckFit(BETA) on the device, on the tower's "
                          "features of the run's training images, load its state_dict() through hubconf.clip_compressor and "
@@ -276,6 +281,16 @@ def main():
                     probe.update(ridge_probe_cv_fit_s=round(time.perf_counter() - t0, 3), ridge_probe_cv_best=ridge.best_params_,
                                  ridge_probe_cv_validation_accuracy=float(ridge.mean_scores_.max()),
                                  ridge_probe_cv_accuracy=float(ridge.best_estimator_.score(comp.open_dataset(ft), np.asarray(Yt))))
+                if args.device_zero_shot:
+                    from lossyless_amd import ZeroShotProbe
+                    t0 = time.perf_counter()
+                    tokens = np.load(args.device_zero_shot)
+                    zs = ZeroShotProbe.from_tokens(hubconf.clip_text_encoder(weights, device="cuda"), tokens)
+                    zs_acc = float(zs.score(comp.open_dataset(ft), np.asarray(Yt)))
+                    zs_top5 = float(zs.top_k_score(comp.open_dataset(ft), min(5, tokens.shape[0]), np.asarray(Yt)))
+                    torch.cuda.synchronize()
+                    probe.update(zero_shot_s=round(time.perf_counter() - t0, 3), zero_shot_accuracy=zs_acc,
+                                 zero_shot_top5_accuracy=zs_top5)
         print(json.dumps(dict(rate_point=name, data=data, clip_weights=weights, images=n,
                               call=("Dataset(transform=RawRGB) -> compress_dataset(dataset, file, label_file, "
                                     f"dict(batch_size={args.batch}, num_workers={args.workers}))") if shaped
