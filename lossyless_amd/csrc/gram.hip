@@ -39,23 +39,15 @@
 //
 // lla_segment_sums: one workgroup per (segment, 128 columns), 8 row lanes x 32 threads of four columns.  Lane l adds rows
 // l, l + 8, ... of the segment in row order in double; the eight lanes are then added in lane order.  No workspace.
-#include "common.h"
-
-#include <hip/hip_fp16.h>
+#include "row_tile.h"      // kRows (a chunk), kZPad, kResident, the checks of the rows and the ordered sum
 
 namespace lla {
 namespace {
 
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-typedef float f32x16 __attribute__((ext_vector_type(16)));
-
-constexpr int kRows = 32;             // rows per staged chunk
 constexpr int kTile = 128;            // columns per panel: the edge of a Gram tile
 constexpr int kTargets = 32;          // targets per cross tile
-constexpr int kZPad = 4;              // floats (probe.hip)
 constexpr int kPitch = kTile + kZPad;
 constexpr int kTPitch = kTargets + kZPad;
-constexpr int kResident = 512;        // workgroups the chip holds at two per CU: the grid is cut to it
 constexpr int kMaxTargets = 4096;
 constexpr int kSegBatch = 256;        // segments per launch of segment_sums_kernel (their offsets travel as an argument)
 constexpr int kSegLanes = 8;
@@ -64,7 +56,7 @@ struct Plan {
   int nt, ntri, ntt, tiles, pmax;
 };
 
-inline bool shape_ok(int C, int T) { return C >= 8 && C <= 1024 && (C & 7) == 0 && T >= 0 && T <= kMaxTargets; }
+inline bool shape_ok(int C, int T) { return cols_ok(C) && T >= 0 && T <= kMaxTargets; }
 
 inline Plan plan_of(int C, int T) {
   Plan pl;
@@ -72,7 +64,7 @@ inline Plan plan_of(int C, int T) {
   pl.ntri = pl.nt * (pl.nt + 1) / 2;
   pl.ntt = (T + kTargets - 1) / kTargets;
   pl.tiles = pl.ntri + pl.nt * pl.ntt;
-  pl.pmax = kResident / pl.tiles < 1 ? 1 : kResident / pl.tiles;
+  pl.pmax = tile_walkers(pl.tiles);
   return pl;
 }
 
@@ -280,22 +272,6 @@ __global__ __launch_bounds__(256) void gram_pass_kernel(const void *__restrict__
   else cross_tile(lds, z, z_f16, ld_z, B, C, t, ld_t, T, q - ntri, nt, partR, partT);
 }
 
-// sum over entries 0 .. n-1 of src[k * stride], added in that order in double, eight loads in flight (probe.hip)
-template <typename S>
-__device__ __forceinline__ double ordered_sum(const S *__restrict__ src, size_t stride, int n) {
-  double sum = 0.0;
-  int k = 0;
-  for (; k + 8 <= n; k += 8) {
-    S v[8];
-#pragma unroll
-    for (int j = 0; j < 8; ++j) v[j] = src[(size_t)(k + j) * stride];
-#pragma unroll
-    for (int j = 0; j < 8; ++j) sum += (double)v[j];
-  }
-  for (; k < n; ++k) sum += (double)src[(size_t)k * stride];
-  return sum;
-}
-
 __device__ __forceinline__ void put(double *o, double sum, int accumulate) { *o = accumulate ? *o + sum : sum; }
 
 // out (+)= the partials of walkers 0 .. P-1, in that order.  Blocks: 64 per Gram tile, then one per panel (column sums), then
@@ -314,7 +290,7 @@ __global__ __launch_bounds__(256) void gram_reduce_kernel(const float *__restric
     tile_of(q, nt, ti, tj);
     const int c = ti * kTile + (e >> 7), d = tj * kTile + (e & 127);
     if (c >= C || d >= C || c > d) return;
-    const double sum = ordered_sum(partG + (size_t)q * P * (kTile * kTile) + e, (size_t)kTile * kTile, P);
+    const double sum = ordered_sum<double>(partG + (size_t)q * P * (kTile * kTile) + e, (size_t)kTile * kTile, P);
     double *o = out_gram + (size_t)c * C + d;
     const double v = accumulate ? *o + sum : sum;
     *o = v;
@@ -324,7 +300,7 @@ __global__ __launch_bounds__(256) void gram_reduce_kernel(const float *__restric
   b -= ntri * 64;
   if (b < nt) {
     const int c = b * kTile + tid;
-    if (tid < kTile && c < C) put(out_sum + c, ordered_sum(partS + (size_t)b * P * (2 * kTile) + tid, kTile, 2 * P), accumulate);
+    if (tid < kTile && c < C) put(out_sum + c, ordered_sum<double>(partS + (size_t)b * P * (2 * kTile) + tid, kTile, 2 * P), accumulate);
     return;
   }
   b -= nt;
@@ -333,13 +309,13 @@ __global__ __launch_bounds__(256) void gram_reduce_kernel(const float *__restric
     const int k = (x / nt) * kTargets + (e >> 7), c = (x % nt) * kTile + (e & 127);
     if (k < T && c < C)
       put(out_cross + (size_t)k * C + c,
-          ordered_sum(partR + (size_t)x * P * (kTargets * kTile) + e, (size_t)kTargets * kTile, P), accumulate);
+          ordered_sum<double>(partR + (size_t)x * P * (kTargets * kTile) + e, (size_t)kTargets * kTile, P), accumulate);
     return;
   }
   b -= nt * ntt * 16;
   const int k = b * kTargets + (tid & 31);
   if (tid < 2 * kTargets && k < T) {
-    const double sum = ordered_sum(partT + (size_t)b * P * (4 * kTargets) + (tid >> 5) * kTargets + (tid & 31), 2 * kTargets, 2 * P);
+    const double sum = ordered_sum<double>(partT + (size_t)b * P * (4 * kTargets) + (tid >> 5) * kTargets + (tid & 31), 2 * kTargets, 2 * P);
     put((tid >> 5 ? out_tsq : out_tsum) + k, sum, accumulate);
   }
 }
@@ -382,12 +358,6 @@ __global__ __launch_bounds__(256) void segment_sums_kernel(const void *__restric
     for (int j = 1; j < kSegLanes; ++j) total += Dp[j][tid];
     put(out + (size_t)blockIdx.x * C + c, total, accumulate);
   }
-}
-
-bool rows_ok(const void *z, int z_dtype, int ld_z, int B, int C) {
-  if (B < 0 || ld_z < C || (ld_z & 3) || (z_dtype != LLA_Z_F32 && z_dtype != LLA_Z_F16)) return false;
-  if (B > 0 && !z) return false;
-  return ((uintptr_t)z & (z_dtype == LLA_Z_F32 ? 15 : 7)) == 0;
 }
 
 }  // namespace

@@ -9,15 +9,15 @@
 //   a_i = argmax_k s_ik (the lowest k on ties)      out_sum[k] = sum_{i: a_i = k} w_i z_i      out_count[k] = |{i: a_i = k}|
 // With W = the centres and b_k = -1/2 |c_k|^2 the argmax is the nearest centre and dist its squared distance.
 //
-// The walk is probe.hip's (lla_svm_pass / lla_softmax_pass) with another step 3.  A persistent workgroup (4 waves) owns one
-// tile of 32 centroids and walks row tiles of 32 rows:
+// The walk is probe.hip's (lla_svm_pass / lla_softmax_pass) with another step 3: steps 1, 2 and 4 are row_tile.h's.  A
+// persistent workgroup (4 waves) owns one tile of 32 centroids and walks row tiles of 32 rows:
 //   1. the row tile is staged in LDS once, as fp32 (fp16 rows are widened exactly), pitch C + 4 floats; eight threads per
-//      row take the row's sum of squares over their columns, in an order fixed by C (knn.hip);
+//      row take the row's sum of squares over their columns, in an order fixed by C (as knn.hip: row_tile.h);
 //   2. scores: S[32 centroids][32 rows] = W_tile Z_tile^T on v_mfma_f32_32x32x2_f32, the C dimension dealt to the four waves
 //      in groups of 8 and their partial tiles added through LDS in a fixed order ((w0 + w2) + (w1 + w3));
 //   3. assignment: one thread per row scans the K real centroids of the tile in ascending order with a strict >, writes
 //      out_assign / out_dist and leaves (a_i, w_i) in LDS: the one-hot residual w_i [k == a_i] is never stored as a matrix;
-//   4. sums: G[32 centroids][C] += R^T Z_tile, the second MFMA of probe.hip with the residual formed from (a_i, w_i); each
+//   4. sums: G[32 centroids][C] += R^T Z_tile, probe.hip's second MFMA with the residual formed from (a_i, w_i); each
 //      wave keeps its C / 4 columns of the slice in accumulator registers over ALL its row tiles.
 // Scores never leave the chip.  LDS: 32 (C + 4) + 2 * 1024 + 384 floats -- 74 KB at C = 512: two workgroups per CU.
 //
@@ -38,105 +38,16 @@
 // floating-point atomics (the counts are integers): every workgroup writes its partial sums to the workspace and
 // kmeans_reduce_kernel adds them in workgroup order, counts and statistics in double; the number of workgroups is a function
 // of (B, K) alone, so two calls on the same inputs give the same bits.
-#include "common.h"
-
-#include <hip/hip_fp16.h>
+#include "row_tile.h"
 
 namespace lla {
 namespace {
-
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-typedef float f32x16 __attribute__((ext_vector_type(16)));
-
-constexpr int kRows = 32;          // rows per staged tile
-constexpr int kClasses = 32;       // centroids per workgroup
-constexpr int kZPad = 4;           // floats (probe.hip)
-constexpr int kResident = 512;     // workgroups the chip holds at two per CU: the grid is cut to it
 
 // what a pass kernel does: everything (K <= 32), steps 1-3 only (K <= 32, predict), steps 1, 3, 4 from out_assign (K > 32)
 enum { kFused = 0, kPredict = 1, kSumsOnly = 2 };
 
 // Zs, two score slots, Np [32 rows][8], then b [32], a [32], w [32], count [32]
 __host__ __device__ inline int lds_floats(int C) { return kRows * (C + kZPad) + 2 * kRows * kClasses + kRows * 8 + 4 * kClasses; }
-inline int class_tiles(int K) { return (K + kClasses - 1) / kClasses; }
-inline int tile_walkers(int nct) { const int w = kResident / nct; return w < 1 ? 1 : w; }
-
-// 1. rows row0 .. row0 + 31 -> Zs [32][C + kZPad] as fp32 (rows beyond B are zeros and are assigned nowhere): probe.hip
-__device__ __forceinline__ void stage_rows(float *Zs, const void *__restrict__ z, int z_f16, int ld_z, int row0, int B,
-                                           int C, int tid) {
-  const int pitch = C + kZPad, c4n = C >> 2;
-  for (int i = tid; i < kRows * c4n; i += 256) {
-    const int row = i / c4n, c4 = i - row * c4n;
-    f32x4 v = {0.f, 0.f, 0.f, 0.f};
-    if (row0 + row < B) {
-      const size_t at = (size_t)(row0 + row) * ld_z + 4 * c4;
-      if (z_f16) {
-        const uint2 raw = *reinterpret_cast<const uint2 *>(static_cast<const __half *>(z) + at);
-        const __half2 lo = __builtin_bit_cast(__half2, raw.x), hi = __builtin_bit_cast(__half2, raw.y);
-        v = f32x4{__low2float(lo), __high2float(lo), __low2float(hi), __high2float(hi)};
-      } else {
-        v = *reinterpret_cast<const f32x4 *>(static_cast<const float *>(z) + at);
-      }
-    }
-    *reinterpret_cast<f32x4 *>(Zs + row * pitch + 4 * c4) = v;
-  }
-}
-
-// the staged rows' sums of squares: thread (row, part) takes columns 4 (part + 8 i) .. + 3, i ascending (knn.hip)
-__device__ __forceinline__ void row_squares(const float *Zs, float *Np, int C, int tid) {
-  const int row = tid >> 3, part = tid & 7;
-  float ss = 0.f;
-  for (int c4 = part; c4 < (C >> 2); c4 += 8) {
-    const f32x4 v = *reinterpret_cast<const f32x4 *>(Zs + row * (C + kZPad) + 4 * c4);
-    ss += v[0] * v[0];
-    ss += v[1] * v[1];
-    ss += v[2] * v[2];
-    ss += v[3] * v[3];
-  }
-  Np[tid] = ss;
-}
-
-// n2 of a staged row from its eight partial sums, in the order of the parts
-__device__ __forceinline__ float row_n2(const float *Np, int row) {
-  const f32x4 a = *reinterpret_cast<const f32x4 *>(Np + 8 * row), b = *reinterpret_cast<const f32x4 *>(Np + 8 * row + 4);
-  float ss = a[0];
-  ss += a[1], ss += a[2], ss += a[3], ss += b[0], ss += b[1], ss += b[2], ss += b[3];
-  return ss;
-}
-
-__device__ __forceinline__ float inv_norm(float n2) { return n2 > 0.f ? 1.f / sqrtf(n2) : 0.f; }
-
-// 2. scores of the staged tile against 32 centroids: Sp [slot][32 centroids][32 rows], the C dimension dealt to the four
-// waves in groups of 8; waves 0, 1 write the slots, waves 2, 3 add to them.  wp: this lane's row of W, + 4 (lane >> 5).
-// Ends on a barrier (probe.hip, gradient mode).
-__device__ __forceinline__ void tile_scores(const float *Zs, float *Sp, const float *__restrict__ wp, int C, int lane,
-                                            int wid) {
-  const int pitch = C + kZPad, ngroups = C >> 3;
-  const int r32 = lane & 31, hk = lane >> 5;
-  f32x16 s;
-#pragma unroll
-  for (int r = 0; r < 16; ++r) s[r] = 0.f;
-  for (int g = wid; g < ngroups; g += 4) {
-    const f32x4 a = *reinterpret_cast<const f32x4 *>(Zs + r32 * pitch + 8 * g + 4 * hk);
-    const f32x4 w = *reinterpret_cast<const f32x4 *>(wp + 8 * g);
-#pragma unroll
-    for (int j = 0; j < 4; ++j) s = __builtin_amdgcn_mfma_f32_32x32x2f32(w[j], a[j], s, 0, 0, 0);
-  }
-  // register r of lane l is centroid 8 (r >> 2) + 4 (l >> 5) + (r & 3), row l & 31
-#pragma unroll
-  for (int stage = 0; stage < 2; ++stage) {
-    if ((wid >> 1) == stage) {
-      float *dst = Sp + (wid & 1) * (kRows * kClasses);
-#pragma unroll
-      for (int r = 0; r < 16; ++r) {
-        const int at = (8 * (r >> 2) + 4 * hk + (r & 3)) * kRows + r32;
-        if (stage == 0) dst[at] = s[r];
-        else dst[at] += s[r];
-      }
-    }
-    __syncthreads();
-  }
-}
 
 // THE score of (row rr of the staged tile, centroid cl of the scored tile): both paths read it here, so that its bits are
 // a function of (z_i, W_k, b_k, C, metric) alone
@@ -207,7 +118,7 @@ __global__ __launch_bounds__(256) void kmeans_pass_kernel(const void *__restrict
     stage_rows(Zs, z, z_f16, ld_z, row0, B, C, tid);                 // 1.
     __syncthreads();
     if (SCORE || cosine) row_squares(Zs, Np, C, tid);
-    if constexpr (SCORE) tile_scores(Zs, Sp, wp, C, lane, wid);      // 2.
+    if constexpr (SCORE) tile_scores<false>(Zs, Sp, wp, nullptr, C, lane, wid);      // 2.
     else __syncthreads();
 
     if (tid < kRows) {                                               // 3. one thread per row
@@ -239,22 +150,8 @@ __global__ __launch_bounds__(256) void kmeans_pass_kernel(const void *__restrict
     }
     if constexpr (SUMS) {
       __syncthreads();
-      // 4. sums slice: "A" lane l = w_i [a_i == l & 31] of row 2 s + (l >> 5), "B" lane l = Z[row 2 s + (l >> 5)][column]
-#pragma unroll 4
-      for (int s2 = 0; s2 < kRows / 2; ++s2) {
-        const int row = 2 * s2 + hk;
-        const float a = Ai[row] == r32 ? Wi[row] : 0.f;
-        const float *zrow = Zs + row * pitch;
-#pragma unroll
-        for (int t = 0; t < NT; ++t) {
-          const int c0 = (wid + 4 * t) * 32;
-          if (c0 < C) {
-            int cc = c0 + r32;
-            if (cc > C - 1) cc = C - 1;          // clamped columns are computed and not stored
-            acc[t] = __builtin_amdgcn_mfma_f32_32x32x2f32(a, zrow[cc], acc[t], 0, 0, 0);
-          }
-        }
-      }
+      // 4. sums slice: "A" lane l = w_i [a_i == l & 31] of row 2 s + (l >> 5)
+      slice_mfma(acc, Zs, [&](int row) { return Ai[row] == r32 ? Wi[row] : 0.f; }, C, lane, wid);
       __syncthreads();                           // the next tile's staging overwrites Zs, and step 3 Ai and Wi
     }
     // (kPredict: the next tile's staging writes Zs only, which step 3 does not read; a barrier follows it before Np and Sp
@@ -263,15 +160,7 @@ __global__ __launch_bounds__(256) void kmeans_pass_kernel(const void *__restrict
 
   if constexpr (SUMS) {
     // this workgroup's partial sums -> workspace (centroids beyond K hold exact zeros and are never read)
-    float *pw = part_W + (size_t)(ct * P + p) * kClasses * C;
-#pragma unroll
-    for (int t = 0; t < NT; ++t) {
-      const int cc = (wid + 4 * t) * 32 + r32;
-      if (cc < C) {
-#pragma unroll
-        for (int r = 0; r < 16; ++r) pw[(size_t)(8 * (r >> 2) + 4 * hk + (r & 3)) * C + cc] = acc[t][r];
-      }
-    }
+    slice_store(acc, part_W + (size_t)(ct * P + p) * kClasses * C, C, lane, wid);
     if (tid < kClasses) part_cnt[(size_t)(ct * P + p) * kClasses + tid] = Cnt[tid];     // (behind the loop's last barrier)
   }
   if constexpr (MODE == kFused) store_stats(reinterpret_cast<double *>(Sp), dsum, nsum, part_stats + 2 * (size_t)p, tid);
@@ -313,7 +202,7 @@ __global__ __launch_bounds__(256) void kmeans_assign_kernel(const void *__restri
         const int c = k0 + cl0 + 8 * j;
         bk[j] = c < K ? bias[c] : 0.f;
       }
-      tile_scores(Zs, Sp, W + (size_t)n * ld_w + 4 * hk, C, lane, wid);
+      tile_scores<false>(Zs, Sp, W + (size_t)n * ld_w + 4 * hk, nullptr, C, lane, wid);
       if (ct == 0) {
         n2 = row_n2(Np, rr);
         rinv = cosine ? inv_norm(n2) : 1.f;
@@ -346,22 +235,6 @@ __global__ __launch_bounds__(256) void kmeans_assign_kernel(const void *__restri
     __syncthreads();                             // the next tile's row_squares and scores overwrite Np and Sp
   }
   if (part_stats) store_stats(reinterpret_cast<double *>(Sp), dsum, nsum, part_stats + 2 * (size_t)blockIdx.x, tid);
-}
-
-// sum over workgroups 0 .. P-1 of src[p * stride], added in that order, eight loads in flight (probe.hip)
-template <typename T, typename S>
-__device__ __forceinline__ T ordered_sum(const S *__restrict__ src, size_t stride, int P) {
-  T sum = 0;
-  int p = 0;
-  for (; p + 8 <= P; p += 8) {
-    S v[8];
-#pragma unroll
-    for (int j = 0; j < 8; ++j) v[j] = src[(size_t)(p + j) * stride];
-#pragma unroll
-    for (int j = 0; j < 8; ++j) sum += (T)v[j];
-  }
-  for (; p < P; ++p) sum += (T)src[(size_t)p * stride];
-  return sum;
 }
 
 // out (+)= the partial sums of walkers 0 .. P-1, in that order.  One thread per (centroid, column); column C of a centroid
@@ -400,9 +273,7 @@ const void *pass_kernel(int C) {
   return reinterpret_cast<const void *>(&kmeans_pass_kernel<8, MODE>);
 }
 
-bool shape_ok(int C, int K) {
-  return C >= 8 && C <= 1024 && (C & 7) == 0 && K >= 1 && class_tiles(K) <= 65535;
-}
+bool shape_ok(int C, int K) { return cols_ok(C) && K >= 1 && class_tiles(K) <= 65535; }
 
 // floats of partial sums and counts: [centroid tile][walker][32][C + 1]
 size_t partial_floats(int C, int K) {
@@ -423,13 +294,10 @@ extern "C" size_t lla_kmeans_pass_workspace_bytes(int C, int K) {
 extern "C" int lla_kmeans_pass(const void *z, int z_dtype, int ld_z, int B, int C, const float *W, const float *b, int K,
                                int ld_w, int metric, int32_t *out_assign, float *out_dist, float *out_sum,
                                double *out_count, double *out_stats, int accumulate, void *workspace, void *stream) {
-  if (!shape_ok(C, K) || B < 0 || ld_z < C || ld_w < C || (ld_z & 3) || (ld_w & 3) || (metric != 0 && metric != 1) ||
-      (z_dtype != LLA_Z_F32 && z_dtype != LLA_Z_F16))
+  if (!shape_ok(C, K) || !rows_ok(z, z_dtype, ld_z, B, C) || ld_w < C || (ld_w & 3) || (metric != 0 && metric != 1))
     return LLA_EINVAL;
-  if (!W || !b || !out_assign || !out_dist || !workspace || (out_sum && (!out_count || !out_stats)) || (B > 0 && !z))
-    return LLA_EINVAL;
-  const uintptr_t z_align = z_dtype == LLA_Z_F32 ? 15 : 7;
-  if (((uintptr_t)z & z_align) || ((uintptr_t)W & 15) || ((uintptr_t)out_sum & 15) || ((uintptr_t)workspace & 15) ||
+  if (!W || !b || !out_assign || !out_dist || !workspace || (out_sum && (!out_count || !out_stats))) return LLA_EINVAL;
+  if (((uintptr_t)W & 15) || ((uintptr_t)out_sum & 15) || ((uintptr_t)workspace & 15) ||
       ((uintptr_t)out_assign & 3) || ((uintptr_t)out_dist & 3) || ((uintptr_t)out_count & 7) || ((uintptr_t)out_stats & 7))
     return LLA_EINVAL;
   if (B == 0 && (accumulate || !out_sum)) return LLA_OK;

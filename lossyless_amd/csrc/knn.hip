@@ -10,7 +10,7 @@
 //   0. once: its share of the query tile goes to REGISTERS -- lane l of wave w holds columns 8 g + 4 (l >> 5) .. + 3 of query
 //      l & 31 for the column groups g = w, w + 4, ... (C / 8 floats per lane: 64 VGPRs at C = 512, 128 at C = 1024), so the
 //      queries are read from memory once per call, not once per row tile;
-//   1. the row tile is staged in LDS once, as fp32 (fp16 rows are widened exactly), pitch C + 4 floats (probe.hip);
+//   1. the row tile is staged in LDS once, as fp32 (fp16 rows are widened exactly), pitch C + 4 floats (row_tile.h);
 //      cosine: eight threads per row take the row's sum of squares over their columns, in an order fixed by C;
 //   2. scores: S[32 queries][32 rows] = Q_tile Z_tile^T on v_mfma_f32_32x32x2_f32, the C dimension dealt to the four waves
 //      in groups of 8 and their partial tiles added through LDS in a fixed order ((w0 + w2) + (w1 + w3));
@@ -31,31 +31,21 @@
 // depends on where row j falls in a tile, a call or a walker's range.  The order (score descending, index ascending) is
 // total, a walker's list is the top k of the rows it saw, and the top k of a union is the top k of the parts' top k: the
 // result is a pure function of the rows shown.  No floating-point atomics (the insertion counter is an integer).
-#include "common.h"
+#include "row_tile.h"
 
-#include <hip/hip_fp16.h>
 #include <limits.h>
 
 namespace lla {
 namespace {
 
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-typedef float f32x16 __attribute__((ext_vector_type(16)));
-
-constexpr int kRows = 32;          // rows per staged tile
-constexpr int kQueries = 32;       // queries per workgroup
-constexpr int kZPad = 4;           // floats (probe.hip)
+constexpr int kQueries = kClasses; // queries per workgroup: the "classes" of row_tile.h's score tile
 constexpr int kSlots = 4;          // list entries per lane: 64 lanes x 4 = kMaxK
 constexpr int kMaxK = 256;
-constexpr int kResident = 512;     // workgroups the chip holds at two per CU
 constexpr int kWalkersMax = 64;    // lists a query's merge reads at the most
 
 __host__ __device__ inline int lds_floats(int C) { return kRows * (C + kZPad) + 2 * kRows * kQueries + kRows * 8; }
-inline int query_tiles(int Q) { return (Q + kQueries - 1) / kQueries; }
-__host__ __device__ inline int walkers_of(int nqt) {
-  const int w = kResident / nqt;
-  return w < 1 ? 1 : (w > kWalkersMax ? kWalkersMax : w);
-}
+inline int query_tiles(int Q) { return class_tiles(Q); }
+inline int walkers_of(int nqt) { const int w = tile_walkers(nqt); return w > kWalkersMax ? kWalkersMax : w; }
 
 // entry (ev, ei) stands before the candidate (cs, cj) in the order (score descending, index ascending)
 __device__ __forceinline__ bool before(float ev, int ei, float cs, int cj) { return ev > cs || (ev == cs && ei < cj); }
@@ -93,27 +83,6 @@ __device__ __forceinline__ void list_load(float (&v)[kSlots], int (&ix)[kSlots],
     const int t = kSlots * lane + s;
     v[s] = (vals && t < k) ? vals[t] : -INFINITY;
     ix[s] = (vals && t < k) ? idx[t] : -1;
-  }
-}
-
-// 1. rows row0 .. row0 + 31 -> Zs [32][C + kZPad] as fp32 (rows beyond n are zeros and never become candidates): probe.hip
-__device__ __forceinline__ void stage_rows(float *Zs, const void *__restrict__ z, int z_f16, int ld_z, int row0, int n,
-                                           int C, int tid) {
-  const int pitch = C + kZPad, c4n = C >> 2;
-  for (int i = tid; i < kRows * c4n; i += 256) {
-    const int row = i / c4n, c4 = i - row * c4n;
-    f32x4 v = {0.f, 0.f, 0.f, 0.f};
-    if (row0 + row < n) {
-      const size_t at = (size_t)(row0 + row) * ld_z + 4 * c4;
-      if (z_f16) {
-        const uint2 raw = *reinterpret_cast<const uint2 *>(static_cast<const __half *>(z) + at);
-        const __half2 lo = __builtin_bit_cast(__half2, raw.x), hi = __builtin_bit_cast(__half2, raw.y);
-        v = f32x4{__low2float(lo), __high2float(lo), __low2float(hi), __high2float(hi)};
-      } else {
-        v = *reinterpret_cast<const f32x4 *>(static_cast<const float *>(z) + at);
-      }
-    }
-    *reinterpret_cast<f32x4 *>(Zs + row * pitch + 4 * c4) = v;
   }
 }
 
@@ -168,20 +137,10 @@ __global__ __launch_bounds__(256) void knn_pass_kernel(const float *__restrict__
     const int row0 = tile * kRows;
     stage_rows(Zs, z, z_f16, ld_z, row0, n, C, tid);                 // 1.
     __syncthreads();
-    if (cosine) {                                // thread (row, part): columns 4 (part + 8 i) .. + 3, i ascending
-      const int row = tid >> 3, part = tid & 7;
-      float ss = 0.f;
-      for (int c4 = part; c4 < (C >> 2); c4 += 8) {
-        const f32x4 v = *reinterpret_cast<const f32x4 *>(Zs + row * pitch + 4 * c4);
-        ss += v[0] * v[0];
-        ss += v[1] * v[1];
-        ss += v[2] * v[2];
-        ss += v[3] * v[3];
-      }
-      Np[tid] = ss;                              // (read after the barriers of step 2)
-    }
+    if (cosine) row_squares(Zs, Np, C, tid);     // (read after the barriers of step 2)
 
-    // 2. scores: "B" lane l = Z[row (l & 31)][c + (l >> 5)]
+    // 2. scores: "B" lane l = Z[row (l & 31)][c + (l >> 5)]; the query operand is in registers, so the MFMA loop is this
+    // file's and only the merge of the partial tiles is row_tile.h's
     f32x16 s;
 #pragma unroll
     for (int r = 0; r < 16; ++r) s[r] = 0.f;
@@ -194,29 +153,10 @@ __global__ __launch_bounds__(256) void knn_pass_kernel(const float *__restrict__
         for (int j = 0; j < 4; ++j) s = __builtin_amdgcn_mfma_f32_32x32x2f32(qreg[i][j], a[j], s, 0, 0, 0);
       }
     }
-    // register r of lane l is query 8 (r >> 2) + 4 (l >> 5) + (r & 3), row l & 31; waves 0, 1 write, waves 2, 3 add
-#pragma unroll
-    for (int stage = 0; stage < 2; ++stage) {
-      if ((wid >> 1) == stage) {
-        float *dst = Sp + (wid & 1) * (kRows * kQueries);
-#pragma unroll
-        for (int r = 0; r < 16; ++r) {
-          const int at = (8 * (r >> 2) + 4 * hk + (r & 3)) * kRows + r32;
-          if (stage == 0) dst[at] = s[r];
-          else dst[at] += s[r];
-        }
-      }
-      __syncthreads();
-    }
+    merge_score_slots<false>(Sp, s, s, r32, hk, wid);
 
     // 3. selection: lane r < 32 holds the candidate of row r
-    float rinv = 1.f;
-    if (cosine) {
-      const f32x4 a = *reinterpret_cast<const f32x4 *>(Np + 8 * r32), b = *reinterpret_cast<const f32x4 *>(Np + 8 * r32 + 4);
-      float ss = a[0];
-      ss += a[1], ss += a[2], ss += a[3], ss += b[0], ss += b[1], ss += b[2], ss += b[3];
-      rinv = ss > 0.f ? 1.f / sqrtf(ss) : 0.f;
-    }
+    const float rinv = cosine ? inv_norm(row_n2(Np, r32)) : 1.f;
     const bool row_ok = hk == 0 && row0 + r32 < n;
     const int j = row_base + row0 + r32;
 #pragma unroll
@@ -329,13 +269,10 @@ extern "C" size_t lla_knn_pass_workspace_bytes(int Q, int k) {
 
 extern "C" int lla_knn_pass(const float *q, int ld_q, int Q, const void *z, int z_dtype, int ld_z, int n, int C, int row_base,
                             int k, int metric, const int32_t *q_self, int accumulate, void *workspace, void *stream) {
-  if (!lists_ok(Q, k) || C < 8 || C > 1024 || (C & 7) || n < 0 || row_base < 0 || (long long)row_base + n > INT_MAX ||
-      (metric != 0 && metric != 1) || ld_q < C || ld_z < C || (ld_q & 3) || (ld_z & 3) ||
-      (z_dtype != LLA_Z_F32 && z_dtype != LLA_Z_F16))
+  if (!lists_ok(Q, k) || !cols_ok(C) || !rows_ok(z, z_dtype, ld_z, n, C) || row_base < 0 ||
+      (long long)row_base + n > INT_MAX || (metric != 0 && metric != 1) || ld_q < C || (ld_q & 3))
     return LLA_EINVAL;
-  if (!q || !workspace || (n > 0 && !z)) return LLA_EINVAL;
-  const uintptr_t z_align = z_dtype == LLA_Z_F32 ? 15 : 7;
-  if (((uintptr_t)z & z_align) || ((uintptr_t)q & 15) || ((uintptr_t)workspace & 7)) return LLA_EINVAL;
+  if (!q || !workspace || ((uintptr_t)q & 15) || ((uintptr_t)workspace & 7)) return LLA_EINVAL;
   if (n == 0) return LLA_OK;
 
   const int nqt = query_tiles(Q), P = walkers_of(nqt);

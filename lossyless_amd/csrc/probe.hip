@@ -14,6 +14,7 @@
 //   3. residuals r_ik (-2 y m, or 2 t) in registers, one (row, 4 classes) per thread, written to LDS [row][class];
 //   4. gradient: G[32 classes][C] += R^T Z_tile, a second MFMA whose operands are both in LDS; each wave keeps its
 //      C / 4 columns of the slice in accumulator registers over ALL its row tiles (64 VGPRs at C = 512).
+// Steps 1, 2 and 4 and the ordered sum of the partials are row_tile.h's, shared with knn.hip and kmeans.hip; step 3 is here.
 // z is read from HBM once per class tile; scores and residuals never leave the chip.  At C <= 512 the workgroup needs
 // 78.6 KB of LDS, so two of them share a CU and one's staging runs beside the other's MFMAs.
 //
@@ -50,21 +51,12 @@
 // for the loads, residual 0.  Only step 3 differs: a thread's four columns lie in up to four groups, and it takes
 // (max, sum exp, sum exp t) of each of them itself from that group's K scores in LDS, in class order -- the loop of the
 // softmax pass over another range, so a group's outputs are the bits lla_softmax_pass gives when the grids agree.
-#include "common.h"
-
-#include <hip/hip_fp16.h>
+#include "row_tile.h"
 
 namespace lla {
 namespace {
 
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-typedef float f32x16 __attribute__((ext_vector_type(16)));
-
-constexpr int kRows = 32;          // rows per staged tile
-constexpr int kClasses = 32;       // classes per workgroup
-constexpr int kZPad = 4;           // floats: 16-byte reads of one column group from 32 rows touch 16 distinct slots
 constexpr int kRPitch = kClasses + 1;
-constexpr int kResident = 512;     // workgroups the chip holds at two per CU: the grid is cut to it
 
 // what step 3 computes: lla_svm_pass, lla_svm_grid_pass, lla_softmax_pass, lla_softmax_grid_pass
 enum { kHinge = 0, kGrid = 1, kSoftmax = 2, kSoftGrid = 3 };
@@ -73,8 +65,6 @@ enum { kHinge = 0, kGrid = 1, kSoftmax = 2, kSoftGrid = 3 };
 __host__ __device__ inline int lds_floats(int C, bool softmax = false) {
   return kRows * (C + kZPad) + 2 * kRows * kClasses + kRows * kRPitch + (softmax ? 2 * kClasses : 0);
 }
-inline int class_tiles(int K) { return (K + kClasses - 1) / kClasses; }
-inline int tile_walkers(int nct) { const int w = kResident / nct; return w < 1 ? 1 : w; }
 inline int walkers_max(int K) { return tile_walkers(class_tiles(K)); }
 // softmax grid pass: the columns of a tile that hold whole groups of K classes, and the tiles G groups take
 inline int group_tile_cols(int K) { return (kClasses / K) * K; }
@@ -98,71 +88,6 @@ struct SoftmaxRows {
   // (fold, col_held [G]), and K is the number of real columns, G classes
   int classes;                // classes per group
 };
-
-// 1. rows row0 .. row0 + 31 -> Zs [32][C + kZPad] as fp32 (rows beyond B are zeros: they contribute exactly nothing)
-__device__ __forceinline__ void stage_rows(float *Zs, const void *__restrict__ z, int z_f16, int ld_z, int row0, int B,
-                                           int C, int tid) {
-  const int pitch = C + kZPad, c4n = C >> 2;
-  for (int i = tid; i < kRows * c4n; i += 256) {
-    const int row = i / c4n, c4 = i - row * c4n;
-    f32x4 v = {0.f, 0.f, 0.f, 0.f};
-    if (row0 + row < B) {
-      const size_t at = (size_t)(row0 + row) * ld_z + 4 * c4;
-      if (z_f16) {
-        const uint2 raw = *reinterpret_cast<const uint2 *>(static_cast<const __half *>(z) + at);
-        const __half2 lo = __builtin_bit_cast(__half2, raw.x), hi = __builtin_bit_cast(__half2, raw.y);
-        v = f32x4{__low2float(lo), __high2float(lo), __low2float(hi), __high2float(hi)};
-      } else {
-        v = *reinterpret_cast<const f32x4 *>(static_cast<const float *>(z) + at);
-      }
-    }
-    *reinterpret_cast<f32x4 *>(Zs + row * pitch + 4 * c4) = v;
-  }
-}
-
-// 2. scores of the staged tile against 32 classes: Sp [product][slot][32 classes][32 rows], the C dimension dealt to the
-// four waves in groups of 8 and the four partial tiles added in wave order (gradient mode leaves two slots for the reader
-// to add; HV holds two products in the same bytes).  wp / vp: this lane's row of W / V, + 4 (lane >> 5).  Ends on a barrier.
-template <bool HV>
-__device__ __forceinline__ void tile_scores(const float *Zs, float *Sp, const float *__restrict__ wp,
-                                            const float *__restrict__ vp, int C, int lane, int wid) {
-  constexpr int NSLOT = HV ? 1 : 2;
-  const int pitch = C + kZPad, ngroups = C >> 3;
-  const int r32 = lane & 31, hk = lane >> 5;
-  f32x16 s, tv;
-#pragma unroll
-  for (int r = 0; r < 16; ++r) s[r] = 0.f, tv[r] = 0.f;
-  for (int g = wid; g < ngroups; g += 4) {
-    const f32x4 a = *reinterpret_cast<const f32x4 *>(Zs + r32 * pitch + 8 * g + 4 * hk);
-    const f32x4 w = *reinterpret_cast<const f32x4 *>(wp + 8 * g);
-#pragma unroll
-    for (int j = 0; j < 4; ++j) s = __builtin_amdgcn_mfma_f32_32x32x2f32(w[j], a[j], s, 0, 0, 0);
-    if (HV) {
-      const f32x4 v = *reinterpret_cast<const f32x4 *>(vp + 8 * g);
-#pragma unroll
-      for (int j = 0; j < 4; ++j) tv = __builtin_amdgcn_mfma_f32_32x32x2f32(v[j], a[j], tv, 0, 0, 0);
-    }
-  }
-  // register r of lane l is class 8 (r >> 2) + 4 (l >> 5) + (r & 3), row l & 31
-#pragma unroll
-  for (int stage = 0; stage < 4 / NSLOT; ++stage) {
-    if (wid / NSLOT == stage) {
-      float *dst = Sp + (wid % NSLOT) * (kRows * kClasses);
-#pragma unroll
-      for (int r = 0; r < 16; ++r) {
-        const int at = (8 * (r >> 2) + 4 * hk + (r & 3)) * kRows + r32;
-        if (stage == 0) {
-          dst[at] = s[r];
-          if (HV) dst[kRows * kClasses + at] = tv[r];
-        } else {
-          dst[at] += s[r];
-          if (HV) dst[kRows * kClasses + at] += tv[r];
-        }
-      }
-    }
-    __syncthreads();
-  }
-}
 
 // HV: Hessian-vector mode.  NT: 32-column tiles of the gradient slice per wave (C <= 128 NT).  OBJ: kHinge -- column k is
 // class k, nothing is held out and every weight is 1; kGrid -- the columns are the problems of `cols` (K is their number J);
@@ -366,35 +291,14 @@ __global__ __launch_bounds__(256) void svm_pass_kernel(const void *__restrict__ 
     }
     __syncthreads();
 
-    // 4. gradient slice: "A" lane l = R[row 2 s + (l >> 5)][class l & 31], "B" lane l = Z[row 2 s + (l >> 5)][column]
-#pragma unroll 4
-    for (int s2 = 0; s2 < kRows / 2; ++s2) {
-      const float a = Rs[(2 * s2 + hk) * kRPitch + r32];
-      const float *zrow = Zs + (2 * s2 + hk) * pitch;
-#pragma unroll
-      for (int t = 0; t < NT; ++t) {
-        const int c0 = (wid + 4 * t) * 32;
-        if (c0 < C) {
-          int cc = c0 + r32;
-          if (cc > C - 1) cc = C - 1;          // clamped columns are computed and not stored
-          acc[t] = __builtin_amdgcn_mfma_f32_32x32x2f32(a, zrow[cc], acc[t], 0, 0, 0);
-        }
-      }
-    }
+    // 4. gradient slice: "A" lane l = R[row 2 s + (l >> 5)][class l & 31]
+    slice_mfma(acc, Zs, [&](int row) { return Rs[row * kRPitch + r32]; }, C, lane, wid);
     __syncthreads();                           // the next tile's staging overwrites Zs, Sp and Rs
   }
 
   // this workgroup's partial sums -> workspace (classes beyond K, and the dead columns from `ncols` on of a kSoftGrid tile,
   // hold exact zeros and are never read: svm_reduce_kernel maps output k to slot k % ncols of tile k / ncols)
-  float *pw = part_W + (size_t)(ct * P + p) * kClasses * C;
-#pragma unroll
-  for (int t = 0; t < NT; ++t) {
-    const int cc = (wid + 4 * t) * 32 + r32;
-    if (cc < C) {
-#pragma unroll
-      for (int r = 0; r < 16; ++r) pw[(size_t)(8 * (r >> 2) + 4 * hk + (r & 3)) * C + cc] = acc[t][r];
-    }
-  }
+  slice_store(acc, part_W + (size_t)(ct * P + p) * kClasses * C, C, lane, wid);
 #pragma unroll
   for (int j = 0; j < 4; ++j) {
     Sp[(cl0 + 8 * j) * kRows + rr] = bacc[j];
@@ -489,23 +393,6 @@ __global__ __launch_bounds__(256) void softmax_rows_kernel(const void *__restric
   }
 }
 
-// sum over walkers 0 .. P-1 of src[p * stride], added in that order; the loads go out eight at a time (a thread that
-// waited for each one before asking for the next spent 0.35 ms on 512 partial sums)
-template <typename T>
-__device__ __forceinline__ T ordered_sum(const float *__restrict__ src, size_t stride, int P) {
-  T sum = 0;
-  int p = 0;
-  for (; p + 8 <= P; p += 8) {
-    float v[8];
-#pragma unroll
-    for (int j = 0; j < 8; ++j) v[j] = src[(size_t)(p + j) * stride];
-#pragma unroll
-    for (int j = 0; j < 8; ++j) sum += (T)v[j];
-  }
-  for (; p < P; ++p) sum += (T)src[(size_t)p * stride];
-  return sum;
-}
-
 // out (+)= the partial sums of walkers 0 .. P-1, in that order.  One thread per (class, column); columns C and C + 1
 // of a class are its out_b and out_loss.  ncols: the live columns of a tile (32; a softmax grid pass: 32 / K whole groups),
 // so that output k is slot k % ncols of tile k / ncols.
@@ -541,9 +428,7 @@ const void *pass_kernel(int C) {
 template <int OBJ>
 const void *pass_kernel(bool hv, int C) { return hv ? pass_kernel<true, OBJ>(C) : pass_kernel<false, OBJ>(C); }
 
-bool shape_ok(int C, int K) {
-  return C >= 8 && C <= 1024 && (C & 7) == 0 && K >= 1 && class_tiles(K) <= 65535;
-}
+bool shape_ok(int C, int K) { return cols_ok(C) && K >= 1 && class_tiles(K) <= 65535; }
 
 }  // namespace
 }  // namespace lla
@@ -564,16 +449,11 @@ int svm_pass_launch(int obj, const void *z, int z_dtype, int ld_z, const int32_t
                     const float *b, const float *V, const float *vb, int K, int ld_w, const GridCols *cols,
                     const float *class_weight, float *out_W, float *out_b, double *out_loss, int accumulate,
                     void *workspace, void *stream, int classes) {
-  if (!shape_ok(C, K) || B < 0 || ld_z < C || ld_w < C || (ld_z & 3) || (ld_w & 3) ||
-      (z_dtype != LLA_Z_F32 && z_dtype != LLA_Z_F16))
-    return LLA_EINVAL;
-  if (!W || !b || !out_W || !out_b || !workspace || (V && !vb) || (!V && !out_loss) || (B > 0 && (!z || !y)))
-    return LLA_EINVAL;
+  if (!shape_ok(C, K) || !rows_ok(z, z_dtype, ld_z, B, C) || ld_w < C || (ld_w & 3)) return LLA_EINVAL;
+  if (!W || !b || !out_W || !out_b || !workspace || (V && !vb) || (!V && !out_loss) || (B > 0 && !y)) return LLA_EINVAL;
   if (obj == kGrid && (!cols->col_class || !cols->col_held || !cols->col_cpos || !cols->col_cneg)) return LLA_EINVAL;
   if (obj == kSoftGrid && (classes < 1 || classes > kClasses || (cols->fold && !cols->col_held))) return LLA_EINVAL;
-  const uintptr_t z_align = z_dtype == LLA_Z_F32 ? 15 : 7;
-  if (((uintptr_t)z & z_align) || ((uintptr_t)W & 15) || ((uintptr_t)V & 15) || ((uintptr_t)workspace & 3))
-    return LLA_EINVAL;
+  if (((uintptr_t)W & 15) || ((uintptr_t)V & 15) || ((uintptr_t)workspace & 3)) return LLA_EINVAL;
   if (B == 0 && accumulate) return LLA_OK;
 
   const int ncols = obj == kSoftGrid ? group_tile_cols(classes) : kClasses;      // live columns of a full tile
