@@ -137,6 +137,50 @@ def test_gather_with_forty_channels():
     assert not st.any() and np.array_equal(out[:, :40].numpy(), want[idx]) and (out[:, 40:] == SENTINEL).all()
 
 
+@pytest.mark.parametrize("dtype", [torch.float32, torch.float16])
+def test_gather_with_six_channels_through_the_ragged_scalar_write_out(dtype):
+    """C = 6 is no multiple of 4 (the second 16-byte chunk of a staged line holds two channels) and a pitch of 7 rules out
+    16-byte stores: bit-equal to lla_rans_decode_batch + lla_dequantise, the padding column untouched."""
+    from lossyless_amd import _lib
+    B, C = 70, 6
+    tab, sym, pay, off, _ = coded_case("5e-02", B, 17, C=C)
+    t = {k: _dev(tab[k]) for k in TABLE_KEYS}
+    payload, offsets = _dev(pay), _dev(off.astype(np.int64))
+    s = torch.empty((B, C), dtype=torch.int32, device="cuda")
+    st2 = torch.zeros(B, dtype=torch.int32, device="cuda")
+    z = torch.empty((B, C), dtype=torch.float32, device="cuda")
+    L = _lib.lib()
+    _lib.check(L.lla_rans_decode_batch(_lib.ptr(payload), _lib.ptr(offsets), 0, B, C, _lib.ptr(t["cdf"]), tab["cdf"].shape[1],
+                                       _lib.ptr(t["cdf_len"]), _lib.ptr(t["offset"]), _lib.ptr(s), _lib.ptr(st2),
+                                       _lib.stream_ptr()), "lla_rans_decode_batch")
+    _lib.check(L.lla_dequantise(_lib.ptr(s), B, C, _lib.ptr(t["bias"]), _lib.ptr(t["exp_scale"]), _lib.ptr(t["median"]),
+                                _lib.ptr(z), _lib.stream_ptr()), "lla_dequantise")
+    torch.cuda.synchronize()
+    assert int(st2.max()) == 0 and np.array_equal(s.cpu().numpy(), sym)
+    idx = np.random.default_rng(5).permutation(B)
+    out, st = device_gather(pay, off, 0, idx, tab, dtype=dtype, ld=7)
+    want = z.cpu()[torch.from_numpy(idx)].to(dtype)
+    assert not st.any() and torch.equal(out[:, :C], want) and (out[:, C:] == SENTINEL).all()
+
+
+def test_gather_zeroes_an_overrun_row_and_keeps_its_neighbours():
+    """Record 100 starts 8 bytes late: it still opens and then runs past its end (the host twin says so first).  Its row is
+    zeroed after the workgroup has written it; every other row of both workgroups is untouched."""
+    B, r = 257, 100
+    tab, _, pay, off, _ = coded_case("5e-02", B, 21, C=40)
+    cut = off.copy()
+    cut[r] = off[r] + 8
+    idx = np.arange(B)
+    rc, _, hst = host_gather(pay, cut, 0, idx, tab)
+    assert rc == 0 and hst[r] == 1 and int(hst.sum()) == 1
+    whole, st0 = device_gather(pay, off, 0, idx, tab)
+    out, st = device_gather(pay, cut, 0, idx, tab)
+    keep = [i for i in range(B) if i != r]
+    assert not st0.any() and np.array_equal(st.numpy(), hst)
+    assert not out[r].any() and torch.equal(out[keep], whole[keep])
+    assert torch.equal(out[[r - 1, r + 1, 256]], whole[[r - 1, r + 1, 256]])     # (named: same workgroup, and the second one)
+
+
 def test_gather_of_edge_rows(tables):
     rows = edge_rows(tables)
     pay, off, want = code_rows(rows, tables)
