@@ -1,7 +1,8 @@
 """torch.hub entry points with the reference's factory names and return shape
 (reference hubconf.py:22-52): ``clip_compressor_b005``, ``clip_compressor_b001`` and
 ``clip_compressor_b01``, each ``(device=..., **kwargs) -> (compressor, transform)``; ``clip_compressor(state_dict)`` and
-``clip_hyperprior_compressor(state_dict)`` take a rate point of the caller's.
+``clip_hyperprior_compressor(state_dict)`` take a rate point of the caller's; ``feature_compressor(state_dict)`` is the
+same dataset surface for a matrix of features from any other encoder, at the width the state dict has.
 
 The reference fetches one state-dict per rate point from its GitHub release
 (hubconf.py:15,23-26).  Here the three state-dicts ship inside the package with their integer
@@ -18,6 +19,7 @@ import torch
 
 from lossyless_amd import ClipCompressor as _Compressor
 from lossyless_amd import HyperpriorClipCompressor as _HyperpriorCompressor
+from lossyless_amd import FeatureCompressor as _FeatureCompressor
 
 _ASSET_DIR = pathlib.Path(__file__).resolve().parent / "lossyless_amd" / "assets"
 _ASSET_NAME = "beta{beta:0.0e}_factorized_rate.pt"
@@ -100,6 +102,23 @@ def clip_compressor(state_dict, device=_ON, **kwargs):
     """
     model = _Compressor(pretrained_state_dict=state_dict, device=device, **kwargs)
     return model, model.preprocess
+
+
+def feature_compressor(state_dict, device=_ON):
+    """Entropy-bottleneck compressor for FEATURES of any frozen encoder, at any width: ``clip_compressor`` without the tower
+    and without CLIP weights.
+
+    state_dict   : a factorized rate point -- ``lossyless_amd.BottleneckFit(beta).fit(Z).state_dict()`` on the features to
+                   compress, or the reference's ``HRateFactorizedPrior`` -- as a dict or a path to it.  ``z_dim`` is read
+                   from it (1024 for the RN50 CLIP tower, 2048 for the reference's SimCLR / SwAV ResNets, ...).
+    device       : "cuda", or "cpu" for the library's host coder (same bytes, same values)
+
+    Returns the compressor alone (there are no images, hence no transform): ``compressor(Z)`` -> reconstructed rows,
+    ``compress`` / ``decompress`` / ``get_rate``, ``compress_dataset(Z, file, label_file=None, labels=None)`` with ``Z`` a
+    ``[N, z_dim]`` tensor or an iterable of batches, ``decompress_dataset`` and ``open_dataset`` (the reference's ``.bin``
+    format; at 512 dimensions the file ``clip_compressor`` writes for the same embeddings).
+    """
+    return _FeatureCompressor(pretrained_state_dict=state_dict, device=device)
 
 
 def clip_text_encoder(clip_weights=None, device=_ON, **kwargs):

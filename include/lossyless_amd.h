@@ -225,6 +225,62 @@ int lla_rans_decode_gather_host(const uint8_t *payload, const uint64_t *off, int
                                 const float *exp_scale, const float *median, void *z_hat, int z_dtype,
                                 size_t ld_out, int32_t *status);
 
+/* ------------------------------------------------------------------------- *
+ * Windowed ("wide") factorized coder: any C, any W <= LLA_WIDE_MAX_W
+ * ------------------------------------------------------------------------- *
+ * The entry points above keep the whole u16 table [C][W] and the per-channel parameters resident in 64 KiB of LDS
+ * and return LLA_EINVAL for a shape that does not fit (C = 512: the encoder from W = 49; C = 1024: from W = 29 or
+ * earlier, the shipped width included).  The *_wide entry
+ * points code the same streams -- byte for byte, symbol for symbol, bit for bit -- with the table passing through
+ * LDS in WINDOWS of channels: one record per lane, all lanes of a workgroup walk the channel index in lock-step, so
+ * at any moment the workgroup needs the rows of one window only.  The next window's rows are fetched while the
+ * current one is coded (two LDS buffers).  The byte stream does not depend on the window.
+ *
+ * window_channels: 0 = the library chooses (lla_rans_wide_window reports the choice); otherwise a positive multiple
+ *   of 4 (the encoder's group of channels; a multiple of 16 suits the gathered decoder's 16-channel staging best).
+ *   A request above 256 or above C rounded up to 4 is clamped to that.  LLA_EINVAL for a value that is no
+ *   multiple of 4, or whose two buffers do not fit 64 KiB of LDS.
+ * Refusals, before any launch: W > LLA_WIDE_MAX_W (the smallest window, 4 channels, no longer fits the gathered
+ *   decoder's LDS: 2 x 4 x W x 2 bytes of rows + 16.3 KiB of staging > 64 KiB; one bound for all three entry points);
+ *   null pointers; the argument errors of the resident entry points.  B == 0: LLA_OK, no launch.
+ * They take EVERY shape within that bound, the ones the resident entry points take included (slower there:
+ * profiles/wide_coder.txt), so a caller chooses with lla_rans_table_fits. */
+#define LLA_WIDE_MAX_W 3000
+#define LLA_CODER_ENCODE 0 /* lla_rans_encode_batch, lla_quantise_encode                */
+#define LLA_CODER_DECODE 1 /* lla_rans_decode_batch, lla_rans_decode_batch_strided      */
+#define LLA_CODER_GATHER 2 /* lla_rans_decode_gather, lla_rans_decode_gather_strided    */
+/* 1 when the RESIDENT entry points of `kind` take a table of C channels x W entries, 0 when they return LLA_EINVAL
+ * for it (or for any C <= 0, W < 3, unknown kind).  Host arithmetic only: no device is touched. */
+int lla_rans_table_fits(int C, int W, int kind);
+/* The window (channels) the wide entry point of `kind` codes a C x W table with when given `window_channels`, and,
+ * if lds_bytes is not NULL, the dynamic LDS of that launch.  LLA_EINVAL exactly where that entry point would refuse
+ * the shape or the window.  Host arithmetic only. */
+int lla_rans_wide_window(int C, int W, int kind, int window_channels, size_t *lds_bytes);
+
+#define LLA_Z_SYMBOLS 0 /* lla_quantise_encode_wide only: `z` holds int32 symbols */
+/* lla_quantise_encode for any table width: same arguments, same end-aligned scratch, lengths and symbols_out.
+ * z_dtype LLA_Z_F16 / LLA_Z_F32 as there; LLA_Z_SYMBOLS makes it lla_rans_encode_batch: z [dev] B*C int32 symbols,
+ * bias / exp_scale / median are not read (may be NULL) and symbols_out, if given, receives a copy. */
+int lla_quantise_encode_wide(const void *z, int z_dtype, int B, int C, const float *bias,
+                             const float *exp_scale, const float *median, const int32_t *cdf, int W,
+                             const int32_t *cdf_len, const int32_t *offset, uint8_t *scratch,
+                             size_t stride, uint32_t *lengths, int32_t *symbols_out, int window_channels,
+                             void *stream);
+/* lla_rans_decode_batch_strided for any table width: same arguments, values and statuses (an unopenable stream:
+ * status 1, row of zeros).  status may be NULL. */
+int lla_rans_decode_batch_wide(const uint8_t *payload, const uint64_t *off, int record_prefix, int off_first,
+                               int off_step, int B, int C, const int32_t *cdf, int W, const int32_t *cdf_len,
+                               const int32_t *offset, int32_t *symbols_out, int32_t *status,
+                               int window_channels, void *stream);
+/* lla_rans_decode_gather_strided for any table width: gather + decode + dequantise, fp16 or fp32 rows at ld_out,
+ * statuses 0 / 1 / 2 and zeroed rows exactly as there; a lane without a record stays with its workgroup to the last
+ * window, so its neighbours' rows are complete. */
+int lla_rans_decode_gather_wide(const uint8_t *payload, const uint64_t *off, int record_prefix, int off_first,
+                                int off_step, int N, const int64_t *index, int B, int C, const int32_t *cdf,
+                                int W, const int32_t *cdf_len, const int32_t *offset, const float *bias,
+                                const float *exp_scale, const float *median, void *z_hat, int z_dtype,
+                                size_t ld_out, int32_t *status, int window_channels, void *stream);
+
 /* The same two coder calls with an arbitrary table row per symbol, i.e. the full
  * ans.RansEncoder().encode_with_indexes(symbols, indexes, cdfs, cdfs_sizes, offsets) /
  * ans.RansDecoder().decode_with_indexes(...) signatures as GaussianConditional.compress /

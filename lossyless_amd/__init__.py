@@ -27,6 +27,7 @@ if not _keep:
 
 from .compressor import ClipCompressor  # noqa: F401
 from .hyperprior_compressor import HyperpriorClipCompressor  # noqa: F401
+from .feature_compressor import FeatureCompressor  # noqa: F401
 from .entropy import EntropyBottleneck  # noqa: F401
 from .latents import CompressedLatents, HyperpriorLatents  # noqa: F401
 from .probe import LinearProbe, LinearProbeCV, LogisticProbe, LogisticProbeCV, MLPProbe  # noqa: F401
@@ -36,4 +37,4 @@ from .clip_text import TextTransformer, synthetic_text_state_dict  # noqa: F401
 from .bottleneck_fit import BottleneckFit, bottleneck_noise  # noqa: F401
 from .hyperprior_fit import HyperpriorFit, hyperprior_noise  # noqa: F401
 
-__all__ = ["ClipCompressor", "HyperpriorClipCompressor", "CompressedLatents", "HyperpriorLatents", "LinearProbe", "LinearProbeCV", "LogisticProbe", "LogisticProbeCV", "MLPProbe", "BatchNormMLPProbe", "KNNProbe", "KMeansProbe", "RidgeProbe", "RidgeProbeCV", "ZeroShotProbe", "TextTransformer", "synthetic_text_state_dict", "BottleneckFit", "bottleneck_noise", "HyperpriorFit", "hyperprior_noise", "philox4x32_10", "dropout_keep", "lr_schedule", "EntropyBottleneck", "VisionTransformer", "synthetic_vit_state_dict"]
+__all__ = ["ClipCompressor", "HyperpriorClipCompressor", "FeatureCompressor", "CompressedLatents", "HyperpriorLatents", "LinearProbe", "LinearProbeCV", "LogisticProbe", "LogisticProbeCV", "MLPProbe", "BatchNormMLPProbe", "KNNProbe", "KMeansProbe", "RidgeProbe", "RidgeProbeCV", "ZeroShotProbe", "TextTransformer", "synthetic_text_state_dict", "BottleneckFit", "bottleneck_noise", "HyperpriorFit", "hyperprior_noise", "philox4x32_10", "dropout_keep", "lr_schedule", "EntropyBottleneck", "VisionTransformer", "synthetic_vit_state_dict"]

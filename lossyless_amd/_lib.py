@@ -16,6 +16,8 @@ LLA_OK = 0
 LLA_EINVAL, LLA_ECAP, LLA_EHIP, LLA_EDATA = -1, -2, -3, -4      # (include/lossyless_amd.h)
 ABI_VERSION = 4
 LLA_Z_F16, LLA_Z_F32 = 1, 2
+LLA_Z_SYMBOLS = 0                                             # lla_quantise_encode_wide: int32 symbols in
+CODER_ENCODE, CODER_DECODE, CODER_GATHER = 0, 1, 2            # LLA_CODER_*: `kind` of lla_rans_table_fits
 LLA_LAYOUT_NHWC, LLA_LAYOUT_NCHW = 0, 1
 LLA_EPI_F16, LLA_EPI_QUICKGELU_F16, LLA_EPI_RESID_F32, LLA_EPI_RELU_F16, LLA_EPI_ADD_RELU_F16 = 0, 1, 2, 4, 5
 _ERR = {-1: "LLA_EINVAL", -2: "LLA_ECAP", -3: "LLA_EHIP", -4: "LLA_EDATA"}
@@ -66,6 +68,13 @@ _SIGNATURES = {
                                               ctypes.c_float, _vp, _i, _i, _vp, _vp, _vp, _i, _sz, _vp, _vp, _vp]),
     "lla_gaussian_decode_gather_means_lds_bytes": (_sz, [_i, _i, _i, _i, _vp]),
     "lla_rans_decode_gather_host": (_i, [_vp, _vp, _i, _i, _vp, _i, _i, _vp, _i, _vp, _vp, _vp, _vp, _vp, _vp, _i, _sz, _vp]),
+    # the windowed coder (any table width): the resident forms' arguments + `window_channels` in front of `stream`
+    "lla_rans_table_fits": (_i, [_i, _i, _i]),
+    "lla_rans_wide_window": (_i, [_i, _i, _i, _i, _vp]),
+    "lla_quantise_encode_wide": (_i, [_vp, _i, _i, _i, _vp, _vp, _vp, _vp, _i, _vp, _vp, _vp, _sz, _vp, _vp, _i, _vp]),
+    "lla_rans_decode_batch_wide": (_i, [_vp, _vp, _i, _i, _i, _i, _i, _vp, _i, _vp, _vp, _vp, _vp, _i, _vp]),
+    "lla_rans_decode_gather_wide": (_i, [_vp, _vp, _i, _i, _i, _i, _vp, _i, _i, _vp, _i, _vp, _vp, _vp, _vp, _vp, _vp, _i,
+                                         _sz, _vp, _i, _vp]),
     "lla_rans_encode_indexed": (_i, [_vp, _vp, _i, _i, _vp, _i, _i, _vp, _vp, _vp, _sz, _vp, _vp]),
     "lla_rans_decode_indexed": (_i, [_vp, _vp, _i, _i, _i, _vp, _vp, _i, _i, _vp, _vp, _vp, _vp, _vp]),
     "lla_dequantise": (_i, [_vp, _i, _i, _vp, _vp, _vp, _vp, _vp]),

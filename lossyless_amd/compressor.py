@@ -139,7 +139,11 @@ class ClipCompressor(nn.Module):
         super().__init__()
         self._init_tower(clip_weights, vit_chunk, gpu_preprocess)
         self.side_z_dim = 512 // 5
+        self._init_rate_model(pretrained_state_dict, device)
 
+    def _init_rate_model(self, pretrained_state_dict, device):
+        """The per-dimension affine and the entropy bottleneck over ``self.z_dim`` channels, loaded from the state dict (a
+        dict or a path) and moved to ``device``: everything behind the tower, shared with ``FeatureCompressor``."""
         self.scaling = torch.nn.Parameter(torch.ones(self.z_dim))
         self.biasing = torch.nn.Parameter(torch.zeros(self.z_dim))
 
@@ -210,7 +214,8 @@ class ClipCompressor(nn.Module):
             return [blob[int(off[i]):int(off[i + 1])] for i in range(z.shape[0])]
         B, C = z.shape
         out = torch.empty((B, C), dtype=torch.float32, device=z.device)
-        rc = _lib.lib().lla_represent(_lib.ptr(z), _lib.LLA_Z_F16, B, C, _lib.ptr(tables["bias"]),
+        zt = _lib.LLA_Z_F16 if z.dtype == torch.float16 else _lib.LLA_Z_F32     # (the tower's rows are fp16)
+        rc = _lib.lib().lla_represent(_lib.ptr(z), zt, B, C, _lib.ptr(tables["bias"]),
                                       _lib.ptr(tables["exp_scale"]), _lib.ptr(tables["median"]),
                                       _lib.ptr(out), _lib.stream_ptr(z.device))
         _lib.check(rc, "lla_represent")
@@ -380,17 +385,22 @@ class ClipCompressor(nn.Module):
             n_all = n_local
 
         if rank == 0:
-            with Path(file).open("wb") as f:
-                f.write(struct.pack(">I", n_all * self.records_per_image))   # write_uints(f, (len(Z_bytes),))
-                f.write(body.tobytes())             # records x { >I len, bytes }
-            enc_time = (time.time() - start) / max(n_all, 1)
-            rate = 8 * Path(file).stat().st_size / max(n_all, 1)
-            if label_file is not None:
-                np.save(label_file, labels, allow_pickle=False)  # no pickle for portability
-            if is_info:
-                print(f"Rate: {rate:.2f} bits/img | Encoding: {1/enc_time:.2f} img/sec ")
+            self._write_container(file, body, n_all, labels, label_file, start, is_info)
         if world > 1:
             lla_dist.barrier()
+
+    def _write_container(self, file, body, n_all, labels, label_file, start, is_info):
+        """The reference's container (hub/compressor.py:192-207): the record count, the length-prefixed records ``body``
+        (uint8 array), the labels next to it, the printed line."""
+        with Path(file).open("wb") as f:
+            f.write(struct.pack(">I", n_all * self.records_per_image))   # write_uints(f, (len(Z_bytes),))
+            f.write(body.tobytes())             # records x { >I len, bytes }
+        enc_time = (time.time() - start) / max(n_all, 1)
+        rate = 8 * Path(file).stat().st_size / max(n_all, 1)
+        if label_file is not None:
+            np.save(label_file, labels, allow_pickle=False)  # no pickle for portability
+        if is_info:
+            print(f"Rate: {rate:.2f} bits/img | Encoding: {1/enc_time:.2f} img/sec ")
 
     @torch.no_grad()
     def encode_batch_records(self, x):

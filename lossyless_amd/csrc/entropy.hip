@@ -198,6 +198,252 @@ __global__ __launch_bounds__(kEncThreads) void rans_decode_gather_kernel(
 }
 
 // ---------------------------------------------------------------------------
+// The three kernels above for a table of any width: the rows and the per-channel parameters pass
+// through LDS in WINDOWS of `wc` channels, two buffers, instead of being resident.  All lanes of a workgroup walk the
+// channel index in lock-step, so the workgroup needs one window at a time; window k holds channels [k * wc,
+// min(C, (k + 1) * wc)), wc a multiple of 4: the borders lie on encode_walk<4>'s group grid counted from channel 0 and
+// the C % 4 tail belongs to the last window.  The encoder walks the windows (and the channels in each) DESCENDING, the
+// decoders ascending; a symbol's arithmetic is rans.h's, so the streams are the resident kernels' byte for byte,
+// whatever wc is.
+// One barrier per window.  In iteration w: the loads of window w' (the next one) are issued into registers
+// (window_fetch: kWinQuads 16-byte loads of rows and one channel's parameters per thread), what the registers do not
+// hold is written straight into the other buffer (window_rest: the rows past the first kWinRegEntries entries), window w
+// is coded from its buffer, the registers are parked in the other buffer (window_park), barrier.  The other buffer is
+// free all that time: its last readers passed the barrier that ended the previous iteration.
+// NO lane leaves before the last barrier: one without a record (past B, bad index, unopenable stream) skips the
+// coding and nothing else.
+// ---------------------------------------------------------------------------
+constexpr int kWinQuads = 4;                              // 16-byte loads per thread in flight across a window's coding
+constexpr int kWinMaxChannels = kEncThreads;              // one thread fetches one channel's parameters
+constexpr int kWinRegEntries = kWinQuads * 4 * kEncThreads;   // table entries the registers of a workgroup hold
+constexpr size_t kWideLdsMax = 64 * 1024;      // what a launch may ask for
+constexpr size_t kWideLdsBudget = 56 * 1024;   // what the library's own choice of window stays within
+
+struct WindowRegs {
+  int4 q[kWinQuads];
+  ChanParams p;
+};
+struct WindowSrc {   // bias / es / med may be null (no quantiser): zeros
+  const int32_t *cdf, *cdf_len, *offset;
+  const float *bias, *es, *med;
+  int W, C;
+};
+struct WindowBuf {
+  uint16_t *tab;     // [n][W]
+  ChanParams *par;   // [n]
+};
+__host__ __device__ inline size_t window_buf_bytes(int wc, int W) { return enc_table_bytes(wc, W) + (size_t)wc * sizeof(ChanParams); }
+__host__ __device__ inline size_t wide_lds_bytes(int wc, int W, bool gather) {
+  return 2 * window_buf_bytes(wc, W) + (gather ? kVoteBytes + kGatherStageBytes : 0);
+}
+__device__ __forceinline__ WindowBuf window_buf(uint8_t *smem, int b, int wc, int W) {
+  uint8_t *base = smem + (size_t)b * window_buf_bytes(wc, W);
+  return WindowBuf{reinterpret_cast<uint16_t *>(base), reinterpret_cast<ChanParams *>(base + enc_table_bytes(wc, W))};
+}
+// rows of channels [c_lo, c_lo + n) are n * W consecutive entries; c_lo * W * 4 bytes is a multiple of 16 (c_lo of 4)
+__device__ __forceinline__ int window_quads(const WindowSrc &t, int n) {
+  return ((reinterpret_cast<uintptr_t>(t.cdf) & 15u) == 0) ? (n * t.W) >> 2 : 0;
+}
+__device__ __forceinline__ void window_fetch(WindowRegs &r, const WindowSrc &t, int c_lo, int n) {
+  const int4 *src = reinterpret_cast<const int4 *>(t.cdf + (size_t)c_lo * t.W);
+  const int quads = window_quads(t, n);
+#pragma unroll
+  for (int u = 0; u < kWinQuads; ++u) {
+    const int i = (int)threadIdx.x + u * kEncThreads;
+    r.q[u] = i < quads ? src[i] : int4{0, 0, 0, 0};
+  }
+  if ((int)threadIdx.x < n) {
+    const int c = c_lo + (int)threadIdx.x;
+    r.p.bias = t.bias ? t.bias[c] : 0.f;
+    r.p.es = t.es ? t.es[c] : 0.f;
+    r.p.med = t.med ? t.med[c] : 0.f;
+    r.p.off = t.offset[c];
+    r.p.len = t.cdf_len[c];
+  }
+}
+__device__ __forceinline__ void put_quad(uint16_t *tab, int i, const int4 &q) {
+  typedef unsigned short u16x4 __attribute__((ext_vector_type(4)));
+  *reinterpret_cast<u16x4 *>(tab + 4 * i) = u16x4{(unsigned short)q.x, (unsigned short)q.y, (unsigned short)q.z, (unsigned short)q.w};
+}
+__device__ __forceinline__ void window_park(const WindowRegs &r, const WindowBuf &b, const WindowSrc &t, int n) {
+  const int quads = window_quads(t, n);
+#pragma unroll
+  for (int u = 0; u < kWinQuads; ++u) {
+    const int i = (int)threadIdx.x + u * kEncThreads;
+    if (i < quads) put_quad(b.tab, i, r.q[u]);
+  }
+  if ((int)threadIdx.x < n) b.par[threadIdx.x] = r.p;
+}
+__device__ __forceinline__ void window_rest(const WindowBuf &b, const WindowSrc &t, int c_lo, int n) {
+  const int32_t *cdf = t.cdf + (size_t)c_lo * t.W;
+  const int4 *src = reinterpret_cast<const int4 *>(cdf);
+  const int quads = window_quads(t, n);
+  for (int i = kWinRegEntries / 4 + (int)threadIdx.x; i < quads; i += kEncThreads) put_quad(b.tab, i, src[i]);
+  for (int i = 4 * quads + (int)threadIdx.x; i < n * t.W; i += kEncThreads) b.tab[i] = (uint16_t)cdf[i];
+}
+// window k of a C-channel string
+__device__ __forceinline__ int window_lo(int k, int wc) { return k * wc; }
+__device__ __forceinline__ int window_n(int k, int wc, int C) { return min(wc, C - k * wc); }
+
+// Calls code(buf, c_lo, n) for every window, from `first` in steps of `step` (+1 / -1), nwin of them, with the
+// staging described above around it.  Every thread of the workgroup calls it.
+template <typename Code>
+__device__ __forceinline__ void walk_windows(uint8_t *smem, const WindowSrc &t, int wc, int first, int step, int nwin,
+                                             Code &&code) {
+  WindowRegs r;
+  {
+    const WindowBuf b0 = window_buf(smem, 0, wc, t.W);
+    const int lo = window_lo(first, wc), n = window_n(first, wc, t.C);
+    window_fetch(r, t, lo, n);
+    window_rest(b0, t, lo, n);
+    window_park(r, b0, t, n);
+  }
+  __syncthreads();
+  for (int i = 0, k = first; i < nwin; ++i, k += step) {
+    const WindowBuf cur = window_buf(smem, i & 1, wc, t.W), nxt = window_buf(smem, (i & 1) ^ 1, wc, t.W);
+    const bool more = i + 1 < nwin;   // uniform
+    int lo2 = 0, n2 = 0;
+    if (more) {
+      lo2 = window_lo(k + step, wc), n2 = window_n(k + step, wc, t.C);
+      window_fetch(r, t, lo2, n2);
+      window_rest(nxt, t, lo2, n2);
+    }
+    code(cur, window_lo(k, wc), window_n(k, wc, t.C));
+    if (more) window_park(r, nxt, t, n2);
+    __syncthreads();
+  }
+}
+
+template <int ZMODE>
+__global__ __launch_bounds__(kEncThreads) void rans_encode_wide_kernel(
+    const void *__restrict__ in, int B, int C, const float *__restrict__ bias, const float *__restrict__ exp_scale,
+    const float *__restrict__ median, const int32_t *__restrict__ cdf, int W, const int32_t *__restrict__ cdf_len,
+    const int32_t *__restrict__ offset, uint8_t *__restrict__ scratch, size_t stride, uint32_t *__restrict__ lengths,
+    int32_t *__restrict__ symbols_out, int wc) {
+  kernel_acquire();
+  extern __shared__ __attribute__((aligned(16))) uint8_t smem[];
+  using elem = typename Fetch<ZMODE>::elem;
+  constexpr int G = 4;   // encode_walk's group here, for every input type: the window borders' grid
+  const WindowSrc t{cdf, cdf_len, offset, ZMODE ? bias : nullptr, ZMODE ? exp_scale : nullptr, ZMODE ? median : nullptr, W, C};
+  const int nwin = (C + wc - 1) / wc;
+
+  const int img = blockIdx.x * kEncThreads + threadIdx.x;
+  const bool live = img < B;
+  const elem *src = reinterpret_cast<const elem *>(in) + (size_t)(live ? img : 0) * C;
+  const bool vec_ok = (reinterpret_cast<uintptr_t>(src) & (G * sizeof(elem) - 1)) == 0;
+  EncState s;
+  uint8_t *end = nullptr;
+  if (live) end = open_encoder(s, scratch, stride, img);
+
+  walk_windows(smem, t, wc, nwin - 1, -1, nwin, [&](const WindowBuf &b, int c_lo, int n) {
+    if (!live) return;
+    elem v[G];
+    auto load = [&](int c0, auto n_c) {
+      constexpr int N = decltype(n_c)::value;
+      const elem *p = src + c_lo + c0;
+      if constexpr (N == 1) {
+        v[0] = p[0];
+      } else if (vec_ok) {
+        using vec = std::conditional_t<sizeof(elem) == 2, uint2, uint4>;
+        *reinterpret_cast<vec *>(v) = *reinterpret_cast<const vec *>(p);
+      } else {
+#pragma unroll
+        for (int k = 0; k < G; ++k) v[k] = p[k];
+      }
+    };
+    auto prep = [&](int c, int k) {
+      const ChanParams q = b.par[c];
+      int32_t sym;
+      if constexpr (ZMODE == 0) sym = v[k];
+      else sym = quantise_one(as_float(v[k]), q.bias, q.es, q.med);
+      if (symbols_out) symbols_out[(size_t)img * C + c_lo + c] = sym;
+      return prepare_channel(b.tab + c * W, q.len, q.off, sym);
+    };
+    encode_walk<G>(s, n, load, prep);
+  });
+  if (live) close_encoder(s, end, lengths, img);
+}
+
+__global__ __launch_bounds__(kEncThreads) void rans_decode_wide_kernel(
+    const uint8_t *__restrict__ payload, const uint64_t *__restrict__ off, int skip, int off_step, int B, int C,
+    const int32_t *__restrict__ cdf, int W, const int32_t *__restrict__ cdf_len, const int32_t *__restrict__ offset,
+    int32_t *__restrict__ out, int32_t *__restrict__ status, int wc) {
+  extern __shared__ __attribute__((aligned(16))) uint8_t smem[];
+  const WindowSrc t{cdf, cdf_len, offset, nullptr, nullptr, nullptr, W, C};
+  const int nwin = (C + wc - 1) / wc;
+
+  const int img = blockIdx.x * kEncThreads + threadIdx.x;
+  DecState s;
+  int32_t *dst = out + (size_t)(img < B ? img : 0) * C;
+  bool live = false;
+  if (img < B) {
+    live = open_stream(s, payload, off, skip, (size_t)img * (size_t)off_step);
+    if (!live) {
+      for (int c = 0; c < C; ++c) dst[c] = 0;
+      if (status) status[img] = 1;
+    }
+  }
+  walk_windows(smem, t, wc, 0, 1, nwin, [&](const WindowBuf &b, int c_lo, int n) {
+    if (!live) return;
+    for (int c = 0; c < n; ++c) {
+      const ChanParams q = b.par[c];
+      dst[c_lo + c] = decode_symbol<false>(s, b.tab + c * W, q.len) + q.off;
+    }
+  });
+  if (live && status) status[img] = s.pos > s.nwords ? 1 : 0;
+}
+
+template <typename OutT>
+__global__ __launch_bounds__(kEncThreads) void rans_decode_gather_wide_kernel(
+    const uint8_t *__restrict__ payload, const uint64_t *__restrict__ off, int skip, int off_first, int off_step, int N,
+    const int64_t *__restrict__ index, int B, int C, const int32_t *__restrict__ cdf, int W,
+    const int32_t *__restrict__ cdf_len, const int32_t *__restrict__ offset, const float *__restrict__ bias,
+    const float *__restrict__ exp_scale, const float *__restrict__ median, OutT *__restrict__ out, size_t ld_out,
+    int32_t *__restrict__ status, int wc) {
+  extern __shared__ __attribute__((aligned(16))) uint8_t smem[];
+  const WindowSrc t{cdf, cdf_len, offset, bias, exp_scale, median, W, C};
+  const int nwin = (C + wc - 1) / wc;
+  int *vote = reinterpret_cast<int *>(smem + 2 * window_buf_bytes(wc, W));
+  float4 *stage = reinterpret_cast<float4 *>(smem + 2 * window_buf_bytes(wc, W) + kVoteBytes);
+  if (threadIdx.x == 0) *vote = 0;   // (walk_windows' first barrier comes before any use)
+
+  const GatherLanes g = gather_lanes(B);
+  const int lane = g.lane, img = g.img;
+  int st;
+  DecState s;
+  const bool live = pick_record(s, st, img, B, index, N, payload, off, skip, off_first, off_step);
+  const bool vec_ok = out_vec_ok(out, ld_out);
+
+  // blocks of kGatherG channels from the window's first channel (a multiple of 4: 16-byte stores stay aligned); the
+  // last block of a window may be short, and write_out is told the window's end as the row's
+  walk_windows(smem, t, wc, 0, 1, nwin, [&](const WindowBuf &b, int c_lo, int n) {
+    for (int c0 = 0; c0 < n; c0 += kGatherG) {
+      float v[kGatherG];
+#pragma unroll
+      for (int k = 0; k < kGatherG; ++k) {
+        const int c = c0 + k;
+        v[k] = 0.f;
+        if (live && c < n) {
+          const ChanParams q = b.par[c];
+          const int32_t sym = decode_symbol<false>(s, b.tab + c * W, q.len) + q.off;
+          v[k] = dequantise_one((float)sym, q.bias, q.es, q.med);
+        }
+      }
+#pragma unroll
+      for (int j = 0; j < kChunks; ++j)
+        park_own(stage, lane, j, float4{v[4 * j], v[4 * j + 1], v[4 * j + 2], v[4 * j + 3]});
+      __syncthreads();
+      write_out(stage, out, ld_out, g, c_lo + c0, c_lo + n, vec_ok);
+      __syncthreads();
+    }
+  });
+
+  if (live && s.pos > s.nwords) st = 1;
+  if (img < B && status) status[img] = st;
+  zero_overrun(vote, live && st == 1, out, ld_out, img, C);
+}
+
+// ---------------------------------------------------------------------------
 // Arbitrary table row per symbol (compressai encode_with_indexes / decode_with_indexes as
 // GaussianConditional uses them: lossyless/rates.py:694-729).  One string per lane; rows are
 // read from global memory (a 64-level scale table is T x W = 64 x ~3100 int32, too large for
@@ -595,6 +841,104 @@ int lla_rans_decode_gather(const uint8_t *payload, const uint64_t *off, int reco
                            size_t ld_out, int32_t *status, void *stream) {
   return lla_rans_decode_gather_strided(payload, off, record_prefix, 0, 1, N, index, B, C, cdf, W, cdf_len, offset,
                                         bias, exp_scale, median, z_hat, z_dtype, ld_out, status, stream);
+}
+
+// --- the windowed coder ---
+int lla_rans_table_fits(int C, int W, int kind) {
+  // the resident launchers' own tests: table_args_ok's bound on the table, then the launch's LDS
+  if (C <= 0 || W < 3 || (size_t)C * W * 2 > 64 * 1024) return 0;
+  size_t lds;
+  if (kind == LLA_CODER_ENCODE) lds = enc_lds_bytes(C, W);
+  else if (kind == LLA_CODER_DECODE) lds = enc_table_bytes(C, W) + (size_t)C * sizeof(int2);
+  else if (kind == LLA_CODER_GATHER) lds = gather_lds_bytes(C, W);
+  else return 0;
+  return lds <= 64 * 1024 ? 1 : 0;
+}
+
+int lla_rans_wide_window(int C, int W, int kind, int window_channels, size_t *lds_bytes) {
+  if (C <= 0 || W < 3 || W > LLA_WIDE_MAX_W || kind < LLA_CODER_ENCODE || kind > LLA_CODER_GATHER || window_channels < 0 ||
+      (window_channels & 3))
+    return LLA_EINVAL;
+  const bool gather = kind == LLA_CODER_GATHER;
+  const int cap = C >= kWinMaxChannels ? kWinMaxChannels : (C + 3) & ~3;
+  int wc;
+  if (window_channels) {
+    wc = window_channels < cap ? window_channels : cap;
+    if (wide_lds_bytes(wc, W, gather) > kWideLdsMax) return LLA_EINVAL;
+  } else {
+    // the largest multiple of 16, up to kWinMaxChannels, whose launch stays within kWideLdsBudget (56 KiB: two workgroups
+    // on a CU with room to spare, no opt-in above 64 KiB); measured (profiles/wide_coder.txt): fewer, larger windows win --
+    // a window costs a barrier and the part of its loads that window_fetch's registers do not keep in flight costs less
+    // than that -- and LDS is free at one record per lane (B = 65536 is one workgroup per CU).  16 for rows too long for
+    // that, fewer where even those do not fit (W <= LLA_WIDE_MAX_W: 4 channels do)
+    wc = cap & ~15;
+    while (wc > 16 && wide_lds_bytes(wc, W, gather) > kWideLdsBudget) wc -= 16;
+    if (wc < 16) wc = cap < 16 ? cap : 16;
+    while (wide_lds_bytes(wc, W, gather) > kWideLdsMax) wc -= 4;
+  }
+  if (lds_bytes) *lds_bytes = wide_lds_bytes(wc, W, gather);
+  return wc;
+}
+
+int lla_quantise_encode_wide(const void *z, int z_dtype, int B, int C, const float *bias, const float *exp_scale,
+                             const float *median, const int32_t *cdf, int W, const int32_t *cdf_len,
+                             const int32_t *offset, uint8_t *scratch, size_t stride, uint32_t *lengths,
+                             int32_t *symbols_out, int window_channels, void *stream) {
+  if (z_dtype != LLA_Z_SYMBOLS && z_dtype != LLA_Z_F16 && z_dtype != LLA_Z_F32) return LLA_EINVAL;
+  size_t lds = 0;
+  const int wc = lla_rans_wide_window(C, W, LLA_CODER_ENCODE, window_channels, &lds);
+  if (wc < 0 || B < 0) return LLA_EINVAL;
+  if (B == 0) return LLA_OK;
+  if (!z || !cdf || !cdf_len || !offset || !scratch || !lengths) return LLA_EINVAL;
+  if (z_dtype != LLA_Z_SYMBOLS && (!bias || !exp_scale || !median)) return LLA_EINVAL;
+  if (stride < lla_rans_max_encoded_bytes(C) || (stride & 3u)) return LLA_ECAP;
+  const int grid = (B + kEncThreads - 1) / kEncThreads;
+  auto launch = [&](auto zt) {
+    rans_encode_wide_kernel<decltype(zt)::mode><<<grid, kEncThreads, lds, as_stream(stream)>>>(
+        z, B, C, bias, exp_scale, median, cdf, W, cdf_len, offset, scratch, stride, lengths, symbols_out, wc);
+  };
+  if (z_dtype == LLA_Z_SYMBOLS) launch(Fetch<0>{});
+  else with_z(z_dtype, launch);
+  return check_launch();
+}
+
+int lla_rans_decode_batch_wide(const uint8_t *payload, const uint64_t *off, int record_prefix, int off_first,
+                               int off_step, int B, int C, const int32_t *cdf, int W, const int32_t *cdf_len,
+                               const int32_t *offset, int32_t *symbols_out, int32_t *status, int window_channels,
+                               void *stream) {
+  size_t lds = 0;
+  const int wc = lla_rans_wide_window(C, W, LLA_CODER_DECODE, window_channels, &lds);
+  if (wc < 0 || B < 0 || off_first < 0 || off_step < 1) return LLA_EINVAL;
+  if (B == 0) return LLA_OK;
+  if (!payload || !off || !symbols_out || !cdf || !cdf_len || !offset) return LLA_EINVAL;
+  const int grid = (B + kEncThreads - 1) / kEncThreads;
+  rans_decode_wide_kernel<<<grid, kEncThreads, lds, as_stream(stream)>>>(
+      payload, off + off_first, record_prefix ? 4 : 0, off_step, B, C, cdf, W, cdf_len, offset, symbols_out, status, wc);
+  return check_launch();
+}
+
+int lla_rans_decode_gather_wide(const uint8_t *payload, const uint64_t *off, int record_prefix, int off_first,
+                                int off_step, int N, const int64_t *index, int B, int C, const int32_t *cdf, int W,
+                                const int32_t *cdf_len, const int32_t *offset, const float *bias,
+                                const float *exp_scale, const float *median, void *z_hat, int z_dtype, size_t ld_out,
+                                int32_t *status, int window_channels, void *stream) {
+  if (z_dtype != LLA_Z_F16 && z_dtype != LLA_Z_F32) return LLA_EINVAL;
+  size_t lds = 0;
+  const int wc = lla_rans_wide_window(C, W, LLA_CODER_GATHER, window_channels, &lds);
+  if (wc < 0 || B < 0 || off_first < 0 || off_step < 1) return LLA_EINVAL;
+  if (B == 0) return LLA_OK;
+  if (!payload || !off || !index || !bias || !exp_scale || !median || !z_hat || !status || N < 0 || !cdf || !cdf_len ||
+      !offset || ld_out < (size_t)C)
+    return LLA_EINVAL;
+  const int grid = (B + kEncThreads - 1) / kEncThreads;
+  const int skip = record_prefix ? 4 : 0;
+  with_z(z_dtype, [&](auto zt) {
+    using OutT = typename decltype(zt)::elem;
+    rans_decode_gather_wide_kernel<OutT><<<grid, kEncThreads, lds, as_stream(stream)>>>(
+        payload, off, skip, off_first, off_step, N, index, B, C, cdf, W, cdf_len, offset, bias, exp_scale, median,
+        reinterpret_cast<OutT *>(z_hat), ld_out, status, wc);
+  });
+  return check_launch();
 }
 
 int lla_rans_encode_indexed(const int32_t *symbols, const int32_t *indexes, int B, int n,

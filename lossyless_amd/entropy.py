@@ -8,7 +8,8 @@ buffer names so the reference's state-dicts load unchanged.
 
 Where the reference loops over images in Python and calls the C++ coder once per image
 (re-marshalling the whole CDF table each time), this class hands the whole batch to
-``lla_quantise_encode`` / ``lla_rans_decode_batch``: one image per GPU lane.
+``lla_quantise_encode`` / ``lla_rans_decode_batch``: one image per GPU lane.  A table too wide to stay resident in
+LDS (``resident_takes``) goes to their windowed twins, ``lla_quantise_encode_wide`` / ``lla_rans_decode_batch_wide``.
 """
 import ctypes
 
@@ -47,6 +48,14 @@ def _require_coder(model):
     if getattr(model, "entropy_coder", None) is None:
         raise RuntimeError("no entropy coder attached (make_pickable_() was called): call undo_pickable_() / "
                            "prepare_compressor_() first")
+
+
+def resident_takes(C, W, kind):
+    """THE place the Python coder chooses its kernels: True when the resident entry points of ``kind``
+    (``_lib.CODER_ENCODE`` / ``CODER_DECODE`` / ``CODER_GATHER``) take a table of ``C`` channels x ``W`` entries whole in
+    LDS (``lla_rans_table_fits``); otherwise the caller goes to the windowed ``*_wide`` entry point, which codes the same
+    bytes for any width.  The resident kernels stay the path wherever they are accepted (they are faster there)."""
+    return bool(_lib.lib().lla_rans_table_fits(int(C), int(W), int(kind)))
 
 
 def pmf_to_quantized_cdf(pmf, precision=16):
@@ -236,12 +245,13 @@ class EntropyBottleneck(nn.Module):
         lengths = torch.empty(max(B, 1), dtype=torch.int32, device=dev)
         symbols = torch.empty((B, C), dtype=torch.int32, device=dev) if want_symbols else None
         st = _lib.stream_ptr(dev)
-        rc = L.lla_quantise_encode(_lib.ptr(z), zt, B, C, _lib.ptr(tables["bias"]),
-                                   _lib.ptr(tables["exp_scale"]), _lib.ptr(tables["median"]),
-                                   _lib.ptr(tables["cdf"]), tables["W"], _lib.ptr(tables["cdf_len"]),
-                                   _lib.ptr(tables["offset"]), _lib.ptr(scratch), stride,
-                                   _lib.ptr(lengths), _lib.ptr(symbols), st)
-        _lib.check(rc, "lla_quantise_encode")
+        args = (_lib.ptr(z), zt, B, C, _lib.ptr(tables["bias"]), _lib.ptr(tables["exp_scale"]), _lib.ptr(tables["median"]),
+                _lib.ptr(tables["cdf"]), tables["W"], _lib.ptr(tables["cdf_len"]), _lib.ptr(tables["offset"]),
+                _lib.ptr(scratch), stride, _lib.ptr(lengths), _lib.ptr(symbols))
+        if resident_takes(C, tables["W"], _lib.CODER_ENCODE):
+            _lib.check(L.lla_quantise_encode(*args, st), "lla_quantise_encode")
+        else:       # a table too wide to stay in LDS: the windowed kernel, the library's choice of window
+            _lib.check(L.lla_quantise_encode_wide(*args, 0, st), "lla_quantise_encode_wide")
         payload, offsets = self.compact_device(scratch, stride, lengths, B, record_prefix)
         return payload, offsets, symbols
 
@@ -268,11 +278,14 @@ class EntropyBottleneck(nn.Module):
         dev = payload.device
         sym = torch.empty((B, C), dtype=torch.int32, device=dev)
         status = torch.zeros(max(B, 1), dtype=torch.int32, device=dev)
-        rc = L.lla_rans_decode_batch(_lib.ptr(payload), _lib.ptr(offsets), 1 if record_prefix else 0,
-                                     B, C, _lib.ptr(tables["cdf"]), tables["W"],
-                                     _lib.ptr(tables["cdf_len"]), _lib.ptr(tables["offset"]),
-                                     _lib.ptr(sym), _lib.ptr(status), _lib.stream_ptr(dev))
-        _lib.check(rc, "lla_rans_decode_batch")
+        head = (_lib.ptr(payload), _lib.ptr(offsets), 1 if record_prefix else 0)
+        tail = (B, C, _lib.ptr(tables["cdf"]), tables["W"], _lib.ptr(tables["cdf_len"]), _lib.ptr(tables["offset"]),
+                _lib.ptr(sym), _lib.ptr(status))
+        if resident_takes(C, tables["W"], _lib.CODER_DECODE):
+            _lib.check(L.lla_rans_decode_batch(*head, *tail, _lib.stream_ptr(dev)), "lla_rans_decode_batch")
+        else:
+            _lib.check(L.lla_rans_decode_batch_wide(*head, 0, 1, *tail, 0, _lib.stream_ptr(dev)),
+                       "lla_rans_decode_batch_wide")
         return sym, status
 
     # ------------------------------------------------- compressai-shaped API

@@ -18,6 +18,7 @@ import numpy as np
 import torch
 
 from . import _lib
+from .entropy import resident_takes
 
 _DTYPES = {torch.float32: _lib.LLA_Z_F32, torch.float16: _lib.LLA_Z_F16}
 
@@ -85,7 +86,7 @@ class _Latents:
 
     def take(self, indices, dtype=torch.float32, out=None, check=True):
         """Rows ``indices`` (list, numpy array or integer tensor on any device; repeats allowed) ->
-        ``[len(indices), 512]`` of ``dtype`` (float32 or float16) on ``self.device``, written into ``out`` if given.
+        ``[len(indices), z_dim]`` of ``dtype`` (float32 or float16) on ``self.device``, written into ``out`` if given.
 
         ``check=True`` reads the per-row status back (one synchronisation): ``IndexError`` for an index outside
         ``[0, N)`` -- negative indices do not wrap around -- and ``ValueError`` for a malformed stream.  With
@@ -134,11 +135,11 @@ class _Latents:
 
     def batches(self, batch_size, shuffle=False, generator=None, drop_last=False, dtype=torch.float32,
                 decode_group=65536):
-        """Iterate over the dataset in minibatches: yields ``z`` (``[batch_size, 512]``, the last one shorter unless
+        """Iterate over the dataset in minibatches: yields ``z`` (``[batch_size, z_dim]``, the last one shorter unless
         ``drop_last``), or ``(z, y)`` when the object holds labels.
 
         ``decode_group`` indices are decoded per launch and the minibatches are VIEWS of that buffer (valid until the
-        next group is decoded): one lane decodes one record, a serial chain of 512 symbols, so a launch of a few
+        next group is decoded): one lane decodes one record, a serial chain of ``z_dim`` symbols, so a launch of a few
         hundred records is bound by that chain's latency and leaves most of the chip idle, while 65536 records fill
         it.  The launch is therefore amortised over many minibatches; ``decode_group`` is rounded down to a multiple
         of ``batch_size`` (at least one batch).  The batches do not depend on it.
@@ -171,7 +172,10 @@ class CompressedLatents(_Latents):
     """``CompressedLatents(file, compressor, label_file=None, device=None)``
 
     file         a container written by ``compress_dataset`` (one record per image).
-    compressor   the :class:`~lossyless_amd.compressor.ClipCompressor` whose tables coded it.
+    compressor   the :class:`~lossyless_amd.compressor.ClipCompressor` or
+                 :class:`~lossyless_amd.feature_compressor.FeatureCompressor` whose tables coded it; the rows have its
+                 ``z_dim`` columns.  Tables too wide for the resident gather kernel are decoded by the windowed one
+                 (``lla_rans_decode_gather_wide``), same values.
     label_file   optional ``.npy`` of N labels, kept as an int64 tensor on ``device``.
     device       where the compressed bytes live and the rows are produced; default: the compressor's device.
                  ``"cpu"`` keeps numpy arrays and decodes with the library's host coder (no GPU needed).
@@ -206,13 +210,16 @@ class CompressedLatents(_Latents):
                 _np_ptr(t["median"]), _lib.ptr(out), _DTYPES[dtype], ld, _lib.ptr(status))
             _lib.check(rc, "lla_rans_decode_gather_host")
         else:
+            head = (_lib.ptr(self._body), _lib.ptr(self._off), 1)
+            tail = (self._n, _lib.ptr(idx), B, C, _lib.ptr(t["cdf"]), self._W, _lib.ptr(t["cdf_len"]), _lib.ptr(t["offset"]),
+                    _lib.ptr(t["bias"]), _lib.ptr(t["exp_scale"]), _lib.ptr(t["median"]), _lib.ptr(out), _DTYPES[dtype], ld,
+                    _lib.ptr(status))
             with torch.cuda.device(self.device):
-                rc = L.lla_rans_decode_gather(
-                    _lib.ptr(self._body), _lib.ptr(self._off), 1, self._n, _lib.ptr(idx), B, C, _lib.ptr(t["cdf"]),
-                    self._W, _lib.ptr(t["cdf_len"]), _lib.ptr(t["offset"]), _lib.ptr(t["bias"]),
-                    _lib.ptr(t["exp_scale"]), _lib.ptr(t["median"]), _lib.ptr(out), _DTYPES[dtype], ld,
-                    _lib.ptr(status), _lib.stream_ptr(self.device))
-            _lib.check(rc, "lla_rans_decode_gather")
+                if resident_takes(C, self._W, _lib.CODER_GATHER):
+                    _lib.check(L.lla_rans_decode_gather(*head, *tail, _lib.stream_ptr(self.device)), "lla_rans_decode_gather")
+                else:       # a table too wide to stay in LDS: the windowed kernel, same rows and statuses
+                    _lib.check(L.lla_rans_decode_gather_wide(*head, 0, 1, *tail, 0, _lib.stream_ptr(self.device)),
+                               "lla_rans_decode_gather_wide")
         return status
 
 
