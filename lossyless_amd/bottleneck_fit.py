@@ -9,7 +9,7 @@ This module is that loop for a matrix of features: a step is ``lla_eb_train_pass
 minibatch: csrc/eb_train.hip), ``lla_eb_aux_grad`` and two ``lla_adamw_step`` calls.  include/lossyless_amd.h states the
 mathematics.
 
-CPU data runs the float64 twin below instead, as every probe of this package does: the same formulas written out by hand in
+CPU data runs the float64 twin below instead, as every estimator of this package does: the same formulas written out by hand in
 torch (NO autograd: the backward is the kernel's, line for line), the same noise, the same step order.  The tests hold the
 twin to torch autograd and the kernels to the twin.
 
@@ -22,7 +22,7 @@ import numpy as np
 import torch
 
 from . import _lib
-from .probe import _Adam, _adamw, _adamw_step, lr_schedule, philox4x32_10
+from ._train import _Adam, _adamw, _adamw_step, lr_schedule, philox4x32_10
 from .rates import BASE_LOG, HRateFactorizedPrior
 
 FILTERS = (3, 3, 3, 3)

@@ -29,9 +29,9 @@ import numpy as np
 import torch
 
 from . import _lib
+from ._train import _adamw, _adamw_step, _mlp_backward, _mlp_forward
 from .bottleneck_fit import (FILTERS, LIK_BOUND, N_NET, NOISE_TAG, BottleneckFit, _Engine, hyperprior_noise, pack_network, twin_aux,
                              twin_likelihood, unpack_network_)
-from .probe import _adamw, _adamw_step, _mlp_backward, _mlp_forward
 from .rates import BASE_LOG, HRateHyperprior
 
 SIDE_TAG = 0x73696465                   # fourth counter word of the side information's noise (``hyperprior_noise(..., tag)``)
@@ -144,7 +144,7 @@ class _DeviceEngine(_Engine):
     buffer -- scaling [C], biasing [C], the network [58][S], then per Linear layer the weight [out_p][in_p] and the bias [out_p],
     every piece starting on a multiple of 4 elements and every layer width padded to a multiple of 8 as ``_DeviceMLP`` pads
     (zero weights and zero biases, whose gradients are zero: AdamW leaves them zero) -- so one ``lla_adamw_step`` updates
-    everything.  ``_forward`` and ``_backward`` stay apart from ``probe._DeviceMLP`` on purpose: EVERY width is padded here
+    everything.  ``_forward`` and ``_backward`` stay apart from that ``_DeviceMLP`` on purpose: EVERY width is padded here
     and only the class width there, and the batchnorm blocks and the cross-entropy slot exist only there; one class for both
     would be switches for all of that."""
 

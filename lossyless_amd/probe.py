@@ -1,4 +1,15 @@
-"""``LinearProbe`` -- the downstream linear classifier, trained from the compressed copy on the device.
+"""The probes: downstream estimators trained and scored where the compressed copy lives.  In file order:
+
+    shared      ``_Rows`` (the walk), ``_check_width`` / ``_z_args`` (what a device pass asks of a group of rows)
+    hinge       ``_Problems``, ``_HostSums``, ``_DeviceNewtonSums`` (the base of the three device sums classes), ``_DeviceSums``,
+                ``_newton_cg``, ``_affine_scores`` (the one ``lla_gemm_f32`` call site) and ``_Scores``, ``LinearProbe``,
+                ``LinearProbeCV``
+    softmax     the four softmax sums classes, ``_newton_cg_joint`` / ``_newton_cg_joint_groups``, ``LogisticProbe``,
+                ``LogisticProbeCV``
+    MLP         the float64 twins, ``_DeviceMLP``, ``MLPProbe``, ``BatchNormMLPProbe`` (optimiser and network primitives: _train.py)
+    k-NN, k-means, ridge, zero-shot     ``KNNProbe``; ``KMeansProbe``; ``RidgeProbe`` / ``RidgeProbeCV``; ``ZeroShotProbe``
+
+``LinearProbe`` is the downstream linear classifier, trained from the compressed copy on the device.
 
 The reference's published workflow ends with ``LinearSVC(C=7e-3).fit(Z, Y)`` on the decompressed features (README.md:74-82
 of the reference, notebooks/Hub.ipynb:415): scikit-learn's single-threaded liblinear over a host float32 array, which its
@@ -40,6 +51,8 @@ import numpy as np
 import torch
 
 from . import _lib
+from ._train import (_Adam, _adamw, _adamw_step, _dropout_scale, _mlp_backward, _mlp_forward, _mlp_init,  # noqa: F401
+                     dropout_keep, lr_schedule, philox4x32_10)
 from .latents import _Latents
 
 _CG_TOL = 0.1            # inner solve: |H d + g|_2 <= 0.1 |g|_2 per class (liblinear's TRON uses the same fraction)
@@ -112,6 +125,18 @@ class _Rows:
         self.buf = self.kept = None
         if self.latents is not None:
             self.latents.release()
+
+
+def _check_width(C, who):
+    """The feature widths the row-tile kernels (csrc/row_tile.h) are built for; ``who`` names the estimator in the message."""
+    if C % 8 or not 8 <= C <= 1024:
+        raise ValueError(f"the device {who} needs a feature width that is a multiple of 8 in [8, 1024], got {C}")
+
+
+def _z_args(z, C):
+    """A group's rows z [g, C] (fp32 or fp16, unit column stride) as a device pass takes them: (pointer, ``LLA_Z_*`` code,
+    pitch in elements -- C for a single row, whose stride says nothing)."""
+    return _lib.ptr(z), _lib.LLA_Z_F16 if z.dtype == torch.float16 else _lib.LLA_Z_F32, int(z.stride(0)) if z.shape[0] > 1 else C
 
 
 class _Problems:
@@ -231,60 +256,79 @@ class _HostSums:
         return self.scale[:, None] * hW, self.scale * hb
 
 
-class _DeviceSums:
-    """The same two quantities from ``lla_svm_grid_pass``, one call per decode group, accumulated on the device."""
+class _DeviceNewtonSums:
+    """The device side of a sums object of the Newton-CG solvers: the width check, the workspace, the walk of the decode
+    groups under the device guard and the count of passes.  A subclass sets up its constant arguments, calls
+    ``_workspace``, and gives ``_pass(W, b, V, vb, st)`` -> (loss or None, dW, db): zero-initialised accumulators, one
+    library call (``accumulate=1``) per group of ``_groups()``, the scaling afterwards."""
     dtype = torch.float32
     slack = 1e-6          # Armijo slack, relative to f: the fp32 loss sums of two passes differ by rounding at this level
 
-    def __init__(self, rows, y, prob, fold=None):
-        C, dev = rows.dim, rows.device
-        if C % 8 or not 8 <= C <= 1024:
-            raise ValueError(f"the device probe needs a feature width that is a multiple of 8 in [8, 1024], got {C}")
-        self.rows, self.C, self.device = rows, C, dev
-        prob.on(self, dev)
-        self.y = y.to(torch.int32).to(dev).contiguous()
-        self.fold = None if fold is None else fold.to(torch.int32).to(dev).contiguous()
-        self.cols = [prob.cls.to(dev), prob.held.to(dev), prob.wpos.to(torch.float32).to(dev),
-                     prob.wneg.to(torch.float32).to(dev)]
-        self.scale32 = self.scale.to(torch.float32)
+    def __init__(self, rows):
+        _check_width(rows.dim, "probe")
+        self.rows, self.dim, self.device = rows, rows.dim, rows.device
         self.L = _lib.lib()
-        nbytes = int(self.L.lla_svm_grid_pass_workspace_bytes(C, self.J))
-        if nbytes == 0:
-            raise ValueError(f"lla_svm_grid_pass refuses C = {C}, J = {self.J}")
-        self.ws = torch.empty(nbytes, dtype=torch.uint8, device=dev)
         self.n_passes = 0
 
-    def _pass(self, W, b, V, vb):
-        J, C = self.J, self.C
-        oW = torch.zeros((J, C), dtype=torch.float32, device=self.device)
-        ob = torch.zeros(J, dtype=torch.float32, device=self.device)
-        loss = torch.zeros(J, dtype=torch.float64, device=self.device) if V is None else None
-        cols = [_lib.ptr(t) for t in self.cols]
+    def _workspace(self, nbytes, refused):
+        """The pass's workspace; a size of 0 is the library refusing the shape (``refused``: the message)."""
+        if int(nbytes) == 0:
+            raise ValueError(refused)
+        self.ws = torch.empty(int(nbytes), dtype=torch.uint8, device=self.device)
+
+    def _groups(self):
+        """-> (first row, n, then the rows [n, C] as ``_z_args`` gives them) of every decode group."""
+        for g0, z in self.rows.groups():
+            yield (g0, int(z.shape[0])) + _z_args(z, self.dim)
+
+    def _run(self, W, b, V, vb):
         with torch.cuda.device(self.device):
-            st = _lib.stream_ptr(self.device)
-            for g0, z in self.rows.groups():
-                g = int(z.shape[0])
-                zt = _lib.LLA_Z_F16 if z.dtype == torch.float16 else _lib.LLA_Z_F32
-                fold = None if self.fold is None else self.fold[g0:g0 + g]
-                rc = self.L.lla_svm_grid_pass(_lib.ptr(z), zt, int(z.stride(0)) if g > 1 else C, _lib.ptr(self.y[g0:g0 + g]),
-                                              _lib.ptr(fold), g, C, _lib.ptr(W), _lib.ptr(b), _lib.ptr(V), _lib.ptr(vb), J, C,
-                                              *cols, _lib.ptr(oW), _lib.ptr(ob), _lib.ptr(loss), 1, _lib.ptr(self.ws), st)
-                _lib.check(rc, "lla_svm_grid_pass")
+            out = self._pass(W, b, V, vb, _lib.stream_ptr(self.device))
         self.n_passes += 1
-        return (None if loss is None else self.scale * loss), self.scale32[:, None] * oW, self.scale32 * ob
+        return out
 
     def column_squares(self):
-        sq = torch.zeros(self.C, dtype=torch.float64, device=self.device)
+        sq = torch.zeros(self.dim, dtype=torch.float64, device=self.device)
         for _, z in self.rows.groups():
             sq += (z.float() ** 2).sum(0, dtype=torch.float64)
         self.n_passes += 1
         return sq
 
     def gradient(self, W, b):
-        return self._pass(W.contiguous(), b.contiguous(), None, None)
+        return self._run(W.contiguous(), b.contiguous(), None, None)
 
     def hessian_vector(self, W, b, V, vb):
-        return self._pass(W.contiguous(), b.contiguous(), V.contiguous(), vb.contiguous())[1:]
+        return self._run(W.contiguous(), b.contiguous(), V.contiguous(), vb.contiguous())[1:]
+
+
+class _DeviceSums(_DeviceNewtonSums):
+    """The same two quantities from ``lla_svm_grid_pass``, one call per decode group, accumulated on the device."""
+
+    def __init__(self, rows, y, prob, fold=None):
+        super().__init__(rows)
+        dev = self.device
+        prob.on(self, dev)
+        self.y = y.to(torch.int32).to(dev).contiguous()
+        self.fold = None if fold is None else fold.to(torch.int32).to(dev).contiguous()
+        self.cols = [prob.cls.to(dev), prob.held.to(dev), prob.wpos.to(torch.float32).to(dev),
+                     prob.wneg.to(torch.float32).to(dev)]
+        self.scale32 = self.scale.to(torch.float32)
+        self._workspace(self.L.lla_svm_grid_pass_workspace_bytes(self.dim, self.J),
+                        f"lla_svm_grid_pass refuses C = {self.dim}, J = {self.J}")
+
+    def _pass(self, W, b, V, vb, st):
+        J, C = self.J, self.dim
+        oW = torch.zeros((J, C), dtype=torch.float32, device=self.device)
+        ob = torch.zeros(J, dtype=torch.float32, device=self.device)
+        loss = torch.zeros(J, dtype=torch.float64, device=self.device) if V is None else None
+        cols = [_lib.ptr(t) for t in self.cols]
+        for g0, g, zp, zt, ld in self._groups():
+            fold = None if self.fold is None else self.fold[g0:g0 + g]
+            rc = self.L.lla_svm_grid_pass(zp, zt, ld, _lib.ptr(self.y[g0:g0 + g]),
+                                          _lib.ptr(fold), g, C, _lib.ptr(W), _lib.ptr(b), _lib.ptr(V), _lib.ptr(vb), J, C,
+                                          *cols, _lib.ptr(oW), _lib.ptr(ob), _lib.ptr(loss), 1, _lib.ptr(self.ws), st)
+            _lib.check(rc, "lla_svm_grid_pass")
+        return (None if loss is None else self.scale * loss), self.scale32[:, None] * oW, self.scale32 * ob
 
 
 def _newton_cg(sums, dim, n_rows, device, tol, max_iter):
@@ -374,6 +418,59 @@ def _labels_of(data, labels, n):
     return y.to(torch.int64)
 
 
+_SCORE_ELEMS = 1 << 25    # fp32 scores a scoring walk of a search holds at a time: larger groups are scored in pieces
+
+
+def _f32_rows(z, C):
+    """fp32 rows as the GEMMs want them: unit column stride, a pitch that is a multiple of 4, 16-byte aligned -> (z, pitch)."""
+    if z.dtype != torch.float32:
+        z = z.float()
+    if z.stride(1) != 1 or (z.shape[0] > 1 and (z.stride(0) % 4 or z.stride(0) < C)) or z.data_ptr() % 16:
+        z = z.contiguous()
+    return z, (int(z.stride(0)) if z.shape[0] > 1 else C)
+
+
+def _gemm_f32(x, ld, W, b, out, ldo, n, o, i, relu, st):
+    """out [n, o] of pitch ldo = x [n, i] of pitch ld times W^T [o, i], plus b (None: no bias), through ReLU if ``relu``."""
+    rc = _lib.lib().lla_gemm_f32(_lib.ptr(x), ld, _lib.ptr(W), i, _lib.ptr(b), _lib.ptr(out), ldo, n, o, i, relu, st)
+    _lib.check(rc, "lla_gemm_f32")
+
+
+def _pack_affine(W, b, dev):
+    """Padded device copies of [K, C] weights and [K] biases for ``_affine_scores`` (as ``MLP._pack``) -> (fp32 [Npad8, C],
+    fp32 [Npad8], Npad8): zero rows up to the next multiple of 8.  Leading dimensions (one set of weights per fold) stay."""
+    K, C = W.shape[-2:]
+    if C % 8:
+        raise ValueError("the device path needs a feature width that is a multiple of 8")
+    npad = -(-K // 8) * 8
+    w = torch.zeros(W.shape[:-2] + (npad, C), dtype=torch.float32, device=dev)
+    w[..., :K, :] = W.to(dev)
+    bp = torch.zeros(b.shape[:-1] + (npad,), dtype=torch.float32, device=dev)
+    bp[..., :K] = b.to(dev)
+    return w, bp, npad
+
+
+def _piece_rows(npad, group):
+    """Rows of a decode group of ``group`` rows scored at a time against ``npad`` columns (``_SCORE_ELEMS``)."""
+    return max(min(_SCORE_ELEMS // npad, group), 1)
+
+
+def _affine_scores(z, w, b, out, piece=None, each=None):
+    """The scores of a group's rows z [g, C] against packed weights (``_pack_affine``), on the current device and stream.
+    Without ``piece``: one launch into out [g, Npad8].  With it: ``piece`` rows at a time into the reused out[:n], and
+    ``each(first row of the piece, out[:n])`` after every launch.  -> the rows as they were scored (``_f32_rows``)."""
+    npad, C = w.shape
+    z, ld = _f32_rows(z, C)
+    g, st = int(z.shape[0]), _lib.stream_ptr(z.device)
+    piece = piece or max(g, 1)
+    for r0 in range(0, g, piece):
+        n = min(piece, g - r0)
+        _gemm_f32(z[r0:r0 + n], ld if n > 1 else C, w, b, out, npad, n, npad, C, 0, st)
+        if each is not None:
+            each(r0, out[:n])
+    return z
+
+
 class _Scores:
     """Scoring shared by the probes: ``coef_`` [K, C] and ``intercept_`` [K] against the rows of a fit / predict call."""
 
@@ -391,15 +488,9 @@ class _Scores:
         self._packed = None
 
     def _pack(self, dev):
-        """Padded device copies of the weights for ``lla_gemm_f32`` (as ``MLP._pack``): fp32 [Npad8][C], bias [Npad8]."""
+        """``_pack_affine`` of the fitted weights, kept per device."""
         if self._packed is None or self._packed[0] != str(dev):
-            K, C = self.coef_.shape
-            npad = -(-K // 8) * 8
-            w = torch.zeros((npad, C), dtype=torch.float32, device=dev)
-            w[:K] = self.coef_.to(dev)
-            b = torch.zeros(npad, dtype=torch.float32, device=dev)
-            b[:K] = self.intercept_.to(dev)
-            self._packed = (str(dev), w, b, npad)
+            self._packed = (str(dev),) + _pack_affine(self.coef_, self.intercept_, dev)
         return self._packed[1:]
 
     def _scores(self, data, rows_per_pass):
@@ -413,21 +504,11 @@ class _Scores:
             raise ValueError(f"data has {rows.dim} features, the probe was fitted on {C}")
         try:
             if rows.device.type == "cuda":
-                if C % 8:
-                    raise ValueError("the device path needs a feature width that is a multiple of 8")
                 w, b, npad = self._pack(rows.device)
                 out = torch.empty((rows.n, npad), dtype=torch.float32, device=rows.device)
-                L = _lib.lib()
                 with torch.cuda.device(rows.device):
                     for g0, z in rows.groups():
-                        z = z if z.dtype == torch.float32 else z.float()
-                        z = z if z.stride(1) == 1 and z.stride(0) % 4 == 0 else z.contiguous()
-                        z = self._rows_in(z)
-                        g = int(z.shape[0])
-                        o = out[g0:g0 + g]
-                        rc = L.lla_gemm_f32(_lib.ptr(z), int(z.stride(0)) if g > 1 else C, _lib.ptr(w), C, _lib.ptr(b),
-                                            _lib.ptr(o), npad, g, npad, C, 0, _lib.stream_ptr(rows.device))
-                        _lib.check(rc, "lla_gemm_f32")
+                        _affine_scores(self._rows_in(z), w, b, out[g0:g0 + int(z.shape[0])])
                 s = out[:, :K]
             else:
                 W, b = self.coef_.to(torch.float64).cpu(), self.intercept_.to(torch.float64).cpu()
@@ -657,25 +738,12 @@ class LinearProbeCV:
             right.add_(hit.sum(0))
 
         if dev.type == "cuda":
-            if C % 8:
-                raise ValueError("the device path needs a feature width that is a multiple of 8")
-            npad = -(-J // 8) * 8
-            w, bp = torch.zeros((npad, C), dtype=torch.float32, device=dev), torch.zeros(npad, dtype=torch.float32, device=dev)
-            w[:J], bp[:J] = W, b
-            piece = max(min((1 << 25) // npad, rows.group), 1)
+            w, bp, npad = _pack_affine(W, b, dev)
+            piece = _piece_rows(npad, rows.group)
             out = torch.empty((min(piece, max(rows.n, 1)), npad), dtype=torch.float32, device=dev)
-            L = _lib.lib()
             with torch.cuda.device(dev):
                 for g0, z in rows.groups():
-                    z = z if z.dtype == torch.float32 else z.float()
-                    z = z if z.stride(1) == 1 and z.stride(0) % 4 == 0 else z.contiguous()
-                    for r0 in range(0, int(z.shape[0]), piece):
-                        zz = z[r0:r0 + piece]
-                        n = int(zz.shape[0])
-                        rc = L.lla_gemm_f32(_lib.ptr(zz), int(zz.stride(0)) if n > 1 else C, _lib.ptr(w), C, _lib.ptr(bp),
-                                            _lib.ptr(out), npad, n, npad, C, 0, _lib.stream_ptr(dev))
-                        _lib.check(rc, "lla_gemm_f32")
-                        count(out[:n, :J], g0 + r0)
+                    _affine_scores(z, w, bp, out, piece, lambda r0, S: count(S[:, :J], g0 + r0))
         else:
             W64, b64 = W.to(torch.float64), b.to(torch.float64)
             for g0, z in rows.groups():
@@ -752,56 +820,31 @@ class _HostSoftmaxSums:
         return self.C * hW, self.C * hb
 
 
-class _DeviceSoftmaxSums:
+class _DeviceSoftmaxSums(_DeviceNewtonSums):
     """The same two quantities from ``lla_softmax_pass``, one call per decode group, accumulated on the device."""
-    dtype = torch.float32
-    slack = _DeviceSums.slack
 
     def __init__(self, rows, idx, cw, C):
-        dim, dev = rows.dim, rows.device
-        if dim % 8 or not 8 <= dim <= 1024:
-            raise ValueError(f"the device probe needs a feature width that is a multiple of 8 in [8, 1024], got {dim}")
-        self.rows, self.dim, self.device, self.C = rows, dim, dev, float(C)
+        super().__init__(rows)
+        dev = self.device
+        self.C = float(C)
         self.K = int(cw.numel())
         self.cmax = self.C * float(cw.max())
         self.y = idx.to(torch.int32).to(dev).contiguous()
         self.cw = None if bool((cw == 1).all()) else cw.to(torch.float32).to(dev)
-        self.L = _lib.lib()
-        nbytes = int(self.L.lla_softmax_pass_workspace_bytes(dim, self.K, min(rows.group, max(rows.n, 1))))
-        if nbytes == 0:
-            raise ValueError(f"lla_softmax_pass refuses C = {dim}, K = {self.K}")
-        self.ws = torch.empty(nbytes, dtype=torch.uint8, device=dev)
-        self.n_passes = 0
+        self._workspace(self.L.lla_softmax_pass_workspace_bytes(self.dim, self.K, min(rows.group, max(rows.n, 1))),
+                        f"lla_softmax_pass refuses C = {self.dim}, K = {self.K}")
 
-    def _pass(self, W, b, V, vb):
+    def _pass(self, W, b, V, vb, st):
         K, C = self.K, self.dim
         oW = torch.zeros((K, C), dtype=torch.float32, device=self.device)
         ob = torch.zeros(K, dtype=torch.float32, device=self.device)
         loss = torch.zeros(K, dtype=torch.float64, device=self.device) if V is None else None
-        with torch.cuda.device(self.device):
-            st = _lib.stream_ptr(self.device)
-            for g0, z in self.rows.groups():
-                g = int(z.shape[0])
-                zt = _lib.LLA_Z_F16 if z.dtype == torch.float16 else _lib.LLA_Z_F32
-                rc = self.L.lla_softmax_pass(_lib.ptr(z), zt, int(z.stride(0)) if g > 1 else C, _lib.ptr(self.y[g0:g0 + g]), g, C,
-                                             _lib.ptr(W), _lib.ptr(b), _lib.ptr(V), _lib.ptr(vb), K, C, _lib.ptr(self.cw),
-                                             _lib.ptr(oW), _lib.ptr(ob), _lib.ptr(loss), 1, _lib.ptr(self.ws), st)
-                _lib.check(rc, "lla_softmax_pass")
-        self.n_passes += 1
+        for g0, g, zp, zt, ld in self._groups():
+            rc = self.L.lla_softmax_pass(zp, zt, ld, _lib.ptr(self.y[g0:g0 + g]), g, C,
+                                         _lib.ptr(W), _lib.ptr(b), _lib.ptr(V), _lib.ptr(vb), K, C, _lib.ptr(self.cw),
+                                         _lib.ptr(oW), _lib.ptr(ob), _lib.ptr(loss), 1, _lib.ptr(self.ws), st)
+            _lib.check(rc, "lla_softmax_pass")
         return (None if loss is None else self.C * loss.sum()), self.C * oW, self.C * ob
-
-    def column_squares(self):
-        sq = torch.zeros(self.dim, dtype=torch.float64, device=self.device)
-        for _, z in self.rows.groups():
-            sq += (z.float() ** 2).sum(0, dtype=torch.float64)
-        self.n_passes += 1
-        return sq
-
-    def gradient(self, W, b):
-        return self._pass(W.contiguous(), b.contiguous(), None, None)
-
-    def hessian_vector(self, W, b, V, vb):
-        return self._pass(W.contiguous(), b.contiguous(), V.contiguous(), vb.contiguous())[1:]
 
 
 def _newton_cg_joint(sums, dim, n_rows, device, tol, max_iter):
@@ -981,74 +1024,52 @@ class _HostSoftmaxGridSums(_HostSoftmaxSums):
         return self.scale[:, None, None] * hW, self.scale[:, None] * hb
 
 
-class _DeviceSoftmaxGridSums:
+class _DeviceSoftmaxGridSums(_DeviceNewtonSums):
     """The same two quantities on the device, one decode per group of rows for all G classifiers.  K <= 32: one
     ``lla_softmax_grid_pass(accumulate=1)`` per decode group.  K > 32: ``lla_softmax_pass`` once per classifier on the same
     taken buffer, with that classifier's held-out rows relabelled -1 (an out-of-range label contributes exactly nothing)."""
-    dtype = torch.float32
-    slack = _DeviceSums.slack
 
     def __init__(self, rows, idx, fold, held, cw, scale):
-        dim, dev = rows.dim, rows.device
-        if dim % 8 or not 8 <= dim <= 1024:
-            raise ValueError(f"the device probe needs a feature width that is a multiple of 8 in [8, 1024], got {dim}")
-        self.rows, self.dim, self.device = rows, dim, dev
+        super().__init__(rows)
+        dim, dev = self.dim, self.device
         self.G, self.K = int(cw.shape[0]), int(cw.shape[1])
         self.scale = scale.to(torch.float64).to(dev)
         self.scale32 = self.scale.to(torch.float32)
         self.cmax = self.scale * cw.to(torch.float64).amax(1).to(dev)
         self.cw = None if bool((cw == 1).all()) else cw.to(torch.float32).to(dev).contiguous()
         self.fused = self.K <= 32
-        self.L = _lib.lib()
         y, fold, held = idx.to(torch.int32).to(dev), fold.to(torch.int32).to(dev), held.to(torch.int32).to(dev)
         if self.fused:
             self.y, self.fold, self.held = y.contiguous(), fold.contiguous(), held.contiguous()
-            nbytes = int(self.L.lla_softmax_grid_pass_workspace_bytes(dim, self.K, self.G))
+            nbytes = self.L.lla_softmax_grid_pass_workspace_bytes(dim, self.K, self.G)
         else:
             self.y, self.fold, self.held = y.contiguous(), fold.contiguous(), held.tolist()
-            nbytes = int(self.L.lla_softmax_pass_workspace_bytes(dim, self.K, min(rows.group, max(rows.n, 1))))
-        if nbytes == 0:
-            raise ValueError(f"the softmax passes refuse C = {dim}, K = {self.K}, G = {self.G}")
-        self.ws = torch.empty(nbytes, dtype=torch.uint8, device=dev)
-        self.n_passes = 0
+            nbytes = self.L.lla_softmax_pass_workspace_bytes(dim, self.K, min(rows.group, max(rows.n, 1)))
+        self._workspace(nbytes, f"the softmax passes refuse C = {dim}, K = {self.K}, G = {self.G}")
 
-    def _pass(self, W, b, V, vb):
+    def _pass(self, W, b, V, vb, st):
         G, K, C = self.G, self.K, self.dim
         oW = torch.zeros((G, K, C), dtype=torch.float32, device=self.device)
         ob = torch.zeros((G, K), dtype=torch.float32, device=self.device)
         loss = torch.zeros((G, K), dtype=torch.float64, device=self.device) if V is None else None
         at = (lambda t, g: None if t is None else t[g])
-        with torch.cuda.device(self.device):
-            st = _lib.stream_ptr(self.device)
-            for g0, z in self.rows.groups():
-                n = int(z.shape[0])
-                zt = _lib.LLA_Z_F16 if z.dtype == torch.float16 else _lib.LLA_Z_F32
-                ld = int(z.stride(0)) if n > 1 else C
-                if self.fused:
-                    rc = self.L.lla_softmax_grid_pass(_lib.ptr(z), zt, ld, _lib.ptr(self.y[g0:g0 + n]), _lib.ptr(self.fold[g0:g0 + n]),
-                                                      n, C, _lib.ptr(W), _lib.ptr(b), _lib.ptr(V), _lib.ptr(vb), K, G, C,
-                                                      _lib.ptr(self.held), _lib.ptr(self.cw), _lib.ptr(oW), _lib.ptr(ob),
-                                                      _lib.ptr(loss), 1, _lib.ptr(self.ws), st)
-                    _lib.check(rc, "lla_softmax_grid_pass")
-                    continue
-                yn, fn = self.y[g0:g0 + n], self.fold[g0:g0 + n]
-                for g in range(G):       # this classifier's labels of the decode group: -1 on the rows it holds out
-                    yg = torch.where(fn == self.held[g], -1, yn).to(torch.int32)
-                    rc = self.L.lla_softmax_pass(_lib.ptr(z), zt, ld, _lib.ptr(yg), n, C, _lib.ptr(W[g]),
-                                                 _lib.ptr(b[g]), _lib.ptr(at(V, g)), _lib.ptr(at(vb, g)), K, C,
-                                                 _lib.ptr(at(self.cw, g)), _lib.ptr(oW[g]), _lib.ptr(ob[g]), _lib.ptr(at(loss, g)),
-                                                 1, _lib.ptr(self.ws), st)
-                    _lib.check(rc, "lla_softmax_pass")
-        self.n_passes += 1
+        for g0, n, zp, zt, ld in self._groups():
+            if self.fused:
+                rc = self.L.lla_softmax_grid_pass(zp, zt, ld, _lib.ptr(self.y[g0:g0 + n]), _lib.ptr(self.fold[g0:g0 + n]),
+                                                  n, C, _lib.ptr(W), _lib.ptr(b), _lib.ptr(V), _lib.ptr(vb), K, G, C,
+                                                  _lib.ptr(self.held), _lib.ptr(self.cw), _lib.ptr(oW), _lib.ptr(ob),
+                                                  _lib.ptr(loss), 1, _lib.ptr(self.ws), st)
+                _lib.check(rc, "lla_softmax_grid_pass")
+                continue
+            yn, fn = self.y[g0:g0 + n], self.fold[g0:g0 + n]
+            for g in range(G):       # this classifier's labels of the decode group: -1 on the rows it holds out
+                yg = torch.where(fn == self.held[g], -1, yn).to(torch.int32)
+                rc = self.L.lla_softmax_pass(zp, zt, ld, _lib.ptr(yg), n, C, _lib.ptr(W[g]),
+                                             _lib.ptr(b[g]), _lib.ptr(at(V, g)), _lib.ptr(at(vb, g)), K, C,
+                                             _lib.ptr(at(self.cw, g)), _lib.ptr(oW[g]), _lib.ptr(ob[g]), _lib.ptr(at(loss, g)),
+                                             1, _lib.ptr(self.ws), st)
+                _lib.check(rc, "lla_softmax_pass")
         return (None if loss is None else self.scale * loss.sum(1)), self.scale32[:, None, None] * oW, self.scale32[:, None] * ob
-
-    column_squares = _DeviceSoftmaxSums.column_squares
-
-    def gradient(self, W, b):
-        return self._pass(W.contiguous(), b.contiguous(), None, None)
-
-    def hessian_vector(self, W, b, V, vb):
-        return self._pass(W.contiguous(), b.contiguous(), V.contiguous(), vb.contiguous())[1:]
 
 
 def _newton_cg_joint_groups(sums, dim, n_rows, device, tol, max_iter):
@@ -1231,69 +1252,6 @@ class LogisticProbeCV:
 
 
 # ---------------------------------------------------------------------- the reference's MLP predictor
-def _mlp_init(dims, generator):
-    """``weights_init`` of the reference (lossyless/helpers.py:153-178) for the Linear layers dims[l] -> dims[l + 1]:
-    ``kaiming_uniform_(nonlinearity="relu")`` -- U(-b, b), b = sqrt(2) sqrt(3 / fan_in) -- on every weight, drawn in fp32 on the
-    CPU from ``generator`` in layer order, and zero biases -> (weights, biases)."""
-    Ws, bs = [], []
-    for fan_in, fan_out in zip(dims[:-1], dims[1:]):
-        bound = (2.0 ** 0.5) * (3.0 / fan_in) ** 0.5
-        Ws.append(torch.empty((fan_out, fan_in), dtype=torch.float32).uniform_(-bound, bound, generator=generator))
-        bs.append(torch.zeros(fan_out, dtype=torch.float32))
-    return Ws, bs
-
-
-class _Adam:
-    """The hyper-parameters of a fit and the two bias corrections of step t, in double on the host (``lla_adamw_step``)."""
-
-    def __init__(self, lr, weight_decay, betas, eps):
-        self.lr, self.wd, self.b1, self.b2, self.eps = float(lr), float(weight_decay), float(betas[0]), float(betas[1]), float(eps)
-
-    def corrections(self, t):
-        return 1.0 - self.b1 ** t, 1.0 - self.b2 ** t
-
-
-def _adamw(params, grads, moments, a, t):
-    """``lla_adamw_step`` on the host: step ``t`` of AdamW with the hyper-parameters ``a`` on a list of tensors, in place;
-    ``moments`` holds (m, v) per parameter."""
-    bc1, bc2 = a.corrections(t)
-    for p, g, (m, v) in zip(params, grads, moments):
-        p.mul_(1.0 - a.lr * a.wd)
-        m.copy_(a.b1 * m + (1.0 - a.b1) * g)
-        v.copy_(a.b2 * v + (1.0 - a.b2) * g * g)
-        p.sub_((a.lr / bc1) * m / (v.sqrt() / bc2 ** 0.5 + a.eps))
-
-
-def _adamw_step(L, p, g, m, v, a, bc1, bc2, st):
-    """``lla_adamw_step`` on the device: AdamW with the hyper-parameters ``a`` and the bias corrections (bc1, bc2) on the whole
-    of the fp32 buffers p (parameters), g (gradients), m and v (moments), in place, on stream ``st``."""
-    rc = L.lla_adamw_step(_lib.ptr(p), _lib.ptr(g), _lib.ptr(m), _lib.ptr(v), p.numel(), a.lr, a.b1, a.b2, a.eps, a.wd, bc1, bc2, st)
-    _lib.check(rc, "lla_adamw_step")
-
-
-def _mlp_forward(Ws, bs, x, pre=None):
-    """-> (output, [x, h_1, ..., h_L]): h = relu(h W^T + b) (``lla_gemm_f32``, relu = 1), then the last Linear.  ``pre``, a
-    list, receives the hidden pre-activations."""
-    hs = [x]
-    for W, b in zip(Ws[:-1], bs[:-1]):
-        a = hs[-1] @ W.T + b
-        if pre is not None:
-            pre.append(a)
-        hs.append(torch.where(a > 0, a, torch.zeros((), dtype=a.dtype)))
-    return hs[-1] @ Ws[-1].T + bs[-1], hs
-
-
-def _mlp_backward(Ws, hs, delta, below=False):
-    """The output's gradient -> (dW per layer, db per layer, the input's gradient -- computed only with ``below``, else None):
-    ``lla_gemm_f32_tn``, and ``lla_gemm_f32_nn`` with the ReLU mask of the layer below."""
-    gW, gb = [None] * len(Ws), [None] * len(Ws)
-    for l in range(len(Ws) - 1, -1, -1):
-        gW[l], gb[l] = delta.T @ hs[l], delta.sum(0)
-        if l > 0:
-            delta = torch.where(hs[l] > 0, delta @ Ws[l], torch.zeros((), dtype=delta.dtype))
-    return gW, gb, delta @ Ws[0] if below else None
-
-
 class _Twin:
     """What the two float64 twins share: the AdamW update of ``_params()`` and the sums of an epoch.  With ``step(x, y)``
     and ``fitted(n_out)`` of its own a twin has the interface of the device engine (``_DeviceMLP``)."""
@@ -1354,15 +1312,6 @@ class _TwinMLP(_Twin):
     def fitted(self, n_out):
         """-> (weights, biases), copies."""
         return [W.clone() for W in self.Ws], [b.clone() for b in self.bs]
-
-
-def _f32_rows(z, C):
-    """fp32 rows as the GEMMs want them: unit column stride, a pitch that is a multiple of 4, 16-byte aligned -> (z, pitch)."""
-    if z.dtype != torch.float32:
-        z = z.float()
-    if z.stride(1) != 1 or (z.shape[0] > 1 and (z.stride(0) % 4 or z.stride(0) < C)) or z.data_ptr() % 16:
-        z = z.contiguous()
-    return z, (int(z.stride(0)) if z.shape[0] > 1 else C)
 
 
 class _DeviceMLP:
@@ -1429,9 +1378,8 @@ class _DeviceMLP:
         for l in range(last + 1):
             i, o = self.dims[l], self.dims[l + 1]
             block = self.bn and l < last
-            rc = self.L.lla_gemm_f32(_lib.ptr(x), ld, _lib.ptr(self.W[l]), i, _lib.ptr(self.b[l]),
-                                     _lib.ptr(self.pre[l] if block else self.acts[l]), o, n, o, i, int(l < last and not self.bn), st)
-            _lib.check(rc, "lla_gemm_f32")
+            _gemm_f32(x, ld, self.W[l], self.b[l], self.pre[l] if block else self.acts[l], o, n, o, i,
+                      int(l < last and not self.bn), st)
             if block:
                 self.bn_fwd(l, n, st)
             x, ld = self.acts[l], o
@@ -1708,71 +1656,6 @@ class MLPProbe(_MinibatchProbe):
 
 
 # ------------------------------------------------- the reference's predictor as configured: batchnorm, dropout, a schedule
-def philox4x32_10(counter, key):
-    """Philox4x32-10 (Salmon et al., SC'11) on the CPU: ``counter`` [..., 4] and ``key`` [..., 2] of 32-bit words (anything
-    numpy broadcasts) -> uint32 [..., 4].  The definition csrc/batchnorm.hip draws its dropout masks from."""
-    c = np.asarray(counter, dtype=np.uint64) & np.uint64(0xFFFFFFFF)
-    k = np.asarray(key, dtype=np.uint64) & np.uint64(0xFFFFFFFF)
-    shape = np.broadcast_shapes(c.shape[:-1], k.shape[:-1])
-    c0, c1, c2, c3 = (np.broadcast_to(c[..., i], shape).copy() for i in range(4))
-    k0, k1 = (np.broadcast_to(k[..., i], shape).copy() for i in range(2))
-    mask, sh = np.uint64(0xFFFFFFFF), np.uint64(32)
-    for _ in range(10):
-        p0, p1 = np.uint64(0xD2511F53) * c0, np.uint64(0xCD9E8D57) * c2          # 32 x 32 -> 64 bits: no overflow
-        c0, c1, c2, c3 = (p1 >> sh) ^ c1 ^ k0, p1 & mask, (p0 >> sh) ^ c3 ^ k1, p0 & mask
-        k0, k1 = (k0 + np.uint64(0x9E3779B9)) & mask, (k1 + np.uint64(0xBB67AE85)) & mask
-    return np.stack([c0, c1, c2, c3], -1).astype(np.uint32)
-
-
-def dropout_keep(seed, step, layer, rows, cols, p):
-    """The keep pattern of ``lla_bn_relu_dropout_fwd`` -> bool tensor [rows, cols] (``cols % 4 == 0``): the quad of columns
-    j .. j + 3 of row i takes the four words of Philox4x32-10 with key (seed_lo, seed_hi) and counter (e_lo, e_hi, step,
-    layer), e = (i cols + j) / 4; a word w gives u = (w >> 8) 2^-24 and the element is kept iff u >= float32(p)."""
-    if cols % 4:
-        raise ValueError("cols must be a multiple of 4")
-    seed = int(seed) & 0xFFFFFFFFFFFFFFFF
-    e = np.arange(rows * cols // 4, dtype=np.uint64)
-    counter = np.stack([e & np.uint64(0xFFFFFFFF), e >> np.uint64(32), np.full_like(e, int(step) & 0xFFFFFFFF),
-                        np.full_like(e, int(layer) & 0xFFFFFFFF)], -1)
-    words = philox4x32_10(counter, np.array([seed & 0xFFFFFFFF, seed >> 32], dtype=np.uint64))
-    u = (words >> np.uint32(8)).astype(np.float32) * np.float32(2.0 ** -24)
-    return torch.from_numpy((u >= np.float32(p)).reshape(rows, cols))
-
-
-def _dropout_scale(p):
-    """s = (float)(1 / (1 - (double)p)), as a Python float holding the fp32 value."""
-    return float(np.float32(1.0 / (1.0 - float(p))))
-
-
-def lr_schedule(scheduler, lr, epochs, decay_factor=100, k_steps=3):
-    """The learning rate of every epoch -> list of ``epochs`` doubles, as lossyless/helpers.py:536-545 builds the schedulers
-    and ``torch.optim.lr_scheduler`` steps them once per epoch (the chained form: each rate is the previous one times a
-    factor).  None: constant.  "unifmultistep": ``MultiStepLR`` with milestones ``(epochs // (k_steps + 1)) i``, i = 1 ..
-    k_steps, and ``gamma = (1 / decay_factor) ** (1 / k_steps)``.  "expdecay": ``ExponentialLR`` with
-    ``gamma = (1 / decay_factor) ** (1 / epochs)``."""
-    lr, epochs = float(lr), int(epochs)
-    if scheduler is None:
-        return [lr] * epochs
-    if scheduler == "unifmultistep":
-        delta = epochs // (k_steps + 1)
-        milestones = [delta * i for i in range(1, k_steps + 1)]
-        gamma = (1 / decay_factor) ** (1 / k_steps)
-        out = []
-        for e in range(epochs):
-            n = milestones.count(e)
-            lr = lr * gamma ** n if n else lr
-            out.append(lr)
-        return out
-    if scheduler == "expdecay":
-        gamma = (1 / decay_factor) ** (1 / epochs)
-        out = []
-        for e in range(epochs):
-            lr = lr * gamma if e else lr
-            out.append(lr)
-        return out
-    raise ValueError(f"scheduler={scheduler!r} is not built: None, 'unifmultistep' or 'expdecay'")
-
-
 def _fold_batchnorm(Ws, b_last, gammas, betas, rms, rvs, eps):
     """Evaluation-mode BatchNorm1d folded into the bias-free Linear below it, in float64 on the host:
     W' = diag(gamma / sqrt(rv + eps)) W,  b' = beta - gamma rm / sqrt(rv + eps)  -> (weights, biases) of a plain ReLU MLP."""
@@ -2057,8 +1940,7 @@ class KNNProbe:
             raise ValueError(f"the queries have {qrows.dim} features, the probe was fitted on {self._dim}")
         C, K = self._dim, 0 if self._y is None else len(self.classes_)
         if on_device:
-            if C % 8 or not 8 <= C <= 1024:
-                raise ValueError(f"the device k-NN needs a feature width that is a multiple of 8 in [8, 1024], got {C}")
+            _check_width(C, "k-NN")
             if k > 256:
                 raise ValueError(f"the device k-NN keeps lists of at most 256 neighbours, got k = {k}")
             if grid and (self._y_dev is None or self._y_dev.device != dev):
@@ -2103,9 +1985,7 @@ class KNNProbe:
             st = _lib.stream_ptr(dev)
             accumulate = 0
             for g0, z in train.groups():
-                g = int(z.shape[0])
-                zt = _lib.LLA_Z_F16 if z.dtype == torch.float16 else _lib.LLA_Z_F32
-                rc = L.lla_knn_pass(_lib.ptr(qn), C, B, _lib.ptr(z), zt, int(z.stride(0)) if g > 1 else C, g, C, g0, k, metric,
+                rc = L.lla_knn_pass(_lib.ptr(qn), C, B, *_z_args(z, C), int(z.shape[0]), C, g0, k, metric,
                                     _lib.ptr(own32), accumulate, _lib.ptr(ws), st)
                 _lib.check(rc, "lla_knn_pass")
                 accumulate = 1
@@ -2279,8 +2159,7 @@ class _DeviceKMeans:
     def __init__(self, rows, K, cosine):
         self.rows, self.K, self.cosine, self.n_passes = rows, int(K), bool(cosine), 0
         L, dev, C, N = _lib.lib(), rows.device, rows.dim, rows.n
-        if C % 8 or not 8 <= C <= 1024:
-            raise ValueError(f"the device k-means needs a feature width that is a multiple of 8 in [8, 1024], got {C}")
+        _check_width(C, "k-means")
         nbytes = int(L.lla_kmeans_pass_workspace_bytes(C, self.K))
         if nbytes == 0:
             raise ValueError(f"lla_kmeans_pass refuses C = {C}, K = {K}")
@@ -2303,10 +2182,9 @@ class _DeviceKMeans:
 
     def run(self, z, W, b, assign, dist, sums, accumulate):
         """One ``lla_kmeans_pass`` over the rows z [g, C] on the current stream."""
-        g, C, dev = int(z.shape[0]), int(W.shape[1]), W.device
-        zt = _lib.LLA_Z_F16 if z.dtype == torch.float16 else _lib.LLA_Z_F32
+        C, dev = int(W.shape[1]), W.device
         rc = _lib.lib().lla_kmeans_pass(
-            _lib.ptr(z), zt, int(z.stride(0)) if g > 1 else C, g, C, _lib.ptr(W), _lib.ptr(b), self.K, C,
+            *_z_args(z, C), int(z.shape[0]), C, _lib.ptr(W), _lib.ptr(b), self.K, C,
             1 if self.cosine else 0, _lib.ptr(assign), _lib.ptr(dist), _lib.ptr(self.sum if sums else None),
             _lib.ptr(self.count if sums else None), _lib.ptr(self.stats if sums else None), accumulate, _lib.ptr(self.ws),
             _lib.stream_ptr(dev))
@@ -2533,6 +2411,14 @@ class KMeansProbe:
         finally:
             rows.close()
 
+    def _pack(self, dev):
+        """``_pack_affine`` of the centres rounded to fp32, with b = -1/2 |c_k|^2 (cosine: 0), kept per device."""
+        if self._packed is None or self._packed[0] != str(dev):
+            W = self.cluster_centers_.to(dev).to(torch.float32)
+            b = torch.zeros_like(W[:, 0]) if self._cosine else (-0.5 * (W.to(torch.float64) ** 2).sum(1)).to(torch.float32)
+            self._packed = (str(dev),) + _pack_affine(W, b, dev)
+        return self._packed[1:]
+
     def transform(self, data, rows_per_pass=65536):
         """Distances to every centre, [N, K]: Euclidean (``sqrt(max(0, |z|^2 - 2 (z . c - 1/2 |c|^2)))``), or ``1 - cos``."""
         rows = self._rows_for(data, rows_per_pass)
@@ -2552,29 +2438,13 @@ class KMeansProbe:
                     else:
                         out.append(torch.sqrt((n2 - 2.0 * (z @ W.T + b)).clamp_min(0.0)))
                 return torch.cat(out) if out else torch.zeros((0, K), dtype=torch.float64)
-            if C % 8:
-                raise ValueError("the device path needs a feature width that is a multiple of 8")
             dev = rows.device
-            if self._packed is None or self._packed[0] != str(dev):
-                npad = -(-K // 8) * 8
-                w = torch.zeros((npad, C), dtype=torch.float32, device=dev)
-                w[:K] = self.cluster_centers_.to(dev)
-                b = torch.zeros(npad, dtype=torch.float32, device=dev)
-                if not cosine:
-                    b[:K] = (-0.5 * (w[:K].to(torch.float64) ** 2).sum(1)).to(torch.float32)
-                self._packed = (str(dev), w, b, npad)
-            _, w, b, npad = self._packed
+            w, b, npad = self._pack(dev)
             out = torch.empty((rows.n, npad), dtype=torch.float32, device=dev)
-            L = _lib.lib()
             with torch.cuda.device(dev):
                 for g0, z in rows.groups():
-                    z = z if z.dtype == torch.float32 else z.float()
-                    z = z if z.stride(1) == 1 and z.stride(0) % 4 == 0 else z.contiguous()
-                    g = int(z.shape[0])
-                    o = out[g0:g0 + g]
-                    rc = L.lla_gemm_f32(_lib.ptr(z), int(z.stride(0)) if g > 1 else C, _lib.ptr(w), C, _lib.ptr(b),
-                                        _lib.ptr(o), npad, g, npad, C, 0, _lib.stream_ptr(dev))
-                    _lib.check(rc, "lla_gemm_f32")
+                    o = out[g0:g0 + int(z.shape[0])]
+                    z = _affine_scores(z, w, b, o)
                     n2 = (z * z).sum(1, keepdim=True)
                     if cosine:
                         o.copy_(1.0 - o * torch.where(n2 > 0, 1.0 / torch.sqrt(n2), torch.zeros_like(n2)))
@@ -2683,8 +2553,7 @@ class _DeviceMoments:
 
     def __init__(self, rows, nb, n_cross, regress):
         C, dev = rows.dim, rows.device
-        if C % 8 or not 8 <= C <= 1024:
-            raise ValueError(f"the device ridge needs a feature width that is a multiple of 8 in [8, 1024], got {C}")
+        _check_width(C, "ridge")
         self.T = n_cross if regress else 0
         nbytes = int(_lib.lib().lla_gram_pass_workspace_bytes(C, self.T))
         if nbytes == 0:
@@ -2704,17 +2573,16 @@ class _DeviceMoments:
 
     def add(self, f, z, seg, t):
         L, C, r = _lib.lib(), self.C, int(z.shape[0])
-        zt = _lib.LLA_Z_F16 if z.dtype == torch.float16 else _lib.LLA_Z_F32
-        ld = int(z.stride(0)) if r > 1 else C
+        za = _z_args(z, C)
         st = _lib.stream_ptr(self.dev)
         with_t = seg is None
-        rc = L.lla_gram_pass(_lib.ptr(z), zt, ld, r, C, _lib.ptr(t) if with_t else None, self.T, self.T,
+        rc = L.lla_gram_pass(*za, r, C, _lib.ptr(t) if with_t else None, self.T, self.T,
                              _lib.ptr(self.gram[f]), _lib.ptr(self.sum[f]), _lib.ptr(self.cross[f]) if with_t else None,
                              _lib.ptr(self.tsum[f]) if with_t else None, _lib.ptr(self.tsq[f]) if with_t else None, 1,
                              _lib.ptr(self.ws), st)
         _lib.check(rc, "lla_gram_pass")
         if seg is not None:
-            rc = L.lla_segment_sums(_lib.ptr(z), zt, ld, r, C, ctypes.c_void_p(seg.data_ptr()), int(seg.numel()) - 1,
+            rc = L.lla_segment_sums(*za, r, C, ctypes.c_void_p(seg.data_ptr()), int(seg.numel()) - 1,
                                     _lib.ptr(self.cross[f]), 1, st)
             _lib.check(rc, "lla_segment_sums")
 
@@ -2943,9 +2811,6 @@ def _ridge_held_out_mse(held, W, b):
     return mse
 
 
-_SCORE_ELEMS = 1 << 25    # fp32 scores a scoring walk of RidgeProbeCV holds at a time: larger runs are scored in pieces
-
-
 class RidgeProbeCV:
     """``RidgeProbeCV(alphas, cv=5, fit_intercept=True)``: the K-fold search over ``alpha`` of a :class:`RidgeProbe` from
     the moments of ONE walk.  The moments add over rows, so the walk keeps them per fold, a fold's training moments are the
@@ -3024,26 +2889,15 @@ class RidgeProbeCV:
 
         if dev.type == "cuda":
             J = A * Kp
-            npad = -(-J // 8) * 8
-            w = torch.zeros((nf, npad, C), dtype=torch.float32, device=dev)
-            bp = torch.zeros((nf, npad), dtype=torch.float32, device=dev)
-            w[:, :J], bp[:, :J] = W.reshape(nf, J, C).to(dev), b.reshape(nf, J).to(dev)
-            piece = max(min(_SCORE_ELEMS // npad, rows.group), 1)
+            w, bp, npad = _pack_affine(W.reshape(nf, J, C), b.reshape(nf, J), dev)
+            piece = _piece_rows(npad, rows.group)
             out = torch.empty((min(piece, rows.n), npad), dtype=torch.float32, device=dev)
-            L = _lib.lib()
             with torch.cuda.device(dev):
                 for g0, z in rows.groups():
-                    z = z if z.dtype == torch.float32 else z.float()
+                    z = _f32_rows(z, C)[0]                 # (fp16 rows: widened once per group, not once per run)
                     for f, a0, a1, _ in walk.runs(g0, int(z.shape[0])):
-                        if f >= nf:
-                            continue
-                        for r0 in range(a0, a1, piece):
-                            zz = z[r0:min(r0 + piece, a1)]
-                            n = int(zz.shape[0])
-                            rc = L.lla_gemm_f32(_lib.ptr(zz), int(zz.stride(0)) if n > 1 else C, _lib.ptr(w[f]), C,
-                                                _lib.ptr(bp[f]), _lib.ptr(out), npad, n, npad, C, 0, _lib.stream_ptr(dev))
-                            _lib.check(rc, "lla_gemm_f32")
-                            count(out[:n, :J], f, g0 + r0)
+                        if f < nf:
+                            _affine_scores(z[a0:a1], w[f], bp[f], out, piece, lambda r0, S: count(S[:, :J], f, g0 + a0 + r0))
         else:
             for g0, z in rows.groups():
                 z = z.to(torch.float64)

@@ -28,7 +28,7 @@ import torch.nn.functional as F
 sys.path.insert(0, os.path.join(os.path.dirname(os.path.abspath(__file__)), ".."))
 from lossyless_amd import HyperpriorFit, _lib                                      # noqa: E402
 from lossyless_amd.hyperprior_fit import _DeviceEngine, pack_parameters            # noqa: E402
-from lossyless_amd.probe import _Adam                                              # noqa: E402
+from lossyless_amd._train import _Adam                                             # noqa: E402
 
 
 class LowerBound(torch.autograd.Function):
