@@ -1,5 +1,6 @@
-"""Shared by test_knn_probe_host.py and test_gpu_knn_probe.py: callers of ``lla_knn_pass`` / ``lla_knn_finish``, the float64
-scores with the rounding bound the kernel's are held to, a brute-force search and the votes in float64 (no test in here)."""
+"""Shared by test_knn_probe_host.py, test_gpu_knn_probe.py and test_gpu_row_tile_walks.py: callers of ``lla_knn_pass`` /
+``lla_knn_finish``, the float64 scores with the rounding bound the kernel's are held to, a brute-force search, the list
+properties of a search and the votes in float64 (no test in here)."""
 import numpy as np
 import torch
 
@@ -74,6 +75,38 @@ def brute_force(s, k, skip=None):
             order = order[order != int(skip[i])]
         out[i] = order[:k]
     return torch.from_numpy(out)
+
+
+def check_lists(val, idx, s, E, k, n, q_self, what):
+    """The issue's list properties of one search against the float64 scores s and their bound E [Q, n]."""
+    val64, idx64 = val.double().cpu(), idx.to(torch.int64).cpu()
+    s, E = s.cpu(), E.cpu()
+    Q = s.shape[0]
+    skip = torch.full((Q,), -1, dtype=torch.int64) if q_self is None else q_self.to(torch.int64).cpu()
+    usable = n - ((skip >= 0) & (skip < n)).to(torch.int64)
+    worst = 0.0
+    for i in range(Q):
+        used = int(min(k, int(usable[i])))
+        ids, vs = idx64[i, :used], val64[i, :used]
+        assert bool((idx64[i, used:] == -1).all()) and bool(torch.isinf(val64[i, used:]).all()) \
+            and bool((val64[i, used:] < 0).all()), f"{what} query {i}: unused slots"
+        assert bool(((ids >= 0) & (ids < n)).all()) and ids.unique().numel() == used, f"{what} query {i}: range / unique"
+        assert not bool((ids == skip[i]).any()), f"{what} query {i}: lists the row it skips"
+        err, lim = (vs - s[i, ids]).abs(), E[i, ids]
+        assert bool((err <= lim).all()), f"{what} query {i}: score error / bound = {float((err / lim).max()):.3g}"
+        worst = max(worst, float((err / lim.clamp_min(1e-300)).max()) if used else 0.0)
+        v32, i32 = val[i, :used].cpu(), ids
+        assert bool(((v32[1:] < v32[:-1]) | ((v32[1:] == v32[:-1]) & (i32[1:] > i32[:-1]))).all()), f"{what} query {i}: order"
+        out = torch.ones(n, dtype=torch.bool)
+        out[ids] = False
+        if 0 <= int(skip[i]) < n:
+            out[skip[i]] = False
+        if used < k:
+            assert not bool(out.any()), f"{what} query {i}: a short list misses rows"
+        elif bool(out.any()):
+            last = ids[-1]
+            assert bool((s[i, out] <= vs[-1] + E[i, out] + E[i, last]).all()), f"{what} query {i}: completeness"
+    return worst
 
 
 def votes64(val, idx, y, K, inv_T):

@@ -11,7 +11,7 @@ import pytest
 import torch
 
 from conftest import load_tables
-from knn_util import knn_search, scores_and_bound, votes64
+from knn_util import check_lists as _check_lists, knn_search, scores_and_bound, votes64
 from oracle import cbind, container, eb
 from probe_util import U
 
@@ -37,38 +37,6 @@ def _case(Q, n, C, dtype, metric, seed, pad=8):
     q_self = torch.randint(-1, n, (Q,), generator=g).to(torch.int32).cuda() if seed % 2 else None
     inv_T = float(np.float32(1 / 0.07 if metric == 1 else 1 / C ** 0.5))
     return z, ld_z, q, ld_q, y, q_self, inv_T
-
-
-def _check_lists(val, idx, s, E, k, n, q_self, what):
-    """The issue's list properties of one search against the float64 scores s and their bound E [Q, n]."""
-    val64, idx64 = val.double().cpu(), idx.to(torch.int64).cpu()
-    s, E = s.cpu(), E.cpu()
-    Q = s.shape[0]
-    skip = torch.full((Q,), -1, dtype=torch.int64) if q_self is None else q_self.to(torch.int64).cpu()
-    usable = n - ((skip >= 0) & (skip < n)).to(torch.int64)
-    worst = 0.0
-    for i in range(Q):
-        used = int(min(k, int(usable[i])))
-        ids, vs = idx64[i, :used], val64[i, :used]
-        assert bool((idx64[i, used:] == -1).all()) and bool(torch.isinf(val64[i, used:]).all()) \
-            and bool((val64[i, used:] < 0).all()), f"{what} query {i}: unused slots"
-        assert bool(((ids >= 0) & (ids < n)).all()) and ids.unique().numel() == used, f"{what} query {i}: range / unique"
-        assert not bool((ids == skip[i]).any()), f"{what} query {i}: lists the row it skips"
-        err, lim = (vs - s[i, ids]).abs(), E[i, ids]
-        assert bool((err <= lim).all()), f"{what} query {i}: score error / bound = {float((err / lim).max()):.3g}"
-        worst = max(worst, float((err / lim.clamp_min(1e-300)).max()) if used else 0.0)
-        v32, i32 = val[i, :used].cpu(), ids
-        assert bool(((v32[1:] < v32[:-1]) | ((v32[1:] == v32[:-1]) & (i32[1:] > i32[:-1]))).all()), f"{what} query {i}: order"
-        out = torch.ones(n, dtype=torch.bool)
-        out[ids] = False
-        if 0 <= int(skip[i]) < n:
-            out[skip[i]] = False
-        if used < k:
-            assert not bool(out.any()), f"{what} query {i}: a short list misses rows"
-        elif bool(out.any()):
-            last = ids[-1]
-            assert bool((s[i, out] <= vs[-1] + E[i, out] + E[i, last]).all()), f"{what} query {i}: completeness"
-    return worst
 
 
 @pytest.mark.parametrize("metric", [0, 1], ids=["dot", "cosine"])
