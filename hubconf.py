@@ -67,7 +67,7 @@ clip_compressor_b001 = _entry("b001", 1e-2)
 clip_compressor_b01 = _entry("b01", 1e-1)
 
 
-def clip_hyperprior_compressor(state_dict, device=_ON, coded_means="scales", **kwargs):
+def clip_hyperprior_compressor(state_dict, device=_ON, coded_means="scales", mlp_precision="fp32", **kwargs):
     """CLIP ViT-B/32 + scale-hyperprior compressor (the model behind the reference's headline table), MI355X kernels.
 
     state_dict   : what the reference's ``HRateHyperprior`` saves (``main.py`` training), as a dict or a path to it.  No
@@ -77,14 +77,20 @@ def clip_hyperprior_compressor(state_dict, device=_ON, coded_means="scales", **k
                    ``"predicted"`` (opt-in: code with the means the model was trained with -- a lower rate for a model of
                    one's own, not the reference's format).  The file does not record the mode: one written in one mode
                    and read in the other, like one read with another state dict, decodes to wrong values without an error.
+    mlp_precision : ``"fp32"`` (default: the hyperprior MLPs on the fp32 matrix cores; files are decoded on the GPU only) or
+                   ``"ordered"`` (opt-in: every MLP output one ascending ``fmaf`` chain, which the host reproduces bit for
+                   bit -- ``decompress_dataset(file, is_cpu=True)`` then decodes without a GPU, also on a compressor built
+                   with ``device="cpu"``).  Not recorded in the file either, with the same consequence.
     device, clip_weights, gpu_preprocess, other kwargs : as for ``clip_compressor_b005``; forwarded to
                    ``lossyless_amd.HyperpriorClipCompressor``
 
     Returns ``(compressor, transform)`` with the factorized entry points' surface; ``compress`` returns
     ``[z_strings, side_z_strings]``, the ``.bin`` file holds two records per image, and ``decompress_dataset`` decodes on
-    the GPU (``is_cpu=True`` raises: the coding-table rows come from an MLP evaluated on the fp32 matrix cores).
+    the GPU (``is_cpu=True`` raises unless ``mlp_precision="ordered"``: the coding-table rows come from an MLP evaluated on
+    the fp32 matrix cores).
     """
-    model = _HyperpriorCompressor(pretrained_state_dict=state_dict, device=device, coded_means=coded_means, **kwargs)
+    model = _HyperpriorCompressor(pretrained_state_dict=state_dict, device=device, coded_means=coded_means,
+                                  mlp_precision=mlp_precision, **kwargs)
     return model, model.preprocess
 
 

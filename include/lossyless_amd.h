@@ -395,6 +395,28 @@ int lla_gaussian_decode_dequantise_means(const uint8_t *payload, const uint64_t 
                                          const int32_t *cdf_len, const int32_t *offset, float *z_hat, int32_t *status,
                                          void *stream);
 
+/* HOST twins of the two conditional coders (csrc/host.cpp; every pointer a host pointer, threaded over images): the same
+ * rows (counted as above), the same three separately rounded fp32 operations and the host coder's rANS primitives -- the
+ * same symbols, bytes and values as the device entry points, given the same `scales` (rates.MLP(precision="ordered")
+ * gives the host the device's scales bit for bit).  means == NULL: the scales are the means (lla_gaussian_quantise_encode
+ * / lla_gaussian_decode_dequantise); else element (b, c) at means[b*ld_means + c] (the _means forms).
+ *   encode: image b's stream goes to out + out_off[b] (behind its be32 length if record_prefix), out_off [B+1] as in
+ *           lla_rans_encode_batch_host -- LLA_ECAP with out_off filled when cap is too small (out may then be NULL).
+ *   decode: image b's stream is record off_first + b*off_step of `off`; status[b] = 1 for a record shorter than 8 bytes,
+ *           not a whole number of words, or read past its end (its row is then zeros, as the device leaves it for a record it
+ *           cannot open, or whatever the bounded reads gave). */
+int lla_gaussian_quantise_encode_host(const void *z, int z_dtype, int B, int C, const float *bias,
+                                      const float *exp_scale, const float *scales, size_t ld_scales,
+                                      const float *means, size_t ld_means, const float *scale_table,
+                                      float scale_bound, const int32_t *cdf, int T, int W, const int32_t *cdf_len,
+                                      const int32_t *offset, int record_prefix, uint8_t *out, size_t cap,
+                                      uint64_t *out_off, int32_t *symbols_out, int32_t *indexes_out);
+int lla_gaussian_decode_dequantise_host(const uint8_t *payload, const uint64_t *off, int record_prefix, int off_first,
+                                        int off_step, int B, int C, const float *bias, const float *exp_scale,
+                                        const float *scales, size_t ld_scales, const float *means, size_t ld_means,
+                                        const float *scale_table, float scale_bound, const int32_t *cdf, int T, int W,
+                                        const int32_t *cdf_len, const int32_t *offset, float *z_hat, int32_t *status);
+
 /* lla_gaussian_decode_gather with means (rates.py:647-650's means, not rates.py:689-696's): `means` is indexed by the
  * OUTPUT row b, as `scales` is.  A row whose status_in is non-zero reads neither matrix.  The means are staged in LDS
  * next to the scales (32 KiB more in front of the packed rows): lla_gaussian_decode_gather_means_lds_bytes is this entry
@@ -648,6 +670,19 @@ int lla_gemm_plan(int epi, int amode, int M, int N, int K, int lda, int ldc, int
  * alone, so the values do not depend on the batch size (encoder and decoder may use different ones). */
 int lla_gemm_f32(const float *A, int lda, const float *W, int ldw, const float *bias, float *C, int ldc,
                  int M, int N, int K, int relu, void *stream);
+
+/* The same layer with a DEFINED arithmetic (csrc/gemm_f32_ordered.hip, whose header comment is the contract), on the
+ * VALU: the operands, pitches and padding rules of lla_gemm_f32 (A, W, C and bias 16-byte aligned besides), and for every
+ * output element, whatever M, the grid or the call's row offset,
+ *     acc = +0.0f;  for k = 0 .. K-1 ascending (padding included): acc = fmaf(A[m][k], W[n][k], acc);
+ *     y = acc + bias[n] (one rounded add; skipped for bias == NULL);  relu: y = y > 0.f ? y : 0.f;  C[m][n] = y
+ * in IEEE-754 binary32, round to nearest even, denormals kept.  lla_gemm_f32_ordered_host (csrc/host.cpp) takes the same
+ * arguments as HOST pointers (no alignment asked) and runs the same chain with std::fmaf, threaded over rows: the same
+ * bits.  What rates.MLP(precision="ordered") runs on, so that a hyperprior container can be decoded without a GPU. */
+int lla_gemm_f32_ordered(const float *A, int lda, const float *W, int ldw, const float *bias, float *C, int ldc,
+                         int M, int N, int K, int relu, void *stream);
+int lla_gemm_f32_ordered_host(const float *A, int lda, const float *W, int ldw, const float *bias, float *C, int ldc,
+                              int M, int N, int K, int relu);
 
 /* One data pass of a linear probe (lossyless_amd/csrc/probe.hip): the sums that the LinearSVC objective -- squared hinge,
  * one-vs-rest, the third step of the reference's workflow (README.md:74-82: LinearSVC(C=7e-3).fit(Z, Y) on the

@@ -107,6 +107,14 @@ _SIGNATURES = {
     "lla_gemm_plan": (_i, [_i, _i, _i, _i, _i, _i, _i, _i, _i, _vp, _vp, _vp]),
     "lla_gemm_f16_ex": (_i, [_vp, _i, _vp, _vp, _vp, _i, _vp, _i, _i, _i, _i, _i, _vp]),
     "lla_gemm_f32": (_i, [_vp, _i, _vp, _i, _vp, _vp, _i, _i, _i, _i, _i, _vp]),
+    # the ordered fp32 Linear layer (one ascending fmaf chain per output) and its host twin; the host twins of the
+    # conditional coder (means = NULL: the scales are the means)
+    "lla_gemm_f32_ordered": (_i, [_vp, _i, _vp, _i, _vp, _vp, _i, _i, _i, _i, _i, _vp]),
+    "lla_gemm_f32_ordered_host": (_i, [_vp, _i, _vp, _i, _vp, _vp, _i, _i, _i, _i, _i]),
+    "lla_gaussian_quantise_encode_host": (_i, [_vp, _i, _i, _i, _vp, _vp, _vp, _sz, _vp, _sz, _vp, ctypes.c_float, _vp, _i,
+                                               _i, _vp, _vp, _i, _vp, _sz, _vp, _vp, _vp]),
+    "lla_gaussian_decode_dequantise_host": (_i, [_vp, _vp, _i, _i, _i, _i, _i, _vp, _vp, _vp, _sz, _vp, _sz, _vp,
+                                                 ctypes.c_float, _vp, _i, _i, _vp, _vp, _vp, _vp]),
     "lla_svm_pass_workspace_bytes": (_sz, [_i, _i]),
     "lla_svm_pass": (_i, [_vp, _i, _i, _vp, _i, _i, _vp, _vp, _vp, _vp, _i, _i, _vp, _vp, _vp, _i, _vp, _vp]),
     "lla_svm_grid_pass_workspace_bytes": (_sz, [_i, _i]),

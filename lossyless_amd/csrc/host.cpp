@@ -144,14 +144,16 @@ inline int digits_of(uint32_t raw) {
   return n;
 }
 
+// `rows`: the table row of every element (the indexed coder: GaussianConditional), or NULL for row = channel.
 void encode_image(const int32_t *sym, int C, const int32_t *cdf, int W, const int32_t *cdf_len,
-                  const int32_t *offset, StreamBuilder &sb) {
+                  const int32_t *offset, StreamBuilder &sb, const int32_t *rows = nullptr) {
   sb.state = kLower;
   sb.spill.clear();
   for (int c = C - 1; c >= 0; --c) {  // last pushed symbol is coded first
-    const int32_t *row = cdf + size_t(c) * W;
-    const int esc = cdf_len[c] - 2;
-    const Coded k = classify(sym[c], offset[c], esc);
+    const int t = rows ? rows[c] : c;
+    const int32_t *row = cdf + size_t(t) * W;
+    const int esc = cdf_len[t] - 2;
+    const Coded k = classify(sym[c], offset[t], esc);
     if (k.escaped) {
       // forward order was: escape slot, count digits, payload digits (LSB first) -> reverse it
       const int nd = digits_of(k.raw);
@@ -185,13 +187,14 @@ struct StreamReader {
 };
 
 int decode_image(const uint8_t *s, size_t n, int C, const int32_t *cdf, int W,
-                 const int32_t *cdf_len, const int32_t *offset, int32_t *out) {
+                 const int32_t *cdf_len, const int32_t *offset, int32_t *out, const int32_t *rows = nullptr) {
   StreamReader r{0, s, s + n};
   const uint32_t lo = r.word(), hi = r.word();
   r.state = uint64_t(lo) | (uint64_t(hi) << 32);
   for (int c = 0; c < C; ++c) {
-    const int32_t *row = cdf + size_t(c) * W;
-    const int len = cdf_len[c], esc = len - 2;
+    const int t = rows ? rows[c] : c;
+    const int32_t *row = cdf + size_t(t) * W;
+    const int len = cdf_len[t], esc = len - 2;
     const uint32_t target = uint32_t(r.state & 0xffffu);
     int slot = int(std::upper_bound(row, row + len, int32_t(target)) - row) - 1;
     if (slot < 0) slot = 0;
@@ -209,7 +212,7 @@ int decode_image(const uint8_t *s, size_t n, int C, const int32_t *cdf, int W,
       v = int64_t(raw >> 1);
       v = (raw & 1u) ? -v - 1 : v + esc;
     }
-    out[c] = int32_t(v + offset[c]);
+    out[c] = int32_t(v + offset[t]);
   }
   return r.overrun ? 1 : 0;
 }
@@ -362,6 +365,199 @@ extern "C" int lla_rans_decode_gather_host(const uint8_t *payload, const uint64_
         else row16[c] = half_bits_rn(z);
       }
       status[b] = st;
+    }
+  });
+  return LLA_OK;
+}
+
+// ---------------------------------------------------------------------------
+// Host side of the ORDERED hyperprior mode (rates.MLP(precision="ordered")): the Linear layers as the chain that
+// gemm_f32_ordered.hip's header comment defines, and the conditional coder's two kernels (entropy_gaussian.hip) with the
+// host coder's primitives above -- a hyperprior container is then decoded, and written, without a GPU, bit-equal.
+// ---------------------------------------------------------------------------
+namespace {
+
+template <typename F>
+void for_rows(int M, int per_thread, F body) {   // for_images with a caller's grain
+  unsigned hw = std::thread::hardware_concurrency();
+  int nt = int(std::min<unsigned>(hw ? hw : 1u, 32u));
+  nt = std::max(1, std::min(nt, M / per_thread));
+  if (nt == 1) { body(0, M); return; }
+  std::vector<std::thread> pool;
+  for (int t = 0; t < nt; ++t) {
+    const int lo = int(int64_t(M) * t / nt), hi = int(int64_t(M) * (t + 1) / nt);
+    pool.emplace_back([=] { body(lo, hi); });
+  }
+  for (auto &th : pool) th.join();
+}
+
+constexpr int kPanel = 16;   // output columns walked together: 16 independent chains per row
+
+// Rows [lo, hi) of the layer.  `wt` holds W in panels of kPanel columns, [panel][k][kPanel], so that the 16 chains of a
+// panel read one contiguous line per k.  Every chain is acc = fmaf(A[m][k], W[n][k], acc) for k ascending from acc = +0
+// (the contract in gemm_f32_ordered.hip): a vector fma is one IEEE fma per lane, so vectorising over the PANEL changes
+// nothing, and nothing here sums across k in another order.  Built once for machines with an FMA unit (std::fmaf is then
+// the instruction) and once without (libm's fmaf: the same values, slowly); the loader picks.
+#if defined(__x86_64__) && !defined(__HIP_DEVICE_COMPILE__)   // (the Makefile compiles this file as HIP: a host and a device pass)
+__attribute__((target_clones("arch=x86-64-v3", "default")))
+#endif
+void ordered_rows(const float *A, int lda, const float *wt, const float *bias, float *C, int ldc, int lo, int hi,
+                  int N, int K, int relu) {
+  for (int m = lo; m < hi; ++m) {
+    const float *a = A + size_t(m) * lda;
+    for (int n0 = 0; n0 < N; n0 += kPanel) {
+      const float *w = wt + size_t(n0) * K;
+      float acc[kPanel];
+      for (int j = 0; j < kPanel; ++j) acc[j] = 0.f;
+      for (int k = 0; k < K; ++k) {
+        const float x = a[k];
+        for (int j = 0; j < kPanel; ++j) acc[j] = std::fmaf(x, w[size_t(k) * kPanel + j], acc[j]);
+      }
+      const int nn = std::min(kPanel, N - n0);
+      for (int j = 0; j < nn; ++j) {
+        float y = acc[j];
+        if (bias) y = y + bias[n0 + j];   // (-ffp-contract=off: one rounded add)
+        if (relu) y = y > 0.f ? y : 0.f;
+        C[size_t(m) * ldc + n0 + j] = y;
+      }
+    }
+  }
+}
+
+// GaussianConditional.build_indexes by counting, as entropy_gaussian.hip's scale_rows: in [0, T-1] whatever the scale.
+inline int scale_row(const float *stab, int T, float bound, float scale) {
+  const float sb = scale < bound ? bound : scale;
+  int row = T - 1;
+  for (int t = 0; t < T - 1; ++t) row -= sb <= stab[t] ? 1 : 0;
+  return row;
+}
+
+// (int32_t)rintf(d) as the device converts: saturating, NaN -> 0
+inline int32_t rint_i32(float d) {
+  const float r = std::nearbyintf(d);   // round half to even (the default rounding mode)
+  if (!(r == r)) return 0;
+  if (r >= 2147483648.f) return INT32_MAX;
+  if (r <= -2147483648.f) return INT32_MIN;
+  return int32_t(r);
+}
+
+inline float half_to_float(uint16_t bits) {
+  _Float16 h;
+  std::memcpy(&h, &bits, sizeof h);
+  return float(h);
+}
+
+bool gauss_args_ok(int B, int C, const float *bias, const float *exp_scale, const float *scales, size_t ld_scales,
+                   const float *means, size_t ld_means, const float *scale_table, const int32_t *cdf, int T, int W,
+                   const int32_t *cdf_len, const int32_t *offset) {
+  return B >= 0 && C > 0 && T > 0 && bias && exp_scale && scales && ld_scales >= size_t(C) &&
+         (!means || ld_means >= size_t(C)) && scale_table && tables_ok(T, cdf, W, cdf_len, offset);
+}
+
+}  // namespace
+
+extern "C" int lla_gemm_f32_ordered_host(const float *A, int lda, const float *W, int ldw, const float *bias,
+                                         float *C, int ldc, int M, int N, int K, int relu) {
+  if (M < 0 || N <= 0 || K <= 0 || (K & 7) || (N & 3) || lda < K || ldw < K || ldc < N || (lda & 3) ||
+      (ldw & 3) || (ldc & 3))
+    return LLA_EINVAL;
+  if (M == 0) return LLA_OK;
+  if (!A || !W || !C) return LLA_EINVAL;
+  const int panels = (N + kPanel - 1) / kPanel;
+  std::vector<float> wt(size_t(panels) * kPanel * K, 0.f);   // (columns beyond N: zero weights, never stored)
+  for (int n = 0; n < N; ++n)
+    for (int k = 0; k < K; ++k)
+      wt[(size_t(n / kPanel) * K + k) * kPanel + n % kPanel] = W[size_t(n) * ldw + k];
+  for_rows(M, 16, [&](int lo, int hi) { ordered_rows(A, lda, wt.data(), bias, C, ldc, lo, hi, N, K, relu); });
+  return LLA_OK;
+}
+
+extern "C" int lla_gaussian_quantise_encode_host(const void *z, int z_dtype, int B, int C, const float *bias,
+                                                 const float *exp_scale, const float *scales, size_t ld_scales,
+                                                 const float *means, size_t ld_means, const float *scale_table,
+                                                 float scale_bound, const int32_t *cdf, int T, int W,
+                                                 const int32_t *cdf_len, const int32_t *offset, int record_prefix,
+                                                 uint8_t *out, size_t cap, uint64_t *out_off, int32_t *symbols_out,
+                                                 int32_t *indexes_out) {
+  // Host twin of gaussian_encode_kernel: quantise_one's three separately rounded operations, scale_rows, the indexed coder.
+  if (z_dtype != LLA_Z_F16 && z_dtype != LLA_Z_F32) return LLA_EINVAL;
+  if (!out_off || (B > 0 && !z) ||
+      !gauss_args_ok(B, C, bias, exp_scale, scales, ld_scales, means, ld_means, scale_table, cdf, T, W, cdf_len, offset))
+    return LLA_EINVAL;
+  std::vector<std::vector<uint8_t>> streams((size_t)B);
+  for_images(B, [&](int lo, int hi) {
+    StreamBuilder sb;
+    std::vector<int32_t> sym((size_t)C), row((size_t)C);
+    for (int b = lo; b < hi; ++b) {
+      const float *sc = scales + size_t(b) * ld_scales;
+      const float *mn = means ? means + size_t(b) * ld_means : sc;   // (the unbounded scale stands in for the mean)
+      for (int c = 0; c < C; ++c) {
+        const float zf = z_dtype == LLA_Z_F32 ? static_cast<const float *>(z)[size_t(b) * C + c]
+                                              : half_to_float(static_cast<const uint16_t *>(z)[size_t(b) * C + c]);
+        const float t = zf + bias[c];
+        const float u = t * exp_scale[c];
+        const float d = u - mn[c];
+        sym[size_t(c)] = rint_i32(d);
+        row[size_t(c)] = scale_row(scale_table, T, scale_bound, sc[c]);
+      }
+      if (symbols_out) std::copy(sym.begin(), sym.end(), symbols_out + size_t(b) * C);
+      if (indexes_out) std::copy(row.begin(), row.end(), indexes_out + size_t(b) * C);
+      encode_image(sym.data(), C, cdf, W, cdf_len, offset, sb, row.data());
+      streams[size_t(b)].resize(sb.bytes());
+      sb.write(streams[size_t(b)].data());
+    }
+  });
+  const size_t pre = record_prefix ? 4 : 0;
+  out_off[0] = 0;
+  for (int b = 0; b < B; ++b) out_off[b + 1] = out_off[b] + pre + streams[size_t(b)].size();
+  if (out_off[B] > cap) return LLA_ECAP;  // out_off still reports the size needed
+  if (out_off[B] && !out) return LLA_EINVAL;
+  for (int b = 0; b < B; ++b) {
+    uint8_t *dst = out + out_off[b];
+    const auto &s = streams[size_t(b)];
+    if (pre) {
+      const uint32_t n = uint32_t(s.size());
+      dst[0] = uint8_t(n >> 24); dst[1] = uint8_t(n >> 16); dst[2] = uint8_t(n >> 8); dst[3] = uint8_t(n);
+      dst += 4;
+    }
+    std::copy(s.begin(), s.end(), dst);
+  }
+  return LLA_OK;
+}
+
+extern "C" int lla_gaussian_decode_dequantise_host(const uint8_t *payload, const uint64_t *off, int record_prefix,
+                                                   int off_first, int off_step, int B, int C, const float *bias,
+                                                   const float *exp_scale, const float *scales, size_t ld_scales,
+                                                   const float *means, size_t ld_means, const float *scale_table,
+                                                   float scale_bound, const int32_t *cdf, int T, int W,
+                                                   const int32_t *cdf_len, const int32_t *offset, float *z_hat,
+                                                   int32_t *status) {
+  // Host twin of gaussian_decode_kernel: scale_rows, the indexed decode, dequantise_one's three rounded operations.
+  if (B == 0) return LLA_OK;
+  if (!payload || !off || off_first < 0 || off_step < 1 || !z_hat || !status ||
+      !gauss_args_ok(B, C, bias, exp_scale, scales, ld_scales, means, ld_means, scale_table, cdf, T, W, cdf_len, offset))
+    return LLA_EINVAL;
+  const size_t pre = record_prefix ? 4 : 0;
+  for_images(B, [&](int lo, int hi) {
+    std::vector<int32_t> sym((size_t)C), row((size_t)C);
+    for (int b = lo; b < hi; ++b) {
+      const size_t rec = size_t(off_first) + size_t(b) * size_t(off_step);
+      const uint64_t a = off[rec] + pre, e = off[rec + 1];
+      float *dst = z_hat + size_t(b) * C;
+      if (e < a || e - a < 8 || ((e - a) & 3u)) {   // (what the device's open_stream refuses)
+        std::fill(dst, dst + C, 0.f);
+        status[b] = 1;
+        continue;
+      }
+      const float *sc = scales + size_t(b) * ld_scales;
+      const float *mn = means ? means + size_t(b) * ld_means : sc;
+      for (int c = 0; c < C; ++c) row[size_t(c)] = scale_row(scale_table, T, scale_bound, sc[c]);
+      status[b] = decode_image(payload + a, size_t(e - a), C, cdf, W, cdf_len, offset, sym.data(), row.data());
+      for (int c = 0; c < C; ++c) {
+        const float zh = float(sym[size_t(c)]) + mn[c];
+        const float q = zh / exp_scale[c];
+        dst[c] = q - bias[c];
+      }
     }
   });
   return LLA_OK;

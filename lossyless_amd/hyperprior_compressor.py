@@ -102,26 +102,35 @@ class HyperpriorClipCompressor(ClipCompressor):
         ``decompress``, ``get_rate``, ``compress_dataset``, ``decompress_dataset`` and ``open_dataset`` all follow it.  The
         container format is the same in both modes and does not record the mode: a file written in one and read in the
         other -- like a file read with another state dict -- decodes to wrong values without an error.
+    mlp_precision : ``"fp32"`` (default), ``"fp16"`` or ``"ordered"``
+        Passed to :class:`~lossyless_amd.rates.HRateHyperprior`: which arithmetic the two hyperprior MLPs run in.  With
+        ``"ordered"`` (every MLP output one ascending ``fmaf`` chain, on a VALU kernel) the host reproduces the GPU's table
+        rows bit for bit, so ``decompress_dataset(file, is_cpu=True)`` decodes on the host -- on this compressor or on one
+        built with ``device="cpu"`` -- and ``decompress(strings)`` works on a CPU compressor; ``compress_dataset``,
+        ``compress`` and ``forward`` still need the GPU (the tower has no CPU path), and ``open_dataset`` on the CPU keeps
+        raising.  Like ``coded_means`` the mode is neither in the container nor in ``state_dict()``, and combines freely
+        with it: a file written in one mode and read in another decodes to wrong values without an error.
 
     ``compress(X)`` returns ``[z_strings, side_z_strings]`` (what ``HRateHyperprior.compress`` returns), ``decompress``
     takes it back.  ``compressor(X)`` is the coded representation without coding and equals ``decompress(compress(X))``
     bit for bit.  ``decompress_dataset`` decodes on the GPU only: ``is_cpu`` defaults to False here and ``is_cpu=True``
-    raises ``NotImplementedError``, because the table rows are chosen by the fp32 MFMA MLP, which a CPU evaluation
-    reproduces to roundoff but not bit for bit -- strings written here are decoded here.
+    raises ``NotImplementedError`` unless ``mlp_precision="ordered"``, because the table rows are chosen by the fp32 MFMA
+    MLP, which a CPU evaluation reproduces to roundoff but not bit for bit -- strings written here are decoded here.
     """
 
     records_per_image = 2
 
     def __init__(self, pretrained_state_dict, is_jit=False,
                  device="cuda" if torch.cuda.is_available() else "cpu", *,
-                 clip_weights=None, vit_chunk=0, gpu_preprocess=False, coded_means="scales"):
+                 clip_weights=None, vit_chunk=0, gpu_preprocess=False, coded_means="scales",
+                 mlp_precision="fp32"):
         nn.Module.__init__(self)     # (ClipCompressor's own constructor goes on to build the factorized model)
         self._init_tower(clip_weights, vit_chunk, gpu_preprocess)
         if not isinstance(pretrained_state_dict, dict):
             pretrained_state_dict = torch.load(pretrained_state_dict, map_location="cpu", weights_only=True)
         side_w = pretrained_state_dict.get("side_encoder.module.8.weight")
         self.hyperprior = HRateHyperprior(self.z_dim, side_z_dim=None if side_w is None else int(side_w.shape[0]),
-                                          coded_means=coded_means)
+                                          coded_means=coded_means, mlp_precision=mlp_precision)
         self.side_z_dim = self.hyperprior.side_z_dim
         missing, _ = self.hyperprior.load_state_dict(pretrained_state_dict, strict=False)
         tables = ("_quantized_cdf", "_offset", "_cdf_length", "scale_table")     # (built below when not carried)
@@ -159,10 +168,14 @@ class HyperpriorClipCompressor(ClipCompressor):
     def decompress(self, all_strings):
         """``[z_strings, side_z_strings]`` -> z_hat [B,512] fp32 on the GPU (one host sync per call: ``decode_device``
         reads the statuses back before it returns)."""
-        self._check_gpu()
+        on_host = self._ordered and str(self.device) == "cpu"      # (ordered: a CPU compressor decodes on the host)
+        if not on_host:
+            self._check_gpu()
         if not (isinstance(all_strings, (list, tuple)) and len(all_strings) == 2):
             raise ValueError("expected [z_strings, side_z_strings]")
         body, off = _pair_records(*all_strings)
+        if on_host:
+            return torch.from_numpy(self._decode_records_host(body, off, len(all_strings[0])))
         return self._decode_records(body, off, len(all_strings[0]))
 
     def get_rate(self, X):
@@ -196,8 +209,21 @@ class HyperpriorClipCompressor(ClipCompressor):
     def _records_of(strings):
         raise NotImplementedError("HyperpriorClipCompressor codes two records per image: see decompress")
 
+    @property
+    def _ordered(self):
+        return self.hyperprior.mlp_precision == "ordered"
+
     def _decode_records_host(self, body, off_np, B):
-        raise NotImplementedError("HyperpriorClipCompressor has no host decoder: " + _WHY_NO_CPU)
+        """Host twin of ``_decode_records`` (``HRateHyperprior.decode_host``) -> float32 [B,512] ndarray, no GPU involved;
+        ``mlp_precision="ordered"`` only."""
+        if not self._ordered:
+            raise NotImplementedError("HyperpriorClipCompressor has no host decoder: " + _WHY_NO_CPU)
+        payload = torch.from_numpy(np.array(body, dtype=np.uint8))      # (a copy: the caller's may be read-only)
+        offsets = torch.from_numpy(np.ascontiguousarray(off_np).astype(np.int64))
+        try:
+            return self.hyperprior.decode_host(payload, offsets, B).numpy()
+        except ValueError as e:
+            raise ValueError(f"{e} in container") from None
 
     # ------------------------------------------------------------------ datasets
     def open_dataset(self, file, label_file=None, device=None):
@@ -205,7 +231,7 @@ class HyperpriorClipCompressor(ClipCompressor):
         serves the rows of any index vector, bit-equal to ``decompress_dataset(file)[indices]``.  GPU only: the object
         always lives on this compressor's device (it reads the compressor's tables and MLP there; ``device`` only says
         GPU or CPU); ``device="cpu"``, or a compressor on the CPU, raises ``NotImplementedError`` before the file is
-        touched."""
+        touched -- with ``mlp_precision="ordered"`` too: ``HyperpriorLatents`` has no host form."""
         here = torch.device(self.device)
         want = here if device is None else torch.device(device)
         if here.type != "cuda" or want.type != "cuda":
@@ -221,12 +247,15 @@ class HyperpriorClipCompressor(ClipCompressor):
         """Decompress a file written by ``compress_dataset`` -> float32 [N,512] ndarray (and the labels).
 
         ``is_cpu=True`` raises ``NotImplementedError``: the table rows are chosen by the fp32 MFMA MLP, and a CPU
-        evaluation of it is roundoff-close, not bit-equal, so it may pick other rows.  ``batch_size`` images are decoded
+        evaluation of it is roundoff-close, not bit-equal, so it may pick other rows -- unless the compressor was built with
+        ``mlp_precision="ordered"``: then the records are decoded on the host (``HRateHyperprior.decode_host``), on a
+        compressor on either device, to the array ``is_cpu=False`` gives, bit for bit.  ``batch_size`` images are decoded
         per launch; any value gives the same array.  ValueError for a file that is truncated, holds an odd number of
         records or a damaged record."""
-        if is_cpu:
+        if is_cpu and not self._ordered:
             raise NotImplementedError("HyperpriorClipCompressor.decompress_dataset(is_cpu=True): " + _WHY_NO_CPU)
-        self._check_gpu()
+        if not is_cpu:
+            self._check_gpu()
         start = time.time()
         blob = np.fromfile(str(file), dtype=np.uint8)
         L = _lib.lib()
@@ -249,8 +278,8 @@ class HyperpriorClipCompressor(ClipCompressor):
         for i in range(0, n_img, batch_size):
             j = min(i + batch_size, n_img)
             b0, b1 = int(off[2 * i]), int(off[2 * j])
-            out = self._decode_records(body[b0:b1 + 4], off[2 * i:2 * j + 1] - off[2 * i], j - i)
-            Z_hat[i:j] = out.cpu().numpy()
+            args = (body[b0:b1 + 4], off[2 * i:2 * j + 1] - off[2 * i], j - i)
+            Z_hat[i:j] = self._decode_records_host(*args) if is_cpu else self._decode_records(*args).cpu().numpy()
 
         dec_time = (time.time() - start) / max(n_img, 1)
         if is_info:

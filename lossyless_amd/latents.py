@@ -245,15 +245,19 @@ class HyperpriorLatents(_Latents):
     s_hat and the MLP activations, ``workspace_nbytes`` = B x (104 + 512 + 512 + 1024) x 4 bytes, 0.56 GB at B = 65536
     -- so that repeated calls of one length allocate nothing; calls on one object therefore belong on one stream.  A
     call of another length replaces them, ``release()`` frees them, and ``batches()`` releases them when the epoch
-    ends.  The tensor returned is never one of them."""
+    ends.  The tensor returned is never one of them.
+
+    A compressor built with ``mlp_precision="ordered"`` is served the same way (``forward_padded`` then runs
+    ``lla_gemm_f32_ordered``).  The object has no host form in either mode: on a CPU compressor it raises, although an
+    ordered container itself can be decoded there (``decompress_dataset(file, is_cpu=True)``)."""
 
     def __init__(self, file, compressor, label_file=None):
         self._set_device(compressor.device, "HyperpriorLatents needs an MI355X")
         if self.device.type != "cuda":
             raise RuntimeError("HyperpriorLatents decodes on the GPU only")
         m = compressor.hyperprior
-        if m.mlp_precision != "fp32":
-            raise NotImplementedError("HyperpriorLatents runs the fp32 z_encoder only")
+        if m.mlp_precision not in ("fp32", "ordered"):
+            raise NotImplementedError("HyperpriorLatents runs the fp32 and the ordered z_encoder only")
         m._check_device_path("HyperpriorLatents")
         self._model = m
         self.z_dim, self._side_dim = int(m.z_dim), int(m.side_z_dim)

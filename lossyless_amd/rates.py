@@ -312,12 +312,18 @@ class MLP(nn.Module):
     on the batch size (a decoder may evaluate the network in other pieces than the encoder did: tested).  They are
     fp32-roundoff close to, not bit-identical with, a CPU / hipBLASLt evaluation (different summation order):
     strings written here are decoded here.  ``precision="fp16"`` (opt-in, round 3's path) runs the layers on the
-    tower's fp16 MFMA GEMMs instead (``lla_gemm_f16_ex``); CPU tensors take torch's fp32 Linear."""
+    tower's fp16 MFMA GEMMs instead (``lla_gemm_f16_ex``); CPU tensors take torch's fp32 Linear.
+
+    ``precision="ordered"`` (opt-in) gives every output a DEFINED value instead: ``acc = +0; for k ascending over the
+    padded K: acc = fmaf(x[k], w[k], acc); y = acc + bias; relu`` in IEEE binary32 (the contract in
+    ``csrc/gemm_f32_ordered.hip``).  CUDA tensors run ``lla_gemm_f32_ordered`` (a VALU kernel), CPU tensors
+    ``lla_gemm_f32_ordered_host`` on the same padded operands ([Npad8][Kpad8] weights): the same bits, so the table rows
+    a CPU derives are the GPU's and strings written on either are decoded on either."""
 
     def __init__(self, in_dim, out_dim, n_hid_layers=1, hid_dim=128, precision="fp32"):
         super().__init__()
-        if precision not in ("fp32", "fp16"):
-            raise ValueError("precision must be 'fp32' or 'fp16'")
+        if precision not in ("fp32", "fp16", "ordered"):
+            raise ValueError("precision must be 'fp32', 'fp16' or 'ordered'")
         self.precision = precision
         layers = [nn.Linear(in_dim, hid_dim), nn.Identity(), nn.ReLU(), nn.Identity()]
         for _ in range(1, n_hid_layers):
@@ -336,7 +342,10 @@ class MLP(nn.Module):
         (fp16 [Npad128][Kpad64] for the opt-in fp16 path) weights + fp32 biases."""
         lin = [m for m in self.module if isinstance(m, nn.Linear)]
         key = (str(dev), self.precision) + tuple((m.weight._version, m.bias._version, m.weight.data_ptr()) for m in lin)
-        if self._packed is None or self._packed[0] != key:
+        if self._packed is None:
+            self._packed = {}
+        cached = self._packed.get(str(dev))     # (one entry per device: an ordered module on the GPU also decodes on the host)
+        if cached is None or cached[0] != key:
             half = self.precision == "fp16"
             gn, gk, wt = (128, 64, torch.float16) if half else (8, 8, torch.float32)
             packs = []
@@ -348,13 +357,13 @@ class MLP(nn.Module):
                 b = torch.zeros(npad, dtype=torch.float32, device=dev)
                 b[:n] = m.bias.detach().to(dev, torch.float32)
                 packs.append((w, b, n, k, npad, kpad))
-            self._packed = (key, packs)
-        return self._packed[1]
+            self._packed[str(dev)] = cached = (key, packs)
+        return cached[1]
 
     def forward(self, X):
         shape = X.shape
         X2 = X.reshape(-1, shape[-1])
-        if not X2.is_cuda:
+        if not X2.is_cuda and self.precision != "ordered":
             return self.module(X2.float()).reshape(*shape[:-1], -1)
         packs = self._pack(X2.device)
         at = torch.float16 if self.precision == "fp16" else torch.float32
@@ -372,7 +381,14 @@ class MLP(nn.Module):
         for i, (w, b, n, k, npad, kpad) in enumerate(packs):
             last = i == len(packs) - 1
             c = torch.empty((rows, npad), dtype=a.dtype, device=dev) if bufs is None else bufs[i]
-            if half:
+            if self.precision == "ordered":
+                args = (_lib.ptr(a), a.shape[1], _lib.ptr(w), kpad, _lib.ptr(b), _lib.ptr(c), npad, rows, npad, kpad,
+                        0 if last else 1)
+                if a.is_cuda:
+                    _lib.check(L.lla_gemm_f32_ordered(*args, _lib.stream_ptr(dev)), "lla_gemm_f32_ordered")
+                else:
+                    _lib.check(L.lla_gemm_f32_ordered_host(*args), "lla_gemm_f32_ordered_host")
+            elif half:
                 rc = L.lla_gemm_f16_ex(_lib.ptr(a), a.shape[1], _lib.ptr(w), _lib.ptr(b), _lib.ptr(c), npad, None, 0,
                                        rows, npad, kpad, _lib.LLA_EPI_F16 if last else _lib.LLA_EPI_RELU_F16,
                                        _lib.stream_ptr(dev))
@@ -397,8 +413,8 @@ class MLP(nn.Module):
         returns the last layer's padded output [rows, Npad] (the result is its leading ``out_dim`` columns, row stride
         Npad), written into ``bufs[-1]`` when ``bufs`` (one [rows, Npad_i] fp32 tensor per layer) is given.  The same GEMM
         calls as ``forward`` on the same values: the same bits."""
-        if self.precision != "fp32":
-            raise NotImplementedError("forward_padded runs the fp32 MLP only")
+        if self.precision not in ("fp32", "ordered"):
+            raise NotImplementedError("forward_padded runs the fp32 and the ordered MLP only")
         packs = self._pack(a.device)
         if a.dtype != torch.float32 or a.dim() != 2 or a.shape[1] != packs[0][5] or not a.is_contiguous():
             raise ValueError(f"a must be a contiguous fp32 [rows, {packs[0][5]}] matrix")
@@ -429,6 +445,13 @@ class HRateHyperprior(HRateEstimator):
     keeps loading ``strict=True`` into the reference's module), and no string or container records it: strings written in
     one mode and read in the other -- like strings read with another state dict -- decode to wrong values without an
     error.
+
+    ``mlp_precision="ordered"`` (opt-in; see :class:`MLP`) is such a constructor argument too -- not in ``state_dict()``,
+    not recorded in any string or container, free to combine with ``coded_means``, and with the same warning: strings
+    written in one ``mlp_precision`` and read in another decode to wrong values without an error.  It gives both MLPs an
+    arithmetic a CPU reproduces bit for bit, so besides ``encode_device`` / ``decode_device`` / ``represent_device`` the
+    module offers ``encode_host`` / ``decode_host`` / ``represent_host`` (same layouts, same bytes, same values, no GPU), and
+    ``compress`` / ``decompress`` take them for CPU tensors.  With any other ``mlp_precision`` the host forms raise.
     """
 
     def __init__(self, z_dim, factor_dim=5, side_z_dim=None, is_pred_mean=True, mlp_precision="fp32",
@@ -455,6 +478,19 @@ class HRateHyperprior(HRateEstimator):
         side_encoder = MLP(self.z_dim, self.side_z_dim, **kwargs_mlp)
         z_encoder = MLP(self.side_z_dim, self.z_dim * (2 if self.is_pred_mean else 1), **kwargs_mlp)
         return side_encoder, z_encoder
+
+    def _exp_scaling(self):
+        """``mlp_precision="ordered"``, outside autograd: exp(scaling) is evaluated on the HOST in float64 wherever the
+        module lives (as ``EntropyBottleneck.device_tables`` does for the factorized model), so the coder on the GPU and
+        the one on a CPU hold the same fp32 factors.  Cached per parameter version: no copy per call."""
+        if self.mlp_precision != "ordered" or torch.is_grad_enabled():
+            return super()._exp_scaling()
+        key = (self.scaling.device, self.scaling._version, self.scaling.data_ptr())
+        cached = getattr(self, "_host_exp", None)
+        if cached is None or cached[0] != key:
+            es = torch.exp(self.scaling.detach().to("cpu", torch.float64)).float().to(self.scaling.device)
+            self._host_exp = cached = (key, es)
+        return cached[1]
 
     def _load_from_state_dict(self, state_dict, prefix, *args, **kwargs):
         try:
@@ -514,6 +550,11 @@ class HRateHyperprior(HRateEstimator):
         """rates.py:701-713 -> ``[z_strings, side_z_strings]``."""
         if not self.is_coder_updated:
             raise RuntimeError("call update() / prepare_compressor_() first")
+        if self.mlp_precision == "ordered" and not z.is_cuda:
+            payload, offsets = self.encode_host(z)
+            off, blob = offsets.numpy(), payload.numpy().tobytes()
+            rec = [blob[int(off[r]) + 4:int(off[r + 1])] for r in range(2 * z.shape[0])]
+            return [rec[0::2], rec[1::2]]
         z_in = self.process_z_in(z)
         side_z = self.side_encoder(z_in)
         side_z_strings = self.entropy_bottleneck.compress(side_z.contiguous())
@@ -527,6 +568,14 @@ class HRateHyperprior(HRateEstimator):
         """rates.py:715-724 -> z_hat [B, z_dim] fp32 on the GPU."""
         assert isinstance(all_strings, list) and len(all_strings) == 2
         z_strings, side_z_strings = all_strings
+        if self.mlp_precision == "ordered" and self.scaling.device.type != "cuda":
+            parts, off = [], [0]
+            for pair in zip(z_strings, side_z_strings, strict=True):
+                for s in pair:
+                    parts += [len(s).to_bytes(4, "big"), bytes(s)]
+                    off.append(off[-1] + 4 + len(s))
+            payload = torch.frombuffer(bytearray(b"".join(parts) + b"\0\0\0\0"), dtype=torch.uint8)
+            return self.decode_host(payload, torch.tensor(off, dtype=torch.int64), len(z_strings))
         indexes, means_hat = self.get_indexes_means_hat(side_z_strings)
         z_hat = self.gaussian_conditional.decompress(z_strings, indexes, means=means_hat)
         return self.process_z_out(z_hat.reshape(z_hat.shape[0], -1))
@@ -683,6 +732,158 @@ class HRateHyperprior(HRateEstimator):
         first = self.z_dim if self.coded_means == "predicted" else 0
         means = self.z_encoder(s_hat)[:, first:first + self.z_dim]
         return self.process_z_out(torch.round(z_in - means) + means)
+
+    # ---- host path (``mlp_precision="ordered"`` only): the device path's steps on CPU tensors with the library's host
+    # entry points -- the two MLPs on ``lla_gemm_f32_ordered_host`` (the device kernel's chain, bit for bit), the side
+    # records on the factorized host coder, the z records on the host twins of the conditional kernels.  Same layout, same
+    # bytes, same values as ``encode_device`` / ``decode_device`` / ``represent_device``; the module may live on either
+    # device (a compressor on the GPU decodes a container on the host with CPU copies of its tables and weights).
+    def _check_host_path(self, what):
+        if self.mlp_precision != "ordered":
+            raise NotImplementedError(
+                f'{what} needs mlp_precision="ordered" (this module runs {self.mlp_precision!r}): the table rows come '
+                "from z_encoder, and only the ordered MLP has an arithmetic a CPU reproduces bit for bit")
+        if not self.is_coder_updated:
+            raise RuntimeError("call update() / prepare_compressor_() first")
+        _require_coder(self.entropy_bottleneck)
+        _require_coder(self.gaussian_conditional)
+
+    def _host_params(self):
+        """CPU copies (contiguous numpy) of what ``_device_params`` and the two ``device_tables`` hold, cached like them."""
+        import numpy as np
+        p, ebt, gct = self._device_params(), self.entropy_bottleneck.device_tables(), self.gaussian_conditional.device_tables()
+        key = (id(p), id(ebt), id(gct))
+        cached = getattr(self, "_host_cache", None)
+        if cached is None or cached[0] != key:
+            host = lambda v: np.ascontiguousarray(v.detach().cpu().numpy()) if hasattr(v, "cpu") else v
+            h = dict(bias=host(p["bias"]), exp_scale=host(p["exp_scale"]), scale_table=host(p["scale_table"]),
+                     scale_bound=p["scale_bound"], eb={k: host(v) for k, v in ebt.items()},
+                     gc={k: host(v) for k, v in gct.items()})
+            self._host_cache = cached = (key, h, (p, ebt, gct))     # (the dicts are kept alive: their ids are the key)
+        return cached[1]
+
+    @staticmethod
+    def _host_z(z, C):
+        if z.dim() != 2 or z.shape[1] != C:
+            raise ValueError(f"z must be [B, {C}], got {tuple(z.shape)}")
+        if z.is_cuda:
+            raise RuntimeError("the host path takes CPU tensors (encode_device / represent_device take the GPU's)")
+        if z.dtype not in (torch.float16, torch.float32):
+            z = z.float()
+        return z.contiguous()
+
+    def _host_side(self, z, h):
+        """-> (z_in, side symbols int32 [B, S]) as ``encode_device`` derives them."""
+        z_in = (z.float() + torch.from_numpy(h["bias"])) * torch.from_numpy(h["exp_scale"])
+        side_z = self.side_encoder(z_in)
+        return z_in, torch.round(side_z - torch.from_numpy(h["eb"]["median"])[None, :]).to(torch.int32)
+
+    def _host_scales(self, side_sym, h):
+        """``_scales_of`` on the host: (z_encoder output fp32 [B, C or 2C] contiguous, scales / means pointers, pitch)."""
+        s_hat = side_sym.to(torch.float32) + torch.from_numpy(h["eb"]["median"])[None, :]
+        params = self.z_encoder(s_hat).float().contiguous()
+        means = ctypes.c_void_p(params.data_ptr() + 4 * self.z_dim) if self.coded_means == "predicted" else None
+        return params, means, params.stride(0)
+
+    @torch.no_grad()
+    def encode_host(self, z, want_symbols=False):
+        """``encode_device`` for a CPU tensor z [B, z_dim] fp16 / fp32, without a GPU: -> ``(payload, offsets)`` CPU tensors
+        in the same layout (uint8 interleaved length-prefixed records + 4 spare bytes, int64 [2B+1]), the same bytes.
+        ``want_symbols``: also ``dict(side_symbols, z_symbols, z_indexes)`` (int32 CPU tensors)."""
+        import numpy as np
+        self._check_host_path("encode_host")
+        z = self._host_z(z, self.z_dim)
+        h, L = self._host_params(), _lib.lib()
+        B, C, S = z.shape[0], self.z_dim, self.side_z_dim
+        P = lambda a: a.ctypes.data_as(ctypes.c_void_p)
+        _, side_sym = self._host_side(z, h)
+        params, means, ld = self._host_scales(side_sym, h)
+        z_sym = torch.empty((B, C), dtype=torch.int32) if want_symbols else None
+        z_idx = torch.empty((B, C), dtype=torch.int32) if want_symbols else None
+        eb, gc = h["eb"], h["gc"]
+
+        def records(call, what):      # size, then write (LLA_ECAP reports the size needed)
+            off = np.zeros(B + 1, dtype=np.uint64)
+            rc = call(None, 0, P(off))
+            if rc not in (_lib.LLA_OK, _lib.LLA_ECAP):
+                _lib.check(rc, what)
+            out = np.empty(max(int(off[-1]), 1), dtype=np.uint8)
+            _lib.check(call(P(out), out.size, P(off)), what)
+            return out.tobytes(), off
+
+        side_sym_np = np.ascontiguousarray(side_sym.numpy())
+        side, soff = records(lambda out, cap, off: L.lla_rans_encode_batch_host(
+            P(side_sym_np), B, S, P(eb["cdf"]), eb["W"], P(eb["cdf_len"]), P(eb["offset"]), 1, out, cap, off),
+            "lla_rans_encode_batch_host")
+        zrec, zoff = records(lambda out, cap, off: L.lla_gaussian_quantise_encode_host(
+            _lib.ptr(z), _lib.LLA_Z_F16 if z.dtype == torch.float16 else _lib.LLA_Z_F32, B, C, P(h["bias"]),
+            P(h["exp_scale"]), _lib.ptr(params), ld, means, ld, P(h["scale_table"]), h["scale_bound"], P(gc["cdf"]),
+            gc["T"], gc["W"], P(gc["cdf_len"]), P(gc["offset"]), 1, out, cap, off, _lib.ptr(z_sym), _lib.ptr(z_idx)),
+            "lla_gaussian_quantise_encode_host")
+        parts, offsets = [], np.zeros(2 * B + 1, dtype=np.int64)
+        for i in range(B):
+            parts += [zrec[int(zoff[i]):int(zoff[i + 1])], side[int(soff[i]):int(soff[i + 1])]]
+            offsets[2 * i + 1] = offsets[2 * i] + len(parts[-2])
+            offsets[2 * i + 2] = offsets[2 * i + 1] + len(parts[-1])
+        payload = torch.frombuffer(bytearray(b"".join(parts) + b"\0\0\0\0"), dtype=torch.uint8)
+        if want_symbols:
+            return payload, torch.from_numpy(offsets), dict(side_symbols=side_sym, z_symbols=z_sym, z_indexes=z_idx)
+        return payload, torch.from_numpy(offsets)
+
+    @torch.no_grad()
+    def decode_host(self, payload, offsets, B):
+        """``decode_device`` without a GPU: payload uint8 / offsets int64 [2B+1] CPU tensors (what ``encode_host`` returns,
+        or ``encode_device``'s copied to the host) -> z_hat [B, z_dim] fp32 CPU tensor, the same bits.  ValueError for
+        offsets that leave the payload or a malformed record."""
+        import numpy as np
+        self._check_host_path("decode_host")
+        if offsets.dtype != torch.int64 or offsets.numel() != 2 * B + 1:
+            raise ValueError("offsets must be int64 [2B+1]")
+        if payload.dtype != torch.uint8 or payload.dim() != 1:
+            raise ValueError("payload must be a 1-D uint8 tensor")
+        if payload.is_cuda or offsets.is_cuda:
+            raise RuntimeError("decode_host takes CPU tensors (decode_device takes the GPU's)")
+        body = np.ascontiguousarray(payload.numpy())
+        off = np.ascontiguousarray(offsets.numpy())
+        if B and (int(off[0]) < 0 or int(off[-1]) > body.size or bool((np.diff(off) < 0).any())):
+            raise ValueError("malformed rANS stream")      # (the host coder reads where the offsets point)
+        h, L = self._host_params(), _lib.lib()
+        C, S = self.z_dim, self.side_z_dim
+        P = lambda a: a.ctypes.data_as(ctypes.c_void_p)
+        eb, gc = h["eb"], h["gc"]
+        # the side records (odd ones), packed back to back for lla_rans_decode_batch_host
+        blob = body.tobytes()
+        side = [blob[int(off[2 * i + 1]):int(off[2 * i + 2])] for i in range(B)]
+        soff = np.zeros(B + 1, dtype=np.uint64)
+        np.cumsum(np.fromiter(map(len, side), dtype=np.uint64, count=B), out=soff[1:])
+        side_body = np.frombuffer(b"".join(side) + b"\0\0\0\0", dtype=np.uint8)
+        side_sym = np.zeros((B, S), dtype=np.int32)
+        status = np.zeros((2, max(B, 1)), dtype=np.int32)
+        _lib.check(L.lla_rans_decode_batch_host(P(side_body), P(soff), 1, B, S, P(eb["cdf"]), eb["W"], P(eb["cdf_len"]),
+                                                P(eb["offset"]), P(side_sym), P(status[0])), "lla_rans_decode_batch_host")
+        params, means, ld = self._host_scales(torch.from_numpy(side_sym), h)
+        z_hat = torch.empty((B, C), dtype=torch.float32)
+        off_u = off.astype(np.uint64)
+        _lib.check(L.lla_gaussian_decode_dequantise_host(
+            P(body), P(off_u), 1, 0, 2, B, C, P(h["bias"]), P(h["exp_scale"]), _lib.ptr(params), ld, means, ld,
+            P(h["scale_table"]), h["scale_bound"], P(gc["cdf"]), gc["T"], gc["W"], P(gc["cdf_len"]), P(gc["offset"]),
+            _lib.ptr(z_hat), P(status[1])), "lla_gaussian_decode_dequantise_host")
+        if B and int(status.max()) != 0:
+            raise ValueError("malformed rANS stream")
+        return z_hat
+
+    @torch.no_grad()
+    def represent_host(self, z):
+        """``represent_device`` for a CPU tensor: the z_hat that ``decode_host(*encode_host(z))`` gives, without coding."""
+        self._check_host_path("represent_host")
+        z = self._host_z(z, self.z_dim)
+        h = self._host_params()
+        z_in, side_sym = self._host_side(z, h)
+        params, _, _ = self._host_scales(side_sym, h)
+        first = self.z_dim if self.coded_means == "predicted" else 0
+        means = params[:, first:first + self.z_dim]
+        es, bias = torch.from_numpy(h["exp_scale"]), torch.from_numpy(h["bias"])
+        return (torch.round(z_in - means) + means) / es - bias
 
 
 def synthetic_hyperprior_state_dict(seed=0, z_dim=512):
